@@ -243,10 +243,10 @@ def parse_args(argv=None):
                          "itself through torch.distributed.run on 127.0.0.1")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=1,
                     help="the K-step timed region (barrier + synchronize on both sides, exactly K steps) is run this many times back to "
-                         "back; `value` / `ms_per_step` are the MEDIAN region, every region is listed under `repeats` (round-5 review: "
-                         "with the driver's --steps 20 one region is 8 ms -- a single sample is not a record)")
+                         "back; `value` / `ms_per_step` are the MEDIAN region, every region is listed under `repeats`.  Default 1: "
+                         "--steps K is then the number of timed steps; pass 5 for a median of five regions (5 x K timed steps)")
     ap.add_argument("--workload", default=None,
                     help="default: c2_hotdog_like (gs_mesh, BASELINE configs[1]/[2]) on one GPU, c4_ficus_like (gs_multi_mesh, "
                          "BASELINE configs[3]: 8 views sharded one per GPU) on several")
@@ -287,7 +287,49 @@ def parse_args(argv=None):
                     help="none: gradients are dropped after the (all-reduced) backward, the headline step; fused_adam / torch_adam: "
                          "also run optimizer.step() of the reference's training_setup() (train.py:147) with lr scaled to ~0 so "
                          "the scene, and with it the work per step, stays fixed")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rendered images, parameter gradients, "
+                         "the loss, the parameters after an optimizer step) as DIR/<name>.npy in float32 / float64, at most 64 MB in all: "
+                         "an array over its share of the budget is written as a fixed, seeded sample of its flattened entries.  The "
+                         "inputs are seeded, so two builds run with the same arguments can be compared output for output")
     return ap.parse_args(argv)
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def param_names(model, params):
+    """Attribute names of `params` on `model` (list attributes as `<name>_<i>`), in the order of `params`."""
+    by_id = {}
+    for name, v in vars(model).items():
+        if isinstance(v, torch.Tensor):
+            by_id.setdefault(id(v), name)
+        elif isinstance(v, (list, tuple)):
+            for i, t in enumerate(v):
+                if isinstance(t, torch.Tensor):
+                    by_id.setdefault(id(t), f"{name}_{i}")
+    return [by_id.get(id(p), f"param_{i}").lstrip("_") for i, p in enumerate(params)]
+
+
+def dump_outputs(directory, arrays):
+    """Write `arrays` (name -> tensor or None) as DIR/<name>.npy: float64 stays float64, everything else becomes float32.  Every
+    array gets an equal share of DUMP_BUDGET_BYTES; a larger one is written as the entries at a fixed, seeded, sorted sample of
+    flat indices (the same indices for the same size on every run).  Returns {name: [written entries, total entries]}."""
+    import numpy as np
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    os.makedirs(directory, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES - 256 * len(arrays)) // max(1, len(arrays))        # (256 B: room for each file's .npy header)
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        cap = share // a.itemsize
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(20261015).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a))
+        written[name] = [int(a.size), int(t.numel())]
+    return written
 
 
 def self_launch(args):
@@ -505,6 +547,9 @@ def main():
             model.update_alpha()
             model.prepare_scaling_rot()
             images = [render(c, model, pipe, bg)["render"] for c in cams]
+            if capture is not None:
+                capture.clear()
+                capture.update({f"image_{v}" if vps > 1 else "image": im for v, im in enumerate(images)})
             if exchange is not None:
                 exchange.watch(model.get_xyz)     # the gather starts inside backward, right after the last rasterizer backward
             if args.loss == "l1_ssim":
@@ -513,6 +558,8 @@ def main():
                     loss = loss + l1_ssim_loss(im, gt_image, 0.2)
                 loss = loss / (vps * world) if vps * world > 1 else loss
                 loss.backward(backward_seed(loss))          # (as games_hip.train does: a cached ones_like instead of a fill launch per step)
+                if capture is not None:
+                    capture["loss"] = loss.detach().double()
             else:
                 with torch.no_grad():                        # dL/dcolor = (image - 0.5) / (3HW), dense
                     grads = [torch.add(neg_half_norm, im, alpha=inv_norm) for im in images]      # one elementwise kernel each
@@ -525,15 +572,23 @@ def main():
             if packed is not None:
                 packed.finish(model.get_xyz, model.active_sh_degree)      # the step's ONE collective
                 packed.disable()
+            if capture is not None:
+                capture.update({f"grad_{n}": p.grad for n, p in zip(names, params)})
             if args.optimizer != "none":
                 model.optimizer.step()
                 model.optimizer.zero_grad(set_to_none=True)
+                if capture is not None:
+                    capture.update({f"param_{n}": p.detach().clone() for n, p in zip(names, params)})
             else:
                 for p in params:
                     p.grad = None
         return step, reducer
 
     rank_spread = {}
+    # --dump-outputs: the step keeps references to what it computed (None: it keeps nothing, the timed path is unchanged)
+    capture = {} if (args.dump_outputs and rank == 0) else None
+    names = param_names(model, params)
+    dumped = None
 
     def timed(step, steps, warmup, tag=None):
         """W untimed steps, then exactly K steps between barrier + synchronize on both sides; MAX over ranks.  `tag`: also record
@@ -583,12 +638,16 @@ def main():
                 frame[0] += 1
                 new_v = verts * (1.0 + 0.05 * math.sin(t))           # scripts/render_time_animated.py:68-87 style
                 if anim is not None:
-                    anim.render(new_v[faces], check=(frame[0] % 64 == 0))      # the frame's counts are read back every 64th frame
+                    out = anim.render(new_v[faces], check=(frame[0] % 64 == 0))      # the frame's counts are read back every 64th frame
                 elif fused_k0:
-                    render_frame(new_v, faces, cam, model, pipe, bg)         # mesh -> image: K0 inside the preprocess thread
+                    out = render_frame(new_v, faces, cam, model, pipe, bg)         # mesh -> image: K0 inside the preprocess thread
                 else:
-                    render_animated(None, new_v[faces], cam, model, pipe, bg)
+                    out = render_animated(None, new_v[faces], cam, model, pipe, bg)
+                if capture is not None:
+                    capture["image"] = out["render"] if isinstance(out, dict) else out
         el = timed(animate_step, args.steps, args.warmup)
+        if capture is not None:
+            dumped = dump_outputs(args.dump_outputs, capture)
         if rank == 0:
             print(json.dumps({"metric": "renders/s (fwd only, per-frame vertex animation + fused face->Gaussian + raster)",
                               "value": round(world * args.steps / el, 2), "unit": "renders/s", "n_gpus": world,
@@ -597,7 +656,8 @@ def main():
                               "config": {"workload": f"{desc['text']}, animate, {size}x{size}",
                                          "k0": ("inside preprocess_fwd (GmsRasterForwardArgs.mesh): no K0 launch, no vertices[faces] gather"
                                                 if (fused_k0 and anim is None) else ("inside preprocess_fwd, frame replayed as a hipGraph" if fused_k0 else "separate launch")),
-                                         "graph": ({"captures": anim.captures, **anim.status()} if anim is not None else None)}}), flush=True)
+                                         "graph": ({"captures": anim.captures, **anim.status()} if anim is not None else None)},
+                              **({"dumped_outputs": dumped} if dumped is not None else {})}), flush=True)
         if distributed:
             dist.destroy_process_group()
         return
@@ -635,6 +695,10 @@ def main():
     _wms, _wcalls = _Cw.c_double(0.0), _Cw.c_int64(0)
     _lib.load().gms_wait_stats(_Cw.byref(_wms), _Cw.byref(_wcalls), 0)
     host_wait_us_per_step = 1000.0 * _wms.value / max(1, args.steps * len(regions))
+    if capture is not None:          # what the last timed step computed, before any untimed step below overwrites it
+        torch.cuda.synchronize(device)
+        dumped = dump_outputs(args.dump_outputs, capture)
+        capture = None
     elapsed = sorted(regions)[len(regions) // 2]          # the median region (each one: exactly K steps, bracketed as the contract says)
     ms_per_step = 1000.0 * elapsed / args.steps
     value = world * vps * args.steps / elapsed
@@ -854,6 +918,8 @@ def main():
                                 "frac_of_8TBps": round(whole_bytes / (ms_per_step * 1e-3) / 8e12, 4)},
         }
         out.update(extra)
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline and desc["model"] == "gs_mesh":
             try:
                 out["cpu_baseline"] = cpu_baseline(workload, args.state)

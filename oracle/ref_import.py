@@ -20,6 +20,30 @@ def available() -> bool:
     return os.path.isdir(os.path.join(REFERENCE_ROOT, "games"))
 
 
+RENDERER_PACKAGES = ("gaussian_renderer", "gaussian_animated_renderer", "flame_gaussian_renderer", "gaussian_points_animated_renderer")
+
+
+def reference_call_sites(root=None):
+    """What the reference's renderers (renderer/<pkg>/__init__.py) ask of the rasterizer, read from their AST: the names they
+    import from `diff_gaussian_rasterization`, every `GaussianRasterizationSettings(...)` / `rasterizer(...)` /
+    `GaussianRasterizer(...)` call as [name, positional argument count, keyword names], and whether the result is unpacked
+    into `rendered_image, radii`.  tests/golden/make_golden.py stores this as tests/golden/reference_call_sites.json."""
+    import ast
+    root = root or REFERENCE_ROOT
+    sites = {}
+    for pkg in RENDERER_PACKAGES:
+        with open(os.path.join(root, "renderer", pkg, "__init__.py")) as f:
+            src = f.read()
+        tree = ast.parse(src)
+        imports = [sorted(a.name for a in n.names) for n in ast.walk(tree)
+                   if isinstance(n, ast.ImportFrom) and n.module == "diff_gaussian_rasterization"]
+        calls = [[c.func.id, len(c.args), [k.arg for k in c.keywords]] for c in ast.walk(tree)
+                 if isinstance(c, ast.Call) and isinstance(c.func, ast.Name)
+                 and c.func.id in ("GaussianRasterizationSettings", "rasterizer", "GaussianRasterizer")]
+        sites[pkg] = {"imports": imports, "calls": calls, "unpacks_rendered_image_radii": "rendered_image, radii" in src}
+    return sites
+
+
 def _stub(name, **attrs):
     m = types.ModuleType(name)
     for k, v in attrs.items():

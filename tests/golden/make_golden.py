@@ -16,10 +16,12 @@ What is pinned here (reference code executed, CPU, float32):
   stages.npz         eval_sh (utils/sh_utils.py:57), geom_transform_points (utils/graphics_utils.py:22),
                      build_covariance_from_scaling_rotation (scene/gaussian_model.py:27-31),
                      rot_to_quat_batch (utils/general_utils.py:43), getProjectionMatrix/getWorld2View2
+  reference_call_sites.json  the keyword names of the rasterizer calls in renderer/*/__init__.py (AST, --only-call-sites)
   loss.npz           l1_loss / ssim (utils/loss_utils.py:17-63) and the training loss of train.py:106-107 with its
                      autograd gradient w.r.t. the rendered image, on two image pairs
 The rasterizer itself cannot be pinned this way (source absent from the reference tree).
 """
+import json
 import os
 import sys
 
@@ -143,6 +145,12 @@ def loss_fixture(ref):
 
 
 def main():
+    # the reference renderers' rasterizer call sites (read from their AST, no code executed)
+    with open(os.path.join(HERE, "reference_call_sites.json"), "w") as f:
+        json.dump(ref_import.reference_call_sites(), f, indent=1)
+        f.write("\n")
+    if "--only-call-sites" in sys.argv:
+        return
     ref = ref_import.import_reference()
     torch.manual_seed(0)
     tonp = lambda d: {k: (v.numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in d.items()}

@@ -22,7 +22,7 @@ def _json_line(out):
 
 def test_single_gpu_line_has_the_contract_fields():
     r = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--workload", "small",
-                        "--profile-steps", "3"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--profile-steps", "3", "--repeats", "5"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
     assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["value"] > 0
@@ -40,6 +40,27 @@ def test_single_gpu_line_has_the_contract_fields():
     rp = d["repeats"]
     assert rp["n"] == 5 and len(rp["ms_per_step"]) == 5 and rp["min"] <= rp["median"] <= rp["max"] and rp["median"] == d["ms_per_step"]
     assert d["host_wait_us_per_step"] >= 0.0
+
+
+def test_dump_outputs_writes_what_the_last_timed_step_computed(tmp_path):
+    """--dump-outputs DIR: the image and every parameter gradient of the last timed step as float32 .npy files, 64 MB at most;
+    by default --steps K is the number of timed steps (one region)."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "4", "--warmup", "1", "--no-cpu-baseline", "--workload", "small",
+                        "--profile-steps", "0", "--dump-outputs", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _json_line(r.stdout)
+    assert d["steps"] == 4 and d["repeats"]["n"] == 1 and d["repeats"]["ms_per_step"] == [d["ms_per_step"]]
+    names = {"image", "grad_vertices", "grad_alpha", "grad_features_dc", "grad_features_rest", "grad_opacity", "grad_scale"}
+    assert {p.name for p in out.iterdir()} == {n + ".npy" for n in names} and set(d["dumped_outputs"]) == names
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    arrays = {n: np.load(out / (n + ".npy")) for n in names}
+    size = d["config"]["image"]
+    assert arrays["image"].shape == (3, size[0], size[1])
+    for n, a in arrays.items():
+        assert a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0, n
+    assert arrays["image"].min() >= 0.0
 
 
 def test_kernel_table_sums_to_no_more_than_the_step():
