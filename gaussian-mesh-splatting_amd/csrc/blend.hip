@@ -4,8 +4,8 @@
 // default 128); one work UNIT = (tile, segment).  A unit is walked by four independent waves, each owning an
 // 8x8 pixel quadrant of the 16x16 tile and launched as its OWN 64-thread block (the four quadrant blocks of a unit are
 // consecutive blocks of one XCD): no block barrier, no quadrant waiting at a barrier for a slower one, a finished
-// quadrant frees its slot, and the dispatcher places work at quadrant granularity.  (GMS_FWD_WPB=4 / GMS_BWD_WPB=4
-// select the older layout: one 256-thread block per unit, the four waves sharing one 256-entry queue.)
+// quadrant frees its slot, and the dispatcher places work at quadrant granularity.  (The older layout -- one 256-thread
+// block per unit, the four waves sharing one 256-entry queue -- was measured and removed; see docs/HISTORY.md.)
 // Compositing is associative, so the segments of a heavy tile (thousands of splats around mesh poles /
 // silhouettes) run on different CUs instead of serialising behind one block:
 //
@@ -59,10 +59,9 @@ __device__ __forceinline__ bool quadrant_hit(const SplatRec *recs, int j, int cn
 }
 
 // ------------------------------------------------------------------------------------ tloc
-template <int NE, int WPB>
+template <int NE>
 __device__ __forceinline__ void tloc_unit(const BlendGrid &g, const SplatRec *rec, const Unit &u, SplatRec *recs, int phase, int wave)
 {
-    constexpr int QN = WPB == 4 ? QUEUE : WAVE;
     if (u.nseg == 1 || u.seg == u.nseg - 1) return;
     // phase 0: the first tloc_head(L) segments of every tile; phase 1: the rest, unless the head already
     // finished every pixel of the tile (then the products are irrelevant: write 0, evaluate nothing)
@@ -74,16 +73,16 @@ __device__ __forceinline__ void tloc_unit(const BlendGrid &g, const SplatRec *re
     }
     const Pix p = pixel_of(g, u, wave);
     float Tl = 1.f;
-    for (uint32_t base = u.beg; base < u.end; base += QN) {
+    for (uint32_t base = u.beg; base < u.end; base += WAVE) {
         // once a pixel's segment product is below 1e-4 every later segment starts dead whatever the exact
         // value: a quadrant whose pixels are all there (or outside the image) stops evaluating
         const bool quad_done = __all(Tl < T_MIN || !p.inside);
-        if (WPB == 1 && quad_done) break;
-        if (WPB == 4) __syncthreads(); else wave_sync();
+        if (quad_done) break;
+        wave_sync();
         const uint32_t idx = base + qt;
-        if (qt < QN && idx < u.end) recs[qt] = rec[(uint32_t)g.keys[idx]];
-        if (WPB == 4) __syncthreads(); else wave_sync();
-        const int cnt = (int)min((uint32_t)QN, u.end - base);
+        if (qt < WAVE && idx < u.end) recs[qt] = rec[(uint32_t)g.keys[idx]];
+        wave_sync();
+        const int cnt = (int)min((uint32_t)WAVE, u.end - base);
         if (quad_done) continue;
         for (int chunk = 0; chunk < cnt; chunk += WAVE) {
             uint64_t mask = __ballot(quadrant_hit(recs, chunk + lane, cnt, p, dbg_on(g, 512u)));
@@ -130,10 +129,9 @@ __global__ void __launch_bounds__(BLOCK) blend_tloc_check_kernel(BlendGrid g)
 }
 
 // ------------------------------------------------------------------------------------ fwd
-template <int NE, int WPB>
+template <int NE>
 __device__ __forceinline__ void fwd_unit(const BlendGrid &g, const BlendFwdOut &o, const Unit &u, SplatRec *recs, int wave)
 {
-    constexpr int QN = WPB == 4 ? QUEUE : WAVE;
     const int qt = threadIdx.x, lane = qt & 63, tid = wave * WAVE + lane;
     const Pix p = pixel_of(g, u, wave);
 
@@ -154,13 +152,13 @@ __device__ __forceinline__ void fwd_unit(const BlendGrid &g, const BlendFwdOut &
     uint32_t last = 0;
     int alive = (!p.inside || dead_on_entry) ? 0 : 1;          // (gms_blend.h::quad_step_exec clears it when the stop rule fires)
 
-    for (uint32_t base = u.beg; base < u.end; base += QN) {
-        if (WPB == 4) { if (__syncthreads_and(alive == 0)) break; }
-        else { if (__all(alive == 0)) break; wave_sync(); }
+    for (uint32_t base = u.beg; base < u.end; base += WAVE) {
+        if (__all(alive == 0)) break;
+        wave_sync();
         const uint32_t idx = base + qt;
-        if (qt < QN && idx < u.end) recs[qt] = o.rec[(uint32_t)g.keys[idx]];
-        if (WPB == 4) __syncthreads(); else wave_sync();
-        const int cnt = (int)min((uint32_t)QN, u.end - base);
+        if (qt < WAVE && idx < u.end) recs[qt] = o.rec[(uint32_t)g.keys[idx]];
+        wave_sync();
+        const int cnt = (int)min((uint32_t)WAVE, u.end - base);
         if (__all(alive == 0)) continue;           // wave-uniform: this quadrant is finished
         for (int chunk = 0; chunk < cnt; chunk += WAVE) {
             uint64_t mask = __ballot(quadrant_hit(recs, chunk + lane, cnt, p, dbg_on(g, 512u)));
@@ -215,31 +213,31 @@ __device__ __forceinline__ void fwd_unit(const BlendGrid &g, const BlendFwdOut &
 
 // First launch: every unit that depends on nothing -- the exact walk of each tile's FIRST segment (single-segment
 // tiles are finished by it) and, for the middle segments of multi-segment tiles, the transmittance products.
-template <int NE, int WPB>
-__global__ void __launch_bounds__(WPB * WAVE) blend_head_kernel(BlendGrid g, BlendFwdOut o, int phase)
+template <int NE>
+__global__ void __launch_bounds__(WAVE) blend_head_kernel(BlendGrid g, BlendFwdOut o, int phase)
 {
-    __shared__ SplatRec recs[WPB == 4 ? QUEUE : WAVE];
+    __shared__ SplatRec recs[WAVE];
     Unit u;
-    const uint32_t bs = blockIdx.x >> 3;            // (WPB: see blend_bwd_kernel)
-    if (!load_unit_at(g, u, WPB == 4 ? bs : bs >> 2, blockIdx.x & 7u)) return;
-    const int wave = WPB == 4 ? (int)(threadIdx.x >> 6) : (int)(bs & 3u);
+    const uint32_t bs = blockIdx.x >> 3;            // (one block per (unit, quadrant): see blend_bwd_kernel)
+    if (!load_unit_at(g, u, bs >> 2, blockIdx.x & 7u)) return;
+    const int wave = (int)(bs & 3u);
     Stamp stamp(dbg_on(g, 256u) ? g.dbg_buf : nullptr);
-    if (u.seg == 0) { if (phase <= 0 && !dbg_on(g, 32u)) fwd_unit<NE, WPB>(g, o, u, recs, wave); }
-    else if (!dbg_on(g, 64u)) tloc_unit<NE, WPB>(g, o.rec, u, recs, phase, wave);
+    if (u.seg == 0) { if (phase <= 0 && !dbg_on(g, 32u)) fwd_unit<NE>(g, o, u, recs, wave); }
+    else if (!dbg_on(g, 64u)) tloc_unit<NE>(g, o.rec, u, recs, phase, wave);
 }
 
 // Second launch: segments 1.. of the multi-segment tiles, from the prefix product of the segments in front.
-template <int NE, int WPB>
-__global__ void __launch_bounds__(WPB * WAVE) blend_fwd_kernel(BlendGrid g, BlendFwdOut o)
+template <int NE>
+__global__ void __launch_bounds__(WAVE) blend_fwd_kernel(BlendGrid g, BlendFwdOut o)
 {
-    __shared__ SplatRec recs[WPB == 4 ? QUEUE : WAVE];
+    __shared__ SplatRec recs[WAVE];
     Unit u;
     const uint32_t bs = blockIdx.x >> 3;
-    if (!load_unit_at(g, u, WPB == 4 ? bs : bs >> 2, blockIdx.x & 7u)) return;
+    if (!load_unit_at(g, u, bs >> 2, blockIdx.x & 7u)) return;
     if (u.seg == 0) return;
-    const int wave = WPB == 4 ? (int)(threadIdx.x >> 6) : (int)(bs & 3u);
+    const int wave = (int)(bs & 3u);
     Stamp stamp(dbg_on(g, 128u) ? g.dbg_buf : nullptr);
-    fwd_unit<NE, WPB>(g, o, u, recs, wave);
+    fwd_unit<NE>(g, o, u, recs, wave);
 }
 
 // ------------------------------------------------------------------------------------ finalize
@@ -288,28 +286,26 @@ __global__ void __launch_bounds__(BLOCK) blend_finalize_kernel(BlendGrid g, Blen
 }
 
 // ------------------------------------------------------------------------------------ bwd
-// WPB = waves per block.  4: one block per unit, the four quadrant waves share one 256-entry queue and move through it
-// in lockstep (two block barriers per queue).  1: one block per (unit, quadrant) -- a wave on its own 64-entry queue: no
-// block barrier, no waiting for a slower quadrant, a quadrant that is done frees its slot, and the scheduler places
-// work at a quarter of the granularity; the price is that each quadrant gathers the unit's records itself (from L2).
+// One block per (unit, quadrant) -- a wave on its own 64-entry queue: no block barrier, no waiting for a slower quadrant, a
+// quadrant that is done frees its slot, and the scheduler places work at a quarter of the granularity; the price is that
+// each quadrant gathers the unit's records itself (from L2).  (One block per unit, the four waves moving through one
+// 256-entry queue in lockstep, was measured and removed; see docs/HISTORY.md.)
 // FAULT: 0 in production; 2 = the negative control "drop the colour composited behind a segment restart" (gmsplat.h,
 // gms_set_fault): a separate instantiation, so the production kernel carries no fault branch.
 // DET (deterministic mode, gmsplat.h): the ten totals of a (quadrant wave, splat) pair are STORED into the partial record of
 // (instance, quadrant) -- a.part[(sorted position * 4 + quadrant) * 16 + field], visited exactly once per frame, zero-filled by
 // the host -- instead of being added to the Gaussian's record with atomics.
-template <bool INVD, int NE, int WPB, int FAULT = 0, bool DET = false>
-__global__ void __launch_bounds__(WPB * WAVE) blend_bwd_kernel(BlendGrid g, BlendBwdArgs a)
+template <bool INVD, int NE, int FAULT = 0, bool DET = false>
+__global__ void __launch_bounds__(WAVE) blend_bwd_kernel(BlendGrid g, BlendBwdArgs a)
 {
-    constexpr int QN = WPB == 4 ? QUEUE : WAVE;
-    __shared__ SplatRec recs[QN];
-    __shared__ uint32_t ids[QN];
-    __shared__ uint32_t wave_max[4];
+    __shared__ SplatRec recs[WAVE];
+    __shared__ uint32_t ids[WAVE];
     Unit u;
-    // WPB == 1: the four quadrants of a unit are consecutive blocks of ONE XCD (they gather the same records)
+    // the four quadrants of a unit are consecutive blocks of ONE XCD (they gather the same records)
     const uint32_t bs = blockIdx.x >> 3;
-    if (!load_unit_at(g, u, WPB == 4 ? bs : bs >> 2, blockIdx.x & 7u)) return;
+    if (!load_unit_at(g, u, bs >> 2, blockIdx.x & 7u)) return;
     if (u.end <= u.beg) return;
-    const int qt = threadIdx.x, lane = qt & 63, wave = WPB == 4 ? qt >> 6 : (int)(bs & 3u);
+    const int qt = threadIdx.x, lane = qt & 63, wave = (int)(bs & 3u);
     const int tid = wave * WAVE + lane;                  // pixel index inside the tile (quadrant-major)
     Stamp stamp(dbg_on(g, 16u) ? g.dbg_buf : nullptr);
     const Pix p = pixel_of(g, u, wave);
@@ -382,12 +378,7 @@ __global__ void __launch_bounds__(WPB * WAVE) blend_bwd_kernel(BlendGrid g, Blen
     m = m > seg_lo ? m : 0u;                       // 0 = this pixel has nothing in this unit
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off));
-    uint32_t top = m;
-    if (WPB == 4) {
-        if (lane == 0) wave_max[wave] = m;
-        __syncthreads();
-        top = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
-    }
+    const uint32_t top = m;
     if (top == 0) return;
     if (dbg_on(g, 2u)) return;                              // experiment: prologue only
 
@@ -453,16 +444,16 @@ __global__ void __launch_bounds__(WPB * WAVE) blend_bwd_kernel(BlendGrid g, Blen
     }
     };
 
-    for (uint32_t hi = top; hi > seg_lo; hi = (hi - seg_lo) > QN ? hi - QN : seg_lo) {
-        const int cnt = (int)min((uint32_t)QN, hi - seg_lo);
-        if (WPB == 4) __syncthreads(); else wave_sync();     // previous queue fully consumed
+    for (uint32_t hi = top; hi > seg_lo; hi = (hi - seg_lo) > WAVE ? hi - WAVE : seg_lo) {
+        const int cnt = (int)min((uint32_t)WAVE, hi - seg_lo);
+        wave_sync();                                  // previous queue fully consumed
         if (qt < cnt) {
             const uint32_t e = hi - 1 - qt;           // queue slot 0 = backmost entry
             const uint32_t id = (uint32_t)g.keys[u.tile_beg + e];
             ids[qt] = id;
             recs[qt] = a.rec[id];
         }
-        if (WPB == 4) __syncthreads(); else wave_sync();
+        wave_sync();
         if (m == 0) continue;                         // wave-uniform: quadrant has nothing in this unit
         for (int chunk = 0; chunk < cnt; chunk += WAVE) {
             // m = furthest position any pixel of this quadrant composited: entries behind it are dead here
@@ -490,39 +481,25 @@ void experiment_switches(BlendGrid &g, uint32_t buf_bits, hipStream_t stream)
 }
 int32_t launch_blend_forward(const BlendGrid &g_in, const BlendFwdOut &o, uint32_t max_units, bool debug, hipStream_t stream)
 {
+    BlendGrid g = g_in;
+    experiment_switches(g, 128u | 256u, stream);
     // two-phase transmittance products pay off when tiles are deep on average (> 2 segments per tile over the
     // whole image); shallow scenes take one launch
-    static int dbg = -1;
-    if (dbg < 0) { const char *e = getenv("GMS_DBG"); dbg = (GMS_EXPERIMENTS && e) ? atoi(e) : 0; }
-    BlendGrid g = g_in;
-    g.dbg = (uint32_t)dbg;
-    g.dbg_buf = nullptr;
-    if (dbg & (128 | 256)) {
-        if (!g_dbg_buf) (void)hipMalloc((void **)&g_dbg_buf, DBG_BYTES);
-        if (g_dbg_buf) { (void)hipMemsetAsync(g_dbg_buf, 0, DBG_BYTES, stream); g.dbg_buf = g_dbg_buf; }
-    }
     static int deep_env = -2;
     if (deep_env == -2) { const char *e = getenv("GMS_DEEP"); deep_env = e ? atoi(e) : -1; }
     const bool deep = deep_env >= 0 ? deep_env != 0 : g.capacity > 512ull * (uint64_t)g.T;
     const unsigned blocks = blend_grid_units(max_units);
-    static int trip = -1;
-    if (trip < 0) { const char *e = getenv("GMS_TRIP"); trip = e ? atoi(e) : 4; }
-    static int wpb = -1;
-    if (wpb < 0) { const char *e = getenv("GMS_FWD_WPB"); wpb = (e && atoi(e) == 4) ? 4 : 1; }
-    auto head = wpb == 4 ? (trip == 2 ? blend_head_kernel<2, 4> : blend_head_kernel<4, 4>)
-                         : (trip == 2 ? blend_head_kernel<2, 1> : blend_head_kernel<4, 1>);
-    auto fwd2 = wpb == 4 ? (trip == 2 ? blend_fwd_kernel<2, 4> : blend_fwd_kernel<4, 4>)
-                         : (trip == 2 ? blend_fwd_kernel<2, 1> : blend_fwd_kernel<4, 1>);
-    const unsigned wblocks = wpb == 4 ? blocks : 4u * blocks, wthreads = wpb == 4 ? BLOCK : WAVE;
+    auto head = blend_head_kernel<4>;          // (4 entries per trip)
+    const unsigned wblocks = 4u * blocks;      // one 64-thread block per (unit, quadrant)
     if (deep) {     // deep scene: head segments, tile-dead check, then the tail segments of the tiles still alive
-        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<wblocks, wthreads, 0, stream>>>(g, o, 0));
+        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<wblocks, WAVE, 0, stream>>>(g, o, 0));
         GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, blend_tloc_check_kernel<<<(unsigned)g.T, BLOCK, 0, stream>>>(g));
-        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<wblocks, wthreads, 0, stream>>>(g, o, 1));
+        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<wblocks, WAVE, 0, stream>>>(g, o, 1));
     } else {
-        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<wblocks, wthreads, 0, stream>>>(g, o, -1));
+        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<wblocks, WAVE, 0, stream>>>(g, o, -1));
     }
     GMS_KERNEL_CHECK(debug, stream, "blend_head");
-    GMS_LAUNCH(GMS_K_BLEND_FWD, stream, fwd2<<<wblocks, wthreads, 0, stream>>>(g, o));
+    GMS_LAUNCH(GMS_K_BLEND_FWD, stream, blend_fwd_kernel<4><<<wblocks, WAVE, 0, stream>>>(g, o));
     GMS_KERNEL_CHECK(debug, stream, "blend_fwd");
     GMS_LAUNCH(GMS_K_BLEND_FINALIZE, stream, blend_finalize_kernel<<<(unsigned)g.T, BLOCK, 0, stream>>>(g, o));
     GMS_KERNEL_CHECK(debug, stream, "blend_finalize");
@@ -532,32 +509,16 @@ int32_t launch_blend_forward(const BlendGrid &g_in, const BlendFwdOut &o, uint32
 int32_t launch_blend_backward(const BlendGrid &g_in, const BlendBwdArgs &a, uint32_t max_units, bool debug, hipStream_t stream)
 {
     BlendGrid g = g_in;
-    static int dbg = -1;
-    if (dbg < 0) { const char *e = getenv("GMS_DBG"); dbg = (GMS_EXPERIMENTS && e) ? atoi(e) : 0; }
-    g.dbg = (uint32_t)dbg;
-    g.dbg_buf = nullptr;
-    if (dbg & 16) {
-        if (!g_dbg_buf) (void)hipMalloc((void **)&g_dbg_buf, DBG_BYTES);
-        if (g_dbg_buf) { (void)hipMemsetAsync(g_dbg_buf, 0, DBG_BYTES, stream); g.dbg_buf = g_dbg_buf; }
-    }
+    experiment_switches(g, 16u, stream);
     const unsigned blocks = blend_grid_units(max_units);
-    static int trip = -1;
-    if (trip < 0) { const char *e = getenv("GMS_TRIP_BWD"); trip = e ? atoi(e) : 4; }
     const bool invd = a.has_invd && a.dL_dinvd;
-    static int wpb = -1;
-    if (wpb < 0) { const char *e = getenv("GMS_BWD_WPB"); wpb = (e && atoi(e) == 4) ? 4 : 1; }
     if (a.part) {                           // deterministic mode (gmsplat.h): stores into per-(instance, quadrant) partial records
-        if (invd) GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (blend_bwd_kernel<true, 4, 1, 0, true><<<4u * blocks, WAVE, 0, stream>>>(g, a)));
-        else GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (blend_bwd_kernel<false, 4, 1, 0, true><<<4u * blocks, WAVE, 0, stream>>>(g, a)));
+        if (invd) GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (blend_bwd_kernel<true, 4, 0, true><<<4u * blocks, WAVE, 0, stream>>>(g, a)));
+        else GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (blend_bwd_kernel<false, 4, 0, true><<<4u * blocks, WAVE, 0, stream>>>(g, a)));
     } else if (fault_mode() == 2 && !invd) {       // negative control (gms_set_fault): its own instantiation
-        GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (blend_bwd_kernel<false, 4, 1, 2><<<4u * blocks, WAVE, 0, stream>>>(g, a)));
-    } else if (wpb == 4) {
-        auto kern = trip == 4 ? (invd ? blend_bwd_kernel<true, 4, 4> : blend_bwd_kernel<false, 4, 4>)
-                              : (invd ? blend_bwd_kernel<true, 2, 4> : blend_bwd_kernel<false, 2, 4>);
-        GMS_LAUNCH(GMS_K_BLEND_BWD, stream, kern<<<blocks, BLOCK, 0, stream>>>(g, a));
+        GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (blend_bwd_kernel<false, 4, 2><<<4u * blocks, WAVE, 0, stream>>>(g, a)));
     } else {
-        auto kern = trip == 4 ? (invd ? blend_bwd_kernel<true, 4, 1> : blend_bwd_kernel<false, 4, 1>)
-                              : (invd ? blend_bwd_kernel<true, 2, 1> : blend_bwd_kernel<false, 2, 1>);
+        auto kern = invd ? blend_bwd_kernel<true, 4> : blend_bwd_kernel<false, 4>;          // (4 entries per trip)
         GMS_LAUNCH(GMS_K_BLEND_BWD, stream, kern<<<4u * blocks, WAVE, 0, stream>>>(g, a));
     }
     GMS_KERNEL_CHECK(debug, stream, "blend_bwd");

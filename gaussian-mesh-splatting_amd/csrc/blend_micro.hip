@@ -20,9 +20,9 @@
 //                  the segment-parallel scheme of blend.hip unchanged -- first segments walked exactly, transmittance
 //                  products of the middle segments, exact walk of segments 1.. from the prefix product, partial sums in
 //                  order, backward restarted at segment boundaries.
-//   backward sums  go to an LDS table indexed by the splat's entry in the unit (ds_add_f32) and leave the block as ONE set of
-//                  global atomics per (unit, entry): 5.3 M global float atomics per frame instead of the 16.6 M a per-(block,
-//                  splat) atomic would issue.
+//   backward sums  go to an LDS table indexed by the splat's entry in the unit (64-bit fixed point since round 5, below) and
+//                  leave the block as ONE set of global atomics per (unit, entry): 5.3 M global float atomics per frame instead
+//                  of the 16.6 M a per-(block, splat) atomic would issue.
 //
 // Positions.  n_contrib holds, per pixel, seg * L + (index in the block's list of that segment) + 1 of the last splat
 // applied: monotone along the block's concatenated lists, which is all the backward needs.
@@ -166,15 +166,13 @@ __device__ __forceinline__ float dpp_mov(float v)
 // partner lanes AND halves the number of live registers, 29 VALU in all.  Partners: lane ^ 8 (row_ror:8), 7 - lane within
 // the half row (row_half_mirror), lane ^ 2, lane ^ 1 (quad_perm).  Result: lane i of the row holds the row total of
 //   i = 0: v0   8: v5   4: v3   12: v8   2: v1   10: v6   6: v4   14: v9   odd i < 8: v2   odd i > 8: v7
-#ifndef GMS_REDUCE_BANKMASK
-#define GMS_REDUCE_BANKMASK 1
-#endif
 // One stage of the transposing reduction for a pair of values (a, b): the lanes whose stage bit is clear end up with a + a[partner], the
 // others with b + b[partner].  The stage bit is constant over a DPP BANK (four lanes) for the first two stages -- lane bit 3 (banks 2, 3)
 // with row_ror:8, lane bit 2 (banks 1, 3) with row_half_mirror -- so two DPP adds with complementary bank masks write the two halves
 // -- a disabled bank keeps what the register holds -- instead of two v_cndmask selects and one DPP add: the kernel is bound by VALU issue
-// (tools/valu_bench.hip: plain 1.2 ns, DPP 1.76 ns per wave-instruction) and the selects were a third of the reduction.  Same sums bit for
-// bit (a + b == b + a).  The s_nop covers the two wait states a DPP read needs behind the VALU write of its source.
+// (tools/valu_bench.hip: plain 1.2 ns, DPP 1.76 ns per wave-instruction) and the selects were a third of the reduction (the select form
+// was measured, then removed: docs/HISTORY.md).  Same sums bit for bit (a + b == b + a).  The s_nop covers the two wait states a DPP read
+// needs behind the VALU write of its source.
 #define GMS_BANK_PAIR(D, A, B, CTRL, LO, HI)                                                                                          \
     "v_add_f32_dpp " D ", " A ", " A " " CTRL " row_mask:0xf bank_mask:" LO "\n\tv_add_f32_dpp " D ", " B ", " B " " CTRL " row_mask:0xf bank_mask:" HI "\n\t"
 // five pairs (v[k], v[k + 5]) over row_ror:8: lanes 0-7 keep the sums of v[k], lanes 8-15 those of v[k + 5].  NINE: v[9] (the
@@ -207,25 +205,13 @@ __device__ __forceinline__ void bank_stage_half_mirror(float a0, float b0, float
 }
 
 template <bool NINE = false>
-__device__ __forceinline__ float row_reduce10(const float *v, bool b3, bool b2, bool b1, bool b0)
+__device__ __forceinline__ float row_reduce10(const float *v, bool b1, bool b0)
 {
     float u[5];
-#if GMS_REDUCE_BANKMASK
     bank_stage_ror8<NINE>(v, u);
     float w0, w1;
     bank_stage_half_mirror(u[0], u[3], u[1], u[4], w0, w1);
     const float w2 = u[2] + dpp_mov<0x141>(u[2]);
-    (void)b3; (void)b2;
-#else
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-        const float keep = b3 ? v[k + 5] : v[k], send = b3 ? v[k] : v[k + 5];
-        u[k] = keep + dpp_mov<0x128>(send);
-    }
-    const float w0 = (b2 ? u[3] : u[0]) + dpp_mov<0x141>(b2 ? u[0] : u[3]);
-    const float w1 = (b2 ? u[4] : u[1]) + dpp_mov<0x141>(b2 ? u[1] : u[4]);
-    const float w2 = u[2] + dpp_mov<0x141>(u[2]);
-#endif
     const float x0 = (b1 ? w1 : w0) + dpp_mov<0x4E>(b1 ? w0 : w1);
     const float x1 = w2 + dpp_mov<0x4E>(w2);
     return (b0 ? x1 : x0) + dpp_mov<0xB1>(b0 ? x0 : x1);
@@ -258,21 +244,19 @@ __device__ __forceinline__ void set_tail(WideTail &d, float b, float invd) { d.v
 __device__ __forceinline__ float2 get_tail(const WideTail &d) { return d.v; }
 template <bool WITHD, bool WIDE> struct RecTailSel { using type = typename RecTail<WITHD>::type; };
 template <> struct RecTailSel<true, true> { using type = WideTail; };
-template <bool WITHD, int LM = LMAX, bool WIDE = false>
+template <bool WITHD, bool WIDE = false>
 struct UnitRecsT {
-    static constexpr int CAP = LM;      // entries the image holds (the frame's segment length must not exceed it)
-    float4 ra[LM];             // pix.x, pix.y, conic A, conic B
-    float4 rb[LM];             // conic C, opacity', r, g
-    typename RecTailSel<WITHD, WIDE>::type rc[LM];
-    uint8_t list[16][LM];      // per 4x4 block: the entries that reach it, in list (depth) order
+    float4 ra[LMAX];           // pix.x, pix.y, conic A, conic B
+    float4 rb[LMAX];           // conic C, opacity', r, g
+    typename RecTailSel<WITHD, WIDE>::type rc[LMAX];
+    uint8_t list[16][LMAX];    // per 4x4 block: the entries that reach it, in list (depth) order
     uint16_t ocnt[16];         // list lengths, longest first
     uint8_t order[16];         // ... and whose they are
     uint8_t wcnt4[16][4];      // staging: per block, the hits of each of the four waves (<= 64): one dword per block
 };
-using UnitRecs = UnitRecsT<true, LMAX, true>;      // (the forward launches)
+using UnitRecs = UnitRecsT<true, true>;      // (the forward launches)
 
 template <int NE> __device__ __forceinline__ uint32_t list_load(const uint8_t *lst, uint32_t pos);
-template <> __device__ __forceinline__ uint32_t list_load<1>(const uint8_t *lst, uint32_t pos) { return lst[pos]; }
 template <> __device__ __forceinline__ uint32_t list_load<2>(const uint8_t *lst, uint32_t pos) { return *reinterpret_cast<const uint16_t *>(lst + pos); }
 template <> __device__ __forceinline__ uint32_t list_load<4>(const uint8_t *lst, uint32_t pos) { return *reinterpret_cast<const uint32_t *>(lst + pos); }
 
@@ -282,8 +266,8 @@ template <> __device__ __forceinline__ uint32_t list_load<4>(const uint8_t *lst,
 // `cmax_out` (forward launches): the largest |colour component| of the unit's splats is folded into the tile's maximum
 // (ImageState::tile_cmax; one integer atomic per wave), which the backward needs to bound the colour behind a splat.
 // Returns the Gaussian id of the thread's entry.
-template <bool FILTER, bool WITHD, int LM, bool WIDE>
-__device__ __forceinline__ uint32_t unit_stage(const BlendGrid &g, const Unit &u, UnitRecsT<WITHD, LM, WIDE> &S, const SplatRec *rec, uint32_t *cmax_out,
+template <bool FILTER, bool WITHD, bool WIDE>
+__device__ __forceinline__ uint32_t unit_stage(const BlendGrid &g, const Unit &u, UnitRecsT<WITHD, WIDE> &S, const SplatRec *rec, uint32_t *cmax_out,
                                                Phases *ph = nullptr)          // (make EXPERIMENTS=1: stamps 3 = records in, 4 = counts exchanged)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -298,7 +282,7 @@ __device__ __forceinline__ uint32_t unit_stage(const BlendGrid &g, const Unit &u
         if (FILTER) { mask = block_mask(r, (float)(u.tx * TILE), (float)(u.ty * TILE)); mm[u.beg + tid] = (uint16_t)mask; }
         S.ra[tid] = r.q0; S.rb[tid] = r.q1; set_tail(S.rc[tid], r.q2.x, r.q2.y);
         cm = fmaxf(fmaxf(fabsf(r.q1.z), fabsf(r.q1.w)), fabsf(r.q2.x));
-    } else if (tid < LM) {
+    } else if (tid < LMAX) {
         // a row that idles behind the end of its list reads whatever byte lies there: every record it can name must be finite
         S.ra[tid] = make_float4(0.f, 0.f, 0.f, 0.f); S.rb[tid] = make_float4(0.f, 0.f, 0.f, 0.f); set_tail(S.rc[tid], 0.f, 0.f);
     }
@@ -590,7 +574,7 @@ __global__ void __launch_bounds__(BLOCK) micro_fwd_kernel(BlendGrid g, BlendFwdO
 // conversion alone: a float multiply by that constant, a conversion to double, the add of the magic number 1.5 * 2^52 and one integer
 // add on the high word -- four instructions per entry.  Measured on the way (HIP events): exponents from every entry's own centre,
 // mantissas shifted by hand, 58 bits: 189 us (4 blocks per CU: 32.1 KB of LDS is 152 bytes too many for five); unit-level exponents,
-// hand-shifted mantissas: 149 us; float scaling + magic number with the exponent of every entry's own opacity (GMS_FX_ENTRY_OPACITY=1):
+// hand-shifted mantissas: 149 us; float scaling + magic number with the exponent of every entry's own opacity:
 // 133 us; this form: 126 us; the float table it replaces: 139-142 us.  The bounds are loose by orders of magnitude on purpose: a value
 // 2^23 below its bound still carries 24 bits, and what lies far below is under the 1e-6 floor of the parity criterion.
 // (fx_exp, fx_scale_exp, fx_from_float, fx_to_float, FxTile, fx_field_base, fx_field_kind live in gms_blend.h: the test hooks run the very
@@ -598,45 +582,33 @@ __global__ void __launch_bounds__(BLOCK) micro_fwd_kernel(BlendGrid g, BlendFwdO
 
 // Backward.  The rows of a wave are aligned at the BOTTOM of their lists: global trip position `pos` is the same list index
 // for every row (rows whose list ends below it idle), so a trip's entry bytes are one aligned LDS read per NE entries.
-// FIXED (default): the gradient table is 64-bit fixed point (above), integer LDS atomics; FIXED = false keeps the float table of
-// rounds 3-4 (ds_add_f32; GMS_BWD_FIXED=0).  DET (deterministic mode, gmsplat.h): the fixed-point table -- integer sums do not depend
-// on the order of the adds, so the table IS deterministic (rounds 3-4 kept one float table per wave and added the rows one after
-// the other: 55 KB of LDS, 235 us) -- and a flush that stores ONE partial record per instance at the instance's position in the
-// sorted list instead of adding to the Gaussian's record with float atomics.
-#ifndef GMS_FX_ENTRY_OPACITY
-#define GMS_FX_ENTRY_OPACITY 0
-#endif
-constexpr bool FX_ENTRY_OPACITY = GMS_FX_ENTRY_OPACITY != 0;      // 1: the exponent of every entry's own opacity (3 more instructions per entry, up to 8 bits tighter)
-template <bool INVD, int NE, int FAULT, bool DET = false, bool FIXED = true, int LM = LMAX>
+// The gradient table is 64-bit fixed point (above), integer LDS atomics (the float table of rounds 3-4, ds_add_f32, was measured and
+// removed; see docs/HISTORY.md).  DET (deterministic mode, gmsplat.h): the same table -- integer sums do not depend on the order of
+// the adds, so the table IS deterministic (rounds 3-4 kept one float table per wave and added the rows one after the other: 55 KB of
+// LDS, 235 us) -- and a flush that stores ONE partial record per instance at the instance's position in the sorted list instead of
+// adding to the Gaussian's record with float atomics.
+template <bool INVD, int NE, int FAULT, bool DET = false>
 __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdArgs a)
 {
-    static_assert(!DET || FIXED, "the deterministic mode is built on the fixed-point table");
     constexpr int NF = INVD ? 10 : 9;                       // fields per entry of the fixed-point table (GRAD_ID last)
-    constexpr uint32_t EMASK = (uint32_t)LM - 1u;           // (LM < 256: a stale list byte behind a row's end must still name a record of the image)
-    __shared__ UnitRecsT<INVD, LM> S;
-    __shared__ __attribute__((aligned(8))) unsigned char table_mem[FIXED ? LM * NF * 8 : LM * 10 * 4];
-    __shared__ uint32_t tile_max[5];                        // FIXED: bits of the unit's largest sum_c |dL/dpixel_c|, |dL/dinvdepth|,
-                                                            //        centre-to-corner distances in x and in y
+    __shared__ UnitRecsT<INVD> S;
+    __shared__ __attribute__((aligned(8))) unsigned char table_mem[LMAX * NF * 8];
+    __shared__ uint32_t tile_max[5];                        // bits of the unit's largest sum_c |dL/dpixel_c|, |dL/dinvdepth|,
+                                                            // centre-to-corner distances in x and in y, opacity
     long long *const fxt = reinterpret_cast<long long *>(table_mem);
-    float *const table_all = reinterpret_cast<float *>(table_mem);
     uint32_t *const uid = reinterpret_cast<uint32_t *>(S.rc);          // (written after the walks: the tails are dead by then)
     Phases ph(g);
     ph.mark(0);
     Unit u;
     if (!load_unit_at(g, u, blockIdx.x >> 3, blockIdx.x & 7u)) return;
     if (u.end <= u.beg) return;
-    if (u.end - u.beg > (uint32_t)LM) return;               // (host picks the instantiation from the frame's segment length)
+    if (u.end - u.beg > (uint32_t)LMAX) return;             // (the host launches these kernels only on frames whose segment length fits)
     const size_t HW = (size_t)g.W * g.H;
-    if (FIXED) {
-        for (int k = threadIdx.x; k < LM * NF; k += BLOCK) fxt[k] = 0ll;
-        if (threadIdx.x < 5) tile_max[threadIdx.x] = 0u;
-    } else {
-        for (int k = threadIdx.x; k < LM * 10; k += BLOCK) table_all[k] = 0.f;
-    }
+    for (int k = threadIdx.x; k < LMAX * NF; k += BLOCK) fxt[k] = 0ll;
+    if (threadIdx.x < 5) tile_max[threadIdx.x] = 0u;
     const uint32_t my_id = unit_stage<false, INVD>(g, u, S, a.rec, nullptr);          // (its barriers also order the table clear)
     ph.mark(1);
     const int q = (int)(((threadIdx.x >> 6) + (blockIdx.x >> 3)) & 3u);
-    float *const table = table_all;
     const int lane = threadIdx.x & 63, row = lane >> 4, li = lane & 15;
     const MPix p = micro_pixel(g, u.tx, u.ty, (int)S.order[4 * q + row], li);
     const size_t pid = (size_t)p.yi * g.W + p.xi;
@@ -649,33 +621,31 @@ __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdA
     }
     const float Tfinal_bgdot = Tfinal * (a.bg[0] * dp0 + a.bg[1] * dp1 + a.bg[2] * dp2);
     FxTile fx = {0, 0, 0, 0, 0};
-    if (FIXED) {
-        // the unit's bounds: largest sum_c |dL/dpixel_c| (the block's 256 lanes hold the tile's 256 pixels), |dL/dinvdepth|, and
-        // centre-to-corner distances of its splats (entry threadIdx.x; the records behind the unit's end are zero)
-        const float tx0 = (float)(u.tx * TILE), ty0 = (float)(u.ty * TILE);
-        const float4 mine = S.ra[threadIdx.x & EMASK];
-        const bool real = (uint32_t)threadIdx.x < u.end - u.beg;
-        const float m_d1 = wave_max_to_lane63((fabsf(dp0) + fabsf(dp1)) + fabsf(dp2));
-        const float m_x = wave_max_to_lane63(real ? fmaxf(fabsf(mine.x - tx0), fabsf(mine.x - tx0 - 15.f)) + 1.f : 1.f);
-        const float m_y = wave_max_to_lane63(real ? fmaxf(fabsf(mine.y - ty0), fabsf(mine.y - ty0 - 15.f)) + 1.f : 1.f);
-        const float m_dd = INVD ? wave_max_to_lane63(fabsf(dinvd)) : 0.f;
-        const float m_op = FX_ENTRY_OPACITY ? 0.f : wave_max_to_lane63(real ? fabsf(S.rb[threadIdx.x & EMASK].y) : 0.f);
-        if (lane == 63) {          // (non-negative floats order like their bits; integer LDS atomics run at the rate of stores)
-            atomicMax(&tile_max[0], __float_as_uint(m_d1)); if (INVD) atomicMax(&tile_max[1], __float_as_uint(m_dd));
-            atomicMax(&tile_max[2], __float_as_uint(m_x)); atomicMax(&tile_max[3], __float_as_uint(m_y));
-            if (!FX_ENTRY_OPACITY) atomicMax(&tile_max[4], __float_as_uint(m_op));
-        }
-        __syncthreads();
-        const float D1 = __uint_as_float(tile_max[0]), Dd = INVD ? __uint_as_float(tile_max[1]) : 0.f;
-        const float cmax = __uint_as_float(g.tile_cmax[u.tile]);
-        const float bgm = fmaxf(fmaxf(fabsf(a.bg[0]), fabsf(a.bg[1])), fabsf(a.bg[2]));
-        // (unit-level opacity bound: folded into eK, and a field's scale is then ONE constant per lane and unit)
-        fx.eK = fx_exp(32.f * ((cmax + bgm) * D1 + 5.f * Dd)) + (FX_ENTRY_OPACITY ? 0 : fx_exp(__uint_as_float(tile_max[4])));
-        fx.eX = fx_exp(__uint_as_float(tile_max[2]));
-        fx.eY = fx_exp(__uint_as_float(tile_max[3]));
-        fx.eCol = fx_exp(32.f * D1);
-        fx.eId = fx_exp(32.f * Dd);
+    // the unit's bounds: largest sum_c |dL/dpixel_c| (the block's 256 lanes hold the tile's 256 pixels), |dL/dinvdepth|, and
+    // centre-to-corner distances of its splats (entry threadIdx.x; the records behind the unit's end are zero)
+    const float tx0 = (float)(u.tx * TILE), ty0 = (float)(u.ty * TILE);
+    const float4 mine = S.ra[threadIdx.x & 0xffu];          // (the mask changes nothing for 256 threads but the compiler's schedule)
+    const bool real = (uint32_t)threadIdx.x < u.end - u.beg;
+    const float m_d1 = wave_max_to_lane63((fabsf(dp0) + fabsf(dp1)) + fabsf(dp2));
+    const float m_x = wave_max_to_lane63(real ? fmaxf(fabsf(mine.x - tx0), fabsf(mine.x - tx0 - 15.f)) + 1.f : 1.f);
+    const float m_y = wave_max_to_lane63(real ? fmaxf(fabsf(mine.y - ty0), fabsf(mine.y - ty0 - 15.f)) + 1.f : 1.f);
+    const float m_dd = INVD ? wave_max_to_lane63(fabsf(dinvd)) : 0.f;
+    const float m_op = wave_max_to_lane63(real ? fabsf(S.rb[threadIdx.x & 0xffu].y) : 0.f);
+    if (lane == 63) {          // (non-negative floats order like their bits; integer LDS atomics run at the rate of stores)
+        atomicMax(&tile_max[0], __float_as_uint(m_d1)); if (INVD) atomicMax(&tile_max[1], __float_as_uint(m_dd));
+        atomicMax(&tile_max[2], __float_as_uint(m_x)); atomicMax(&tile_max[3], __float_as_uint(m_y));
+        atomicMax(&tile_max[4], __float_as_uint(m_op));
     }
+    __syncthreads();
+    const float D1 = __uint_as_float(tile_max[0]), Dd = INVD ? __uint_as_float(tile_max[1]) : 0.f;
+    const float cmax = __uint_as_float(g.tile_cmax[u.tile]);
+    const float bgm = fmaxf(fmaxf(fabsf(a.bg[0]), fabsf(a.bg[1])), fabsf(a.bg[2]));
+    // (unit-level opacity bound: folded into eK, and a field's scale is then ONE constant per lane and unit)
+    fx.eK = fx_exp(32.f * ((cmax + bgm) * D1 + 5.f * Dd)) + fx_exp(__uint_as_float(tile_max[4]));
+    fx.eX = fx_exp(__uint_as_float(tile_max[2]));
+    fx.eY = fx_exp(__uint_as_float(tile_max[3]));
+    fx.eCol = fx_exp(32.f * D1);
+    fx.eId = fx_exp(32.f * Dd);
     const uint32_t posbase = (uint32_t)u.seg * u.L;
     const uint32_t cn = u.end - u.beg;
     const uint32_t cnt = S.ocnt[4 * q + row];
@@ -723,7 +693,7 @@ __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdA
     ph.mark(2);
 
     // lane -> field of the 64-byte gradient record (the layout row_reduce10 leaves)
-    const bool b3 = (li & 8) != 0, b2 = (li & 4) != 0, b1 = (li & 2) != 0, b0 = (li & 1) != 0;
+    const bool b1 = (li & 2) != 0, b0 = (li & 1) != 0;
     int afield;
     switch (li) {
     case 0: afield = GRAD_MX; break;
@@ -751,7 +721,7 @@ __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdA
 #pragma unroll
         for (int e = 0; e < NE; e++) {
             const uint32_t pos = (uint32_t)g0 + (uint32_t)(NE - 1 - e);          // descending within the trip
-            se[e] = (ep >> (8 * (NE - 1 - e))) & (0xffu & EMASK);
+            se[e] = (ep >> (8 * (NE - 1 - e))) & 0xffu;
             const float4 r0 = S.ra[se[e]];
             r1[e] = S.rb[se[e]]; r2[e] = get_tail(S.rc[se[e]]);
             dx[e] = r0.x - p.xf; dy[e] = r0.y - p.yf;
@@ -774,25 +744,17 @@ __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdA
                 bwd_step<INVD>(st8, act[e], r1[e], q2, dx[e], dy[e], G[e], al[e], dp0, dp1, dp2, dinvd, Tfinal_bgdot, v[e]);
             }
 #pragma unroll
-            for (int e = 0; e < NE; e++) y[e] = row_reduce10<!INVD>(v[e], b3, b2, b1, b0);
+            for (int e = 0; e < NE; e++) y[e] = row_reduce10<!INVD>(v[e], b1, b0);
         }
         // a row with no active pixel for an entry sums exact zeros: nothing to add (and its entry byte may be stale)
-        if (FIXED) {
-            long long val[NE];
+        long long val[NE];
 #pragma unroll
-            for (int e = 0; e < NE; e++)          // (a pair is only ever active on a positive opacity: its bits >> 23 are its exponent)
-                val[e] = FX_ENTRY_OPACITY ? fx_from_float(y[e], fx_scale_exp(fxbase, fkind == 0 ? __float_as_uint(r1[e].y) >> 23 : 126u))
-                                          : fx_from_float(y[e], fxs);
-            // (adding without the test for zero was measured: 141 us against 133 -- the zeros of the idle rows are atomics too)
+        for (int e = 0; e < NE; e++) val[e] = fx_from_float(y[e], fxs);
+        // (adding without the test for zero was measured: 141 us against 133 -- the zeros of the idle rows are atomics too)
 #pragma unroll
-            for (int e = 0; e < NE; e++)
-                if (alane && y[e] != 0.f)
-                    atomicAdd(reinterpret_cast<unsigned long long *>(fxt) + se[e] * (uint32_t)NF + (uint32_t)afield, (unsigned long long)val[e]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < NE; e++)
-                if (alane && y[e] != 0.f) atomicAdd(&table[se[e] * 10u + (uint32_t)afield], y[e]);
-        }
+        for (int e = 0; e < NE; e++)
+            if (alane && y[e] != 0.f)
+                atomicAdd(reinterpret_cast<unsigned long long *>(fxt) + se[e] * (uint32_t)NF + (uint32_t)afield, (unsigned long long)val[e]);
     }
     }
     ph.mark(3);
@@ -803,7 +765,7 @@ __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdA
     // flush.  Float-atomics mode: NF consecutive lanes per entry, one per field of its 64-byte record (one cache line), BLOCK / NF entries
     // per step -- 28 (27 lanes of 256 idle) instead of the 16 of a 16-lanes-per-entry layout whose lanes NF..15 had nothing to add: ten
     // steps instead of sixteen for a full unit (round 6: the launch is bound by VALU issue and this loop ran on every wave).
-    if (FIXED && !DET) {
+    if (!DET) {
         constexpr int EPS = BLOCK / NF;                       // entries per step
         const int f = (int)threadIdx.x % NF;
         int cx, cy, kind;
@@ -813,8 +775,7 @@ __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdA
             for (uint32_t e = threadIdx.x / NF; e < cn; e += EPS) {
                 const long long sv = fxt[e * (uint32_t)NF + (uint32_t)f];
                 if (sv != 0ll)
-                    unsafeAtomicAdd(a.accum + (size_t)uid[e] * GRAD_STRIDE + f,
-                                    fx_to_float(sv, FX_ENTRY_OPACITY && kind == 0 ? fx_scale_exp(fx_field_base(fx, cx, cy, kind), __float_as_uint(S.rb[e].y) >> 23) : kexp));
+                    unsafeAtomicAdd(a.accum + (size_t)uid[e] * GRAD_STRIDE + f, fx_to_float(sv, kexp));
             }
         }
     } else {
@@ -822,22 +783,9 @@ __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdA
         int cx, cy, kind;
         fx_field_kind(f, cx, cy, kind);
         for (uint32_t e = threadIdx.x >> 4; e < cn; e += BLOCK / 16) {
-            if (DET) {
-                // every instance of the unit gets its record (zeros included: the buffer is not cleared between frames)
-                const long long sv = f < NF ? fxt[e * (uint32_t)NF + (uint32_t)f] : 0ll;
-                a.part[(size_t)(u.beg + e) * GRAD_STRIDE + f] =
-                    sv != 0ll ? fx_to_float(sv, fx_scale_exp(fx_field_base(fx, cx, cy, kind), (FX_ENTRY_OPACITY && kind == 0) ? __float_as_uint(S.rb[e].y) >> 23 : 126u)) : 0.f;
-            } else if (FIXED) {
-                if (f < NF) {
-                    const long long sv = fxt[e * (uint32_t)NF + (uint32_t)f];
-                    if (sv != 0ll)
-                        unsafeAtomicAdd(a.accum + (size_t)uid[e] * GRAD_STRIDE + f,
-                                        fx_to_float(sv, fx_scale_exp(fx_field_base(fx, cx, cy, kind), (FX_ENTRY_OPACITY && kind == 0) ? __float_as_uint(S.rb[e].y) >> 23 : 126u)));
-                }
-            } else if (f < 10) {
-                const float y = table[e * 10u + (uint32_t)f];
-                if (y != 0.f) unsafeAtomicAdd(a.accum + (size_t)uid[e] * GRAD_STRIDE + f, y);
-            }
+            // every instance of the unit gets its record (zeros included: the buffer is not cleared between frames)
+            const long long sv = f < NF ? fxt[e * (uint32_t)NF + (uint32_t)f] : 0ll;
+            a.part[(size_t)(u.beg + e) * GRAD_STRIDE + f] = sv != 0ll ? fx_to_float(sv, fx_scale_exp(fx_field_base(fx, cx, cy, kind), 126u)) : 0.f;
         }
     }
     ph.value(7, ((unsigned long long)u.idx << 40) | ((unsigned long long)(u.end - u.beg) << 28) | ((unsigned long long)u.nseg << 14) | (unsigned long long)u.seg);
@@ -853,10 +801,7 @@ int32_t launch_micro_forward(const BlendGrid &g_in, const BlendFwdOut &o, uint32
     if (deep_env == -2) { const char *e = getenv("GMS_DEEP"); deep_env = e ? atoi(e) : -1; }
     const bool deep = deep_env >= 0 ? deep_env != 0 : g.capacity > 512ull * (uint64_t)g.T;
     const unsigned blocks = blend_grid_units(max_units);
-    static int trip = -1;
-    if (trip < 0) { const char *e = getenv("GMS_TRIP"); trip = e ? atoi(e) : 4; }      // (forward: 4 entries per trip; 2: -2 % it/s)
-    auto head = trip == 4 ? micro_head_kernel<4> : (trip == 1 ? micro_head_kernel<1> : micro_head_kernel<2>);
-    auto fwd2 = trip == 4 ? micro_fwd_kernel<4> : (trip == 1 ? micro_fwd_kernel<1> : micro_fwd_kernel<2>);
+    auto head = micro_head_kernel<4>;          // (4 entries per trip; 2 was -2 % it/s: docs/HISTORY.md)
     if (deep) {     // deep scene: head segments, tile-dead check, then the tail segments of the tiles still alive
         GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<blocks, BLOCK, 0, stream>>>(g, o, 0));
         GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, micro_tloc_check_kernel<<<(unsigned)g.T, BLOCK, 0, stream>>>(g));
@@ -865,7 +810,7 @@ int32_t launch_micro_forward(const BlendGrid &g_in, const BlendFwdOut &o, uint32
         GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<blocks, BLOCK, 0, stream>>>(g, o, -1));
     }
     GMS_KERNEL_CHECK(debug, stream, "micro_head");
-    GMS_LAUNCH(GMS_K_BLEND_FWD, stream, fwd2<<<blocks, BLOCK, 0, stream>>>(g, o));
+    GMS_LAUNCH(GMS_K_BLEND_FWD, stream, micro_fwd_kernel<4><<<blocks, BLOCK, 0, stream>>>(g, o));
     GMS_KERNEL_CHECK(debug, stream, "micro_fwd");
     GMS_LAUNCH(GMS_K_BLEND_FINALIZE, stream, micro_finalize_kernel<<<(unsigned)g.T, BLOCK, 0, stream>>>(g, o));
     GMS_KERNEL_CHECK(debug, stream, "micro_finalize");
@@ -877,36 +822,15 @@ int32_t launch_micro_backward(const BlendGrid &g_in, const BlendBwdArgs &a, uint
     BlendGrid g = g_in;
     experiment_switches(g, 1024u, stream);          // (make EXPERIMENTS=1 only: GMS_DBG & 1024 = per-wave phase stamps)
     const unsigned blocks = blend_grid_units(max_units);
-    static int trip = -1;
-    if (trip < 0) { const char *e = getenv("GMS_TRIP_BWD"); trip = e ? atoi(e) : 2; }
     const bool invd = a.has_invd && a.dL_dinvd;
-    static int fixed = -1;              // GMS_BWD_FIXED=0: the float LDS table of rounds 3-4 (ds_add_f32) instead of the 64-bit fixed-point one
-    if (fixed < 0) { const char *e = getenv("GMS_BWD_FIXED"); fixed = e ? (atoi(e) != 0) : 1; }
-    if (a.part) {                           // deterministic mode (gmsplat.h): the fixed-point table, per-instance partial records
+    if (a.part) {                           // deterministic mode (gmsplat.h): per-instance partial records
         if (invd) GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (micro_bwd_kernel<true, 2, 0, true><<<blocks, BLOCK, 0, stream>>>(g, a)));
         else GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (micro_bwd_kernel<false, 2, 0, true><<<blocks, BLOCK, 0, stream>>>(g, a)));
     } else if (fault_mode() == 2 && !invd) {       // negative control (gms_set_fault): its own instantiation
         GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (micro_bwd_kernel<false, 2, 2><<<blocks, BLOCK, 0, stream>>>(g, a)));
-    } else if (!fixed) {
-        auto kern = invd ? micro_bwd_kernel<true, 2, 0, false, false> : micro_bwd_kernel<false, 2, 0, false, false>;
-        GMS_LAUNCH(GMS_K_BLEND_BWD, stream, kern<<<blocks, BLOCK, 0, stream>>>(g, a));
     } else {
-#if GMS_EXPERIMENTS
-        // Occupancy experiment (make EXPERIMENTS=1, GMS_SEG_LEN=128): a 128-entry unit image is 16 KB of LDS -> 8 blocks per CU instead
-        // of 5.  Measured (round 6, profiles/r06c_*): 126.2 us against 125.7 -- 8 192 resident waves instead of 5 120, the same ~2 400 of
-        // them in the walk, every phase of a wave proportionally slower.  The kernel is bound by VALU issue, not by latency or occupancy.
-        if (seg_len_forced() != 0 && seg_len_forced() <= 128u && !invd) {
-            GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (micro_bwd_kernel<false, 2, 0, false, true, 128><<<blocks, BLOCK, 0, stream>>>(g, a)));
-            GMS_KERNEL_CHECK(debug, stream, "micro_bwd");
-            return GMS_OK;
-        }
-#endif
-        auto kern = trip == 1 ? (invd ? micro_bwd_kernel<true, 1, 0> : micro_bwd_kernel<false, 1, 0>)
-                  : trip == 4 ? (invd ? micro_bwd_kernel<true, 4, 0> : micro_bwd_kernel<false, 4, 0>)
-                              : (invd ? micro_bwd_kernel<true, 2, 0> : micro_bwd_kernel<false, 2, 0>);
-        static int lds_pad = -1;            // (make EXPERIMENTS=1 only) GMS_LDS_PAD: bytes of unused dynamic LDS per block, to time other occupancies
-        if (lds_pad < 0) { const char *e = getenv("GMS_LDS_PAD"); lds_pad = (GMS_EXPERIMENTS && e) ? atoi(e) : 0; }
-        GMS_LAUNCH(GMS_K_BLEND_BWD, stream, kern<<<blocks, BLOCK, (size_t)lds_pad, stream>>>(g, a));
+        auto kern = invd ? micro_bwd_kernel<true, 2, 0> : micro_bwd_kernel<false, 2, 0>;          // (2 entries per trip)
+        GMS_LAUNCH(GMS_K_BLEND_BWD, stream, kern<<<blocks, BLOCK, 0, stream>>>(g, a));
     }
     GMS_KERNEL_CHECK(debug, stream, "micro_bwd");
     return GMS_OK;

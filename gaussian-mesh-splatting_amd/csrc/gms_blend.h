@@ -77,10 +77,6 @@ inline uint32_t max_slots(uint64_t instances, uint32_t L) { return 2u * (uint32_
 #ifndef GMS_MICRO_DEFAULT
 #define GMS_MICRO_DEFAULT 1
 #endif
-#ifndef GMS_QUEUE
-#define GMS_QUEUE 256
-#endif
-constexpr int QUEUE = GMS_QUEUE;   // LDS splat-queue entries per batch (<= BLOCK)
 constexpr uint32_t TLOC_HEAD_ENTRIES = 1024;   // list entries (per tile) whose transmittance products are always evaluated
 __host__ __device__ __forceinline__ int tloc_head(uint32_t L) { return (int)(TLOC_HEAD_ENTRIES / L > 0 ? TLOC_HEAD_ENTRIES / L : 1u); }
 
@@ -309,9 +305,8 @@ constexpr int FX_SHIFT = 47;
 __device__ __forceinline__ int fx_exp(float x) { return (int)((__float_as_uint(x) >> 23) & 0xffu) - 126; }
 
 // The power of two a partial sum is scaled by before it is rounded: k = FX_SHIFT - E.  `base` = FX_SHIFT minus the unit-level part of
-// the field's exponent (a constant of the lane that holds the field), `op_exp` = 126 (the opacity bound is part of `base`), or -- builds
-// with GMS_FX_ENTRY_OPACITY=1 -- the biased exponent of the entry's own opacity for the geometric fields (op < 2^(op_exp - 126)).
-// Kept inside a float's exponent range.
+// the field's exponent (a constant of the lane that holds the field), `op_exp` = 126 (the opacity bound is part of `base`; an exponent
+// taken from every entry's own opacity was measured and removed, docs/HISTORY.md).  Kept inside a float's exponent range.
 __device__ __forceinline__ int fx_scale_exp(int base, uint32_t op_exp) { return min(max(base + 126 - (int)op_exp, -100), 100); }
 
 // round(y * 2^k) as a 64-bit integer for |y| * 2^k <= 2^47: the product with a power of two is exact in float, and adding 1.5 * 2^52 in

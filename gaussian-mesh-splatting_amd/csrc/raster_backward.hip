@@ -684,9 +684,7 @@ extern "C" int32_t gms_rasterize_backward(const GmsRasterBackwardArgs *A, void *
     p.clamped = geom.clamped; p.accum = A->grad_accum; p.rezero = fault_mode() == 3 ? 0 : A->grad_accum_rezero; p.dL_dmean2D = A->dL_dmeans2D;
     p.dL_dcolors = A->colors_precomp ? A->dL_dcolors : nullptr; p.dL_dcolor_sh = (A->shs && A->sh_factor_mode) ? A->dL_dcolors : nullptr; p.campos_row = A->factor_campos_row; p.dL_dopacity = A->dL_dopacity; p.dL_dmeans3D = A->dL_dmeans3D;
     p.dL_dcov3D = A->dL_dcov3D; p.dL_dsh = A->dL_dsh; p.dL_dsh_rest = A->dL_dsh_rest; p.dL_dscales = A->dL_dscales; p.dL_drots = A->dL_drotations;
-    static int pre_linear = -1;         // GMS_PRE_BWD_LINEAR=0: the 52-dword-pitch scatter staging of rounds 1-4 for split degree-3 storage
-    if (pre_linear < 0) { const char *e = getenv("GMS_PRE_BWD_LINEAR"); pre_linear = e ? (atoi(e) != 0) : 1; }
-    const int lin_ok = pre_linear && A->shs && A->shs_rest && A->D == 3 && (((uintptr_t)A->shs) & 15u) == 0 && (((uintptr_t)A->shs_rest) & 15u) == 0 &&
+    const int lin_ok = A->shs && A->shs_rest && A->D == 3 && (((uintptr_t)A->shs) & 15u) == 0 && (((uintptr_t)A->shs_rest) & 15u) == 0 &&
                        (A->sh_factor_mode || ((((uintptr_t)A->dL_dsh) & 15u) == 0 && (((uintptr_t)A->dL_dsh_rest) & 15u) == 0));
     if (mesh) {
         p.mesh = *mesh; p.mesh_dvertices = A->mesh_dL_dvertices; p.mesh_dalpha = A->mesh_dL_dalpha; p.mesh_dscale = A->mesh_dL_dscale; p.mesh_dopacity = A->mesh_dL_d_opacity;

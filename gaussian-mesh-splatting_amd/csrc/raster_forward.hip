@@ -125,12 +125,10 @@ __device__ __forceinline__ void sh_colour(const float *row_lds, float x, float y
     }
 }
 
-// MODE 0: everything in one launch.  MODE 1 / 2: the same kernel cut in two for the two-stream forward -- 1 = geometry (what
-// the binning needs: projection, conic, radius, extents, tile counts; 8 KB of LDS instead of 53), 2 = SH -> RGB (57 MB of
-// coefficient reads that only the compositing needs: runs on a second stream beside scan / emit / sort / filter).  The two
-// write disjoint bytes of the 48-byte record.
+// (a two-stream forward -- this kernel cut into a geometry launch and an SH -> RGB launch on a second stream beside scan / emit /
+// sort -- was measured, no gain, and removed; see docs/HISTORY.md)
 // (cull_extents -- the noise-aware half extents stored in record words 10, 11 -- lives in gms_blend.h)
-// DMA (round 5; split storage, degree 3, MODE 0): the wave's coefficient block goes global -> LDS with `global_load_lds_dwordx4`
+// DMA (round 5; split storage, degree 3): the wave's coefficient block goes global -> LDS with `global_load_lds_dwordx4`
 // (1 KiB per wave instruction, no staging VGPRs, no ds_write pass).  The LDS destination of that instruction is lane-linear, and
 // so is the source here: the 64 rows of `_features_rest` a wave owns are 11 520 contiguous, 16-byte aligned bytes, copied as they
 // lie (row pitch 45 dwords: odd, so the per-lane ds_read_b32 of a row are conflict-free), the 768 bytes of `_features_dc` behind
@@ -139,24 +137,25 @@ __device__ __forceinline__ void sh_colour(const float *row_lds, float x, float y
 // Gaussian from the mesh -- barycentric centre, face frame -> activated scale and unit quaternion, sigmoid opacity, the statements
 // of mesh_fwd_kernel (gms_mesh.h::splat_from_face) -- instead of loading means3D / scales / rotations / opacities: those four
 // tensors (44 bytes per Gaussian written by K0 and read back here, plus K0's raw copies) never reach HBM and the K0 launch is gone.
-template <int SHDEG, bool SPLIT, int MODE = 0, bool DMA = false, bool K0 = false>
+template <int SHDEG, bool SPLIT, bool DMA = false, bool K0 = false>
 __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a)
 {
 #pragma clang fp contract(off)
-    static_assert(!DMA || (SHDEG >= 0 && SHDEG <= 3 && SPLIT && MODE == 0), "the LDS-DMA staging exists for split degree-3 STORAGE (any active degree: the rows come in whole)");
+    static_assert(!DMA || (SHDEG >= 0 && SHDEG <= 3 && SPLIT), "the LDS-DMA staging exists for split degree-3 STORAGE (any active degree: the rows come in whole)");
     static_assert(!K0 || DMA, "the fused mesh input rides on the LDS-DMA instantiation");
+    static_assert(DMA || !SPLIT || SHDEG != 3, "split degree-3 storage is staged by LDS-DMA (the register-staged rows were measured and removed)");
     // Round 6: the REST rows come in as TWO halves of 32 rows through the same 6 KB of LDS per wave (6 x 1 KiB DMA instructions each,
     // 1 440 of the 1 536 floats used), the 64 x 3 DC floats behind them: 27 KB per block instead of 49.
     constexpr int DMA_HALF_ROWS = WAVE / 2, DMA_HALF_Q = 6;                       // rows and DMA instructions per half
     constexpr int DMA_REST_FLOATS = DMA_HALF_Q * WAVE * 4;                        // 1 536 (>= 32 x 45 = 1 440)
     constexpr int DMA_WAVE_FLOATS = DMA_REST_FLOATS + WAVE * 3;
-    __shared__ __attribute__((aligned(16))) float sh_lds[MODE == 1 ? 2 * TT_SLOTS : (DMA ? 4 * DMA_WAVE_FLOATS : 4 * WAVE * SH_PITCH)];
+    __shared__ __attribute__((aligned(16))) float sh_lds[DMA ? 4 * DMA_WAVE_FLOATS : 4 * WAVE * SH_PITCH];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x * BLOCK + tid;
     const bool valid = i < a.P;
-    if (MODE != 2 && a.zero_cursor)
+    if (a.zero_cursor)
         for (int q = i; q < a.T; q += (int)gridDim.x * BLOCK) a.zero_cursor[q] = 0u;
-    if (MODE != 2 && a.zero_cmax)
+    if (a.zero_cmax)
         for (int q = i; q < a.T; q += (int)gridDim.x * BLOCK) a.zero_cmax[q] = 0u;
     if (K0 && a.mesh.prezero)          // the [V,3] buffer the mesh backward accumulates into (what spare blocks of mesh_fwd clear)
         for (int64_t q = i; q < a.mesh.prezero_count; q += (int64_t)gridDim.x * BLOCK) a.mesh.prezero[q] = 0.f;
@@ -176,8 +175,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a)
     if (SHDEG >= 0) {
         const int g0 = blockIdx.x * BLOCK + wave * WAVE;
         const int rows = min(WAVE, a.P - g0);
-        if (MODE == 1) {
-        } else if (DMA) {
+        if (DMA) {
             float *wl = sh_lds + wave * DMA_WAVE_FLOATS;
             const float *sp = a.shs_rest + (size_t)g0 * RESTF;       // g0 % 64 == 0: 16-byte aligned
             const int nfl = max(0, min(rows, DMA_HALF_ROWS)) * RESTF;        // first half: rows 0 .. 31
@@ -209,20 +207,8 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a)
                 const int e = lane + WAVE * j;
                 dcv[j] = e < rows * 3 ? a.shs[(size_t)g0 * 3 + e] : 0.f;
             }
-            if (SHDEG == 3) {
-                const float *sp = a.shs_rest + (size_t)g0 * RESTF;       // g0 % 64 == 0: 16-byte aligned
-                const float4 *src = reinterpret_cast<const float4 *>(sp);
-                const int nfl = rows * RESTF;
-#pragma unroll
-                for (int j = 0; j < NQ; j++) {
-                    const int e4 = (lane + WAVE * j) * 4;
-                    if (e4 + 3 < nfl) stg[j] = src[lane + WAVE * j];
-                    else stg[j] = make_float4(e4 < nfl ? sp[e4] : 0.f, e4 + 1 < nfl ? sp[e4 + 1] : 0.f,
-                                              e4 + 2 < nfl ? sp[e4 + 2] : 0.f, 0.f);
-                }
-            }
         }
-        if (valid && MODE != 2 && !K0) {
+        if (valid && !K0) {
             op_in = a.opac[i];
             if (!a.cov3Dp) {
                 s_in[0] = a.scales[3 * (size_t)i]; s_in[1] = a.scales[3 * (size_t)i + 1]; s_in[2] = a.scales[3 * (size_t)i + 2];
@@ -253,10 +239,9 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a)
         }
     } else if (valid) {
         px = a.means3D[3 * (size_t)i]; py = a.means3D[3 * (size_t)i + 1]; pz = a.means3D[3 * (size_t)i + 2];
-        if (MODE == 2) vis = a.radii[i] > 0;                          // (decided by the geometry launch)
-        else { view_transform(a.view, px, py, pz, vx, vy, vz); vis = vz > NEAR_Z; }
+        view_transform(a.view, px, py, pz, vx, vy, vz); vis = vz > NEAR_Z;
     }
-    if (vis && MODE != 2) {
+    if (vis) {
         const float *Mx = a.proj;
         float hx = dot3p(Mx[0], px, Mx[4], py, Mx[8], pz, Mx[12]);
         float hy = dot3p(Mx[1], px, Mx[5], py, Mx[9], pz, Mx[13]);
@@ -300,8 +285,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a)
     // ---- colour
     float rgb[3] = {0, 0, 0};
     unsigned clampbits = 0;
-    if (MODE == 1) {
-    } else if (DMA) {
+    if (DMA) {
         float *wl = sh_lds + wave * DMA_WAVE_FLOATS;
         const int g0 = blockIdx.x * BLOCK + wave * WAVE;
         const int rows = max(0, min(WAVE, a.P - g0));          // (the last block's later waves may own no row at all)
@@ -366,17 +350,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a)
                 const int e = lane + WAVE * j;
                 wl[(e / 3) * SH_PITCH + (e % 3)] = dcv[j];
             }
-            if (SHDEG == 3) {
-#pragma unroll
-                for (int j = 0; j < NQ; j++) {
-                    const float v4[4] = {stg[j].x, stg[j].y, stg[j].z, stg[j].w};
-#pragma unroll
-                    for (int t = 0; t < 4; t++) {
-                        const int e = (lane + WAVE * j) * 4 + t;       // flat element of the wave's REST block
-                        if (e < WAVE * RESTF) wl[(e / RESTF) * SH_PITCH + 3 + (e % RESTF)] = v4[t];
-                    }
-                }
-            } else if (SHDEG > 0) {
+            if (SHDEG > 0) {
                 // low active degree: only the first NB3-3 floats of each REST row are needed
                 const int g0 = blockIdx.x * BLOCK + wave * WAVE;
                 const int rows = min(WAVE, a.P - g0);
@@ -429,31 +403,11 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a)
         rgb[0] = a.colors[3 * (size_t)i]; rgb[1] = a.colors[3 * (size_t)i + 1]; rgb[2] = a.colors[3 * (size_t)i + 2];
     }
 
-    if (MODE == 2) {          // colour launch: the three colour words of the record and the clamp bits, nothing else
-        if (vis) {
-            float *rw = reinterpret_cast<float *>(a.geom.rec + i);
-            *reinterpret_cast<float2 *>(rw + 6) = make_float2(rgb[0], rgb[1]);
-            rw[8] = rgb[2];
-            a.geom.clamped[i] = (uint8_t)clampbits;
-        }
-        return;
-    }
     if (valid && !vis) a.radii[i] = 0;
     if (valid) a.geom.rect[i] = vis ? make_ushort4((unsigned short)minx, (unsigned short)miny, (unsigned short)maxx, (unsigned short)maxy)
                                     : make_ushort4(0, 0, 0, 0);          // (the rectangle the tile counts below were taken over)
     if (valid && a.visible) a.visible[i] = vis ? 1 : 0;
-    if (vis && MODE == 1) {   // geometry launch: everything but the colour words
-        float ex, ey;
-        cull_extents(a_d, c_d, cA, cB, cC, opp, ex, ey);
-        float *rw = reinterpret_cast<float *>(a.geom.rec + i);
-        *reinterpret_cast<float4 *>(rw) = make_float4(pix, piy, cA, cB);
-        *reinterpret_cast<float2 *>(rw + 4) = make_float2(cC, opp);
-        rw[9] = 1.f / vz;
-        *reinterpret_cast<float2 *>(rw + 10) = make_float2(ex, ey);
-        a.geom.depth[i] = vz;
-        a.radii[i] = (int)rad;
-    }
-    if (vis && MODE == 0) {
+    if (vis) {
         float ex, ey;
         cull_extents(a_d, c_d, cA, cB, cC, opp, ex, ey);
         SplatRec rec;
@@ -502,8 +456,8 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a)
     }
 }
 
-template <int SHDEG, bool SPLIT, int MODE = 0>
-__global__ void __launch_bounds__(BLOCK) preprocess_fwd_kernel(PreArgs a) { preprocess_fwd_body<SHDEG, SPLIT, MODE, false, false>(a); }
+template <int SHDEG, bool SPLIT>
+__global__ void __launch_bounds__(BLOCK) preprocess_fwd_kernel(PreArgs a) { preprocess_fwd_body<SHDEG, SPLIT, false, false>(a); }
 // The LDS-DMA instantiations: 27 KB of LDS per block (SH rows in two halves) admits five blocks per CU, and five blocks per CU hold the whole
 // grid of the headline frame (1 171 blocks) in ONE round -- at three (49 KB) and at four (100 registers) a second, half-empty round follows:
 // 35.5 / 34.9 us against 31.5 at five (profiles/r06w1_*, r06w2_*).  The compiler is held to the 96 registers that takes (two to four spilled).
@@ -512,7 +466,7 @@ __global__ void __launch_bounds__(BLOCK) preprocess_fwd_kernel(PreArgs a) { prep
 template <bool K0, int DEG = 3>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5))) preprocess_fwd_dma_kernel(PreArgs a)
 {
-    preprocess_fwd_body<DEG, true, 0, true, K0>(a);
+    preprocess_fwd_body<DEG, true, true, K0>(a);
 }
 
 // ------------------------------------------------------------------------------------ K2
@@ -981,7 +935,7 @@ __device__ void lds_bitonic(uint64_t *s, int m, int k0, int j0, bool first_mirro
 }
 
 // Per-tile sort in three stages.
-//  (1) presort: grid (T, 8), 256 threads: block (t, c) sorts runs c, c+8, ... of SORT_RUN keys of tile t in LDS (the
+//  (1) presort: grid (T, 8), 256 threads: block (t, c) sorts runs c, c+8, ... of SORT_RUN keys of tile t in registers (the
 //      runs of one tile sort on different CUs).
 //  (2) when some tile is deeper than SORT_BIG_CHUNK keys: merge-path passes for every multi-run tile, run width
 //      doubling per pass; every block produces one 1024-key chunk of the output from the co-ranks of its two ends
@@ -1012,44 +966,14 @@ __device__ __forceinline__ int sort_class(uint64_t n, int passes_launched, int &
     return n <= (uint64_t)SORT_BIG_CHUNK ? SORT_LDS : SORT_FALLBACK;
 }
 
-__global__ void __launch_bounds__(256) tile_presort_kernel(const uint32_t *tile_offset, const uint32_t *run_total, const uint2 *run_tab,
-                                                           uint32_t max_runs, uint64_t *keys, uint64_t *tmp, uint64_t capacity,
-                                                           int passes_launched, uint32_t *zero_count, int T)
-{
-    __shared__ uint64_t s[SORT_RUN];
-    const int tid = threadIdx.x;
-    // inline-scan frames: the per-tile counters were read by the emit launch; they are cleared here (all zero between frames)
-    if (zero_count)
-        for (int q = (int)blockIdx.x * 256 + tid; q < T; q += (int)gridDim.x * 256) zero_count[q] = 0u;
-    if (blockIdx.x >= run_total[0] || blockIdx.x >= max_runs) return;      // one block per (tile, run) of the run table
-    const uint2 tr = run_tab[blockIdx.x];
-    const uint64_t beg = tile_offset[tr.x], end64 = tile_offset[tr.x + 1];
-    if (end64 > capacity) return;                 // overflowed launch: results are discarded by the host
-    const long n = (long)(end64 - beg);
-    int q;
-    const int cls = sort_class((uint64_t)n, passes_launched, q);
-    if (cls == SORT_FALLBACK) return;
-    uint64_t *dst_base = (cls == SORT_MERGEPATH && (q & 1)) ? tmp : keys;
-    const long c0 = (long)tr.y * SORT_RUN;
-    const int cn = (int)min((long)SORT_RUN, n - c0);
-    const uint64_t *g = keys + beg + c0;
-    uint64_t *d = dst_base + beg + c0;
-    if (cn <= 1) { if (cn == 1 && tid == 0) d[0] = g[0]; return; }
-    int m = 2;
-    while (m < cn) m <<= 1;
-    for (int i = tid; i < m; i += 256) s[i] = i < cn ? g[i] : ~0ull;
-    lds_bitonic<256>(s, m, 2, 0, true, tid);
-    for (int i = tid; i < cn; i += 256) d[i] = s[i];
-}
-
 // ---- register-resident presort ------------------------------------------------------------------------------------
-// The same all-ascending bitonic network (mirror step + half-cleaners: every step pairs element i with i ^ M) on a run of
-// <= 1024 keys, but with the keys in REGISTERS: thread t of 256 holds keys 4t .. 4t+3.  A step whose mask only touches bits
+// The all-ascending bitonic network of lds_bitonic (mirror step + half-cleaners: every step pairs element i with i ^ M) on a run of
+// <= 1024 keys, with the keys in REGISTERS: thread t of 256 holds keys 4t .. 4t+3.  A step whose mask only touches bits
 // 0-1 is a compare-exchange between the thread's own registers; bits 2-7 select the partner LANE (lane ^ (M >> 2)): DPP row
 // operations for the lane masks 1, 2, 3, 4, 7, 8, 15 (full rate, no LDS), ds_bpermute for those that cross a 16-lane row; only
-// the four steps with bits 8-9 (k = 512 mirror, k = 1024 mirror, strides 512 and 256) go through LDS.  The LDS version pays an
-// LDS round trip and a barrier or wave sync for each of its 55 steps (a lone 1024-key block takes ~25 us: pure latency, and
-// the launch is a single round of blocks); this one pays four.
+// the four steps with bits 8-9 (k = 512 mirror, k = 1024 mirror, strides 512 and 256) go through LDS.  The LDS version (measured,
+// removed; see docs/HISTORY.md) paid an LDS round trip and a barrier or wave sync for each of its 55 steps (a lone 1024-key block
+// took ~25 us: pure latency, and the launch is a single round of blocks); this one pays four.
 template <int CTRL>
 __device__ __forceinline__ uint64_t dpp64(uint64_t v)
 {
@@ -1627,40 +1551,7 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
         set_error("split SH storage (shs_rest) needs M == 16 and 16-byte aligned pointers");
         return GMS_ERR_INVALID_ARGUMENT;
     }
-    // Two-stream forward (GMS_SH_STREAM=1 enables; measured on the headline scene: no gain, 2 158 against 2 173 it/s, so off by default): the SH -> RGB half of the preprocess runs on a library-owned second stream
-    // beside tile scan / emit / sort / filter, which leave most of the chip idle and need only the geometry half; the
-    // compositing waits for it (fork / join with two events).  The 57 MB of coefficient reads leave the critical path.
-    static int sh_stream_env = -1;
-    if (sh_stream_env < 0) { const char *e = getenv("GMS_SH_STREAM"); sh_stream_env = e ? (atoi(e) != 0) : 0; }
-    struct Aux { int device; hipStream_t s; hipEvent_t fork, join; };
-    static thread_local std::vector<Aux> t_aux;
-    Aux *aux = nullptr;
-    const bool two_stream = sh_stream_env && sh_fast && A->D > 0 && !mesh;
-    if (two_stream) {
-        for (auto &x : t_aux) if (x.device == device) aux = &x;
-        if (!aux) {
-            Aux x{device, nullptr, nullptr, nullptr};
-            GMS_HIP_CHECK(hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking));
-            GMS_HIP_CHECK(hipEventCreateWithFlags(&x.fork, hipEventDisableTiming));
-            GMS_HIP_CHECK(hipEventCreateWithFlags(&x.join, hipEventDisableTiming));
-            t_aux.push_back(x); aux = &t_aux.back();
-        }
-    }
-    static int pre_dma = -1;          // GMS_PRE_DMA=0: the register-staged SH rows instead of LDS-DMA (split degree-3 storage)
-    if (pre_dma < 0) { const char *e = getenv("GMS_PRE_DMA"); pre_dma = e ? (atoi(e) != 0) : 1; }
-#define GMS_PRE_M(DEG, SP, MODE, STR) GMS_LAUNCH(GMS_K_PREPROCESS_FWD, STR, (preprocess_fwd_kernel<DEG, SP, MODE><<<pblocks, BLOCK, 0, STR>>>(pa)))
-#define GMS_PRE(DEG, SP)                                                              \
-    do {                                                                              \
-        if (aux) {                                                                    \
-            GMS_PRE_M(DEG, SP, 1, stream);                                            \
-            GMS_HIP_CHECK(hipEventRecord(aux->fork, stream));                         \
-            GMS_HIP_CHECK(hipStreamWaitEvent(aux->s, aux->fork, 0));                  \
-            GMS_PRE_M(DEG, SP, 2, aux->s);                                            \
-            GMS_HIP_CHECK(hipEventRecord(aux->join, aux->s));                         \
-        } else {                                                                      \
-            GMS_PRE_M(DEG, SP, 0, stream);                                            \
-        }                                                                             \
-    } while (0)
+#define GMS_PRE(DEG, SP) GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_kernel<DEG, SP><<<pblocks, BLOCK, 0, stream>>>(pa)))
     if (mesh) {          // (validated above: split degree-3 storage; the active degree picks the instantiation)
         switch (A->D) {
         case 0: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<true, 0><<<pblocks, BLOCK, 0, stream>>>(pa))); break;
@@ -1670,21 +1561,17 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
         }
     } else
     switch ((sh_fast ? A->D : -1) * 2 + (split ? 1 : 0)) {
-    case 0: GMS_PRE_M(0, false, 0, stream); break;
-    case 1: GMS_PRE_M(0, true, 0, stream); break;
+    case 0: GMS_PRE(0, false); break;
+    case 1: GMS_PRE(0, true); break;
     case 2: GMS_PRE(1, false); break;
     case 3: GMS_PRE(1, true); break;
     case 4: GMS_PRE(2, false); break;
     case 5: GMS_PRE(2, true); break;
     case 6: GMS_PRE(3, false); break;
-    case 7:
-        if (pre_dma && !aux) GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<false><<<pblocks, BLOCK, 0, stream>>>(pa)));
-        else GMS_PRE(3, true);
-        break;
-    default: GMS_PRE_M(-1, false, 0, stream); break;
+    case 7: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<false><<<pblocks, BLOCK, 0, stream>>>(pa))); break;
+    default: GMS_PRE(-1, false); break;
     }
 #undef GMS_PRE
-#undef GMS_PRE_M
     GMS_KERNEL_CHECK(A->debug, stream, "preprocess_fwd");
     const uint32_t L = seg_len_min();         // sizes and carving; the frame's own L is chosen by the scan (scan_out[3])
     // deferred read-back (gmsplat.h, count_ticket_out): this frame's counts go to the next slot of the thread's ring and nobody waits here
@@ -1751,14 +1638,8 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
         const uint32_t max_multi = (uint32_t)BinningState::n_multi((size_t)capacity);
         const uint32_t *run_total = img.class_first + NCLASS * ((size_t)T + 1) + T;
         const uint32_t *multi_total = img.class_first + (NCLASS + 1) * ((size_t)T + 1) + T;
-        static int presort_lds = -1;        // GMS_PRESORT=lds: the LDS bitonic presort instead of the register-resident one
-        if (presort_lds < 0) { const char *e = getenv("GMS_PRESORT"); presort_lds = (e && e[0] == 'l') ? 1 : 0; }
-        if (presort_lds)
-            GMS_LAUNCH(GMS_K_TILE_SORT, stream, tile_presort_kernel<<<max_deep, 256, 0, stream>>>(img.tile_offset, run_total, bin.deep_tab, max_deep, bin.keys,
+        GMS_LAUNCH(GMS_K_TILE_SORT, stream, tile_presort_reg_kernel<<<max_deep, 256, 0, stream>>>(img.tile_offset, run_total, bin.deep_tab, max_deep, bin.keys,
                                                                                                  sort_tmp, capacity, sort_np, inl ? img.tile_count : nullptr, T));
-        else
-            GMS_LAUNCH(GMS_K_TILE_SORT, stream, tile_presort_reg_kernel<<<max_deep, 256, 0, stream>>>(img.tile_offset, run_total, bin.deep_tab, max_deep, bin.keys,
-                                                                                                     sort_tmp, capacity, sort_np, inl ? img.tile_count : nullptr, T));
         if (inl) ctr->dirty = false;          // the counters are clean again once this launch has run
         for (int pass = 0; pass < sort_np; pass++)
             GMS_LAUNCH(GMS_K_TILE_SORT, stream, tile_mergepath_kernel<<<max_deep, 256, 0, stream>>>(img.tile_offset, run_total, bin.deep_tab, max_deep, bin.keys,
@@ -1773,7 +1654,6 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
         g.unit_first = img.unit_first; g.mseg_first = img.mseg_first; g.unit_tile = bin.unit_tile; g.keys = bin.keys;
         g.seg_state = bin.seg_state; g.capacity = capacity; g.max_units = mu; g.dbg = 0; g.unit_run = unit_run(); g.dbg_buf = nullptr; g.tile_dead = img.tile_dead; g.tile_cmax = img.tile_cmax;
         g.mmask = bin.mmask;
-        if (aux) GMS_HIP_CHECK(hipStreamWaitEvent(stream, aux->join, 0));      // the colours (second stream) before the compositing
         t_last_used_micro = use_micro(capacity, T) ? 1 : 0;
         if (use_micro(capacity, T)) {
             // the micro-tile kernels index a unit's entries with one byte: never launch them on a frame whose L they cannot hold

@@ -24,7 +24,7 @@ import srchash  # noqa: E402
 NS = {"plain": 1.2, "dpp": 1.76, "wide": 1.8, "trans": 3.4}          # tools/valu_bench.hip, 8 waves per SIMD
 TRANS = ("v_exp_", "v_rcp_", "v_log_", "v_sqrt_", "v_rsq_", "v_sin_", "v_cos_")
 KERNELS = {          # bench.py's kernel name -> (file, regex on the demangled name of the shipped instantiation)
-    "blend_bwd": ("blend_micro.hip", r"micro_bwd_kernel<false, 2, 0, false, true, 256>"),
+    "blend_bwd": ("blend_micro.hip", r"micro_bwd_kernel<false, 2, 0, false>"),
     "blend_head": ("blend_micro.hip", r"micro_head_kernel<4>"),
     "blend_fwd": ("blend_micro.hip", r"micro_fwd_kernel<4>"),
 }
