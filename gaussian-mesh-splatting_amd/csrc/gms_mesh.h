@@ -74,12 +74,13 @@ __device__ __forceinline__ void face_frame(V3 t0, V3 t1, V3 t2, Frame &f)
 // rotation matrix with columns (v0,v1,v2) -> quaternion; also reports the selected candidate
 struct QuatSel { int sel; float a; float sign; float cand[4]; float xsel; };   // xsel = argument of the selected sqrt
 
-__device__ __forceinline__ void rot_to_quat(const Frame &f, float q[4], QuatSel *qs)
+// (columns given as three vectors: the face frame below, the pseudo-triangle frame of gms_points.h)
+__device__ __forceinline__ void rot_to_quat(V3 v0, V3 v1, V3 v2, float q[4], QuatSel *qs)
 {
 #pragma clang fp contract(off)
-    const float m00 = f.v0.x, m01 = f.v1.x, m02 = f.v2.x;
-    const float m10 = f.v0.y, m11 = f.v1.y, m12 = f.v2.y;
-    const float m20 = f.v0.z, m21 = f.v1.z, m22 = f.v2.z;
+    const float m00 = v0.x, m01 = v1.x, m02 = v2.x;
+    const float m10 = v0.y, m11 = v1.y, m12 = v2.y;
+    const float m20 = v0.z, m21 = v1.z, m22 = v2.z;
     float x[4] = {1.0f + m00 + m11 + m22, 1.0f + m00 - m11 - m22, 1.0f - m00 + m11 - m22, 1.0f - m00 - m11 + m22};
     float qa[4];
     int sel = 0;
@@ -108,6 +109,46 @@ __device__ __forceinline__ void rot_to_quat(const Frame &f, float q[4], QuatSel 
         for (int k = 0; k < 4; k++) qs->cand[k] = c[k];
         qs->xsel = xsel;
     }
+}
+__device__ __forceinline__ void rot_to_quat(const Frame &f, float q[4], QuatSel *qs) { rot_to_quat(f.v0, f.v1, f.v2, q, qs); }
+
+// d loss / d (columns v0, v1, v2) of rot_to_quat, given d loss / d q (the selected candidate, its 0.1 floor and the sign flip)
+__device__ __forceinline__ void quat_backward(const QuatSel &qs, const float dq[4], V3 &g0, V3 &g1, V3 &g2)
+{
+    const float den = 2.0f * fmaxf(qs.a, 0.1f);
+    float gc[4];
+    float dden = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float gk = qs.sign * dq[k];
+        gc[k] = gk / den;
+        dden -= gk * qs.cand[k] / (den * den);
+    }
+    // a enters through den (if a > 0.1) and through cand[sel] = a^2
+    const float gsel = qs.sel == 0 ? gc[0] : qs.sel == 1 ? gc[1] : qs.sel == 2 ? gc[2] : gc[3];
+    float da = (qs.a > 0.1f ? 2.f * dden : 0.f) + 2.f * qs.a * gsel;
+    const float dx = (qs.xsel > 0.f) ? da / (2.f * qs.a) : 0.f;   // a = sqrt(x), zero subgradient at x <= 0
+    float d00 = 0, d01 = 0, d02 = 0, d10 = 0, d11 = 0, d12 = 0, d20 = 0, d21 = 0, d22 = 0;
+    switch (qs.sel) {
+    case 0:
+        d00 += dx; d11 += dx; d22 += dx;
+        d21 += gc[1]; d12 -= gc[1]; d02 += gc[2]; d20 -= gc[2]; d10 += gc[3]; d01 -= gc[3];
+        break;
+    case 1:
+        d00 += dx; d11 -= dx; d22 -= dx;
+        d21 += gc[0]; d12 -= gc[0]; d10 += gc[2]; d01 += gc[2]; d02 += gc[3]; d20 += gc[3];
+        break;
+    case 2:
+        d00 -= dx; d11 += dx; d22 -= dx;
+        d02 += gc[0]; d20 -= gc[0]; d10 += gc[1]; d01 += gc[1]; d12 += gc[3]; d21 += gc[3];
+        break;
+    default:
+        d00 -= dx; d11 -= dx; d22 += dx;
+        d10 += gc[0]; d01 -= gc[0]; d20 += gc[1]; d02 += gc[1]; d21 += gc[2]; d12 += gc[2];
+        break;
+    }
+    // m[i][j] = v_j[i]
+    g0 = {d00, d10, d20}; g1 = {d01, d11, d21}; g2 = {d02, d12, d22};
 }
 
 // host: sizes / tables of a GmsMeshArgs are consistent (F * splats_per_face == P or the CSR tables present, a known alpha_mode, no
@@ -206,40 +247,8 @@ __device__ __forceinline__ void face_backward(const GmsMeshArgs &a, int f, const
 #pragma unroll
         for (int k = 0; k < 4; k++) G.dq[k] = (G.dq[k] - u[k] * d) / n;
     }
-    const float den = 2.0f * fmaxf(qs.a, 0.1f);
-    float gc[4];
-    float dden = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const float gk = qs.sign * G.dq[k];
-        gc[k] = gk / den;
-        dden -= gk * qs.cand[k] / (den * den);
-    }
-    // a enters through den (if a > 0.1) and through cand[sel] = a^2
-    const float gsel = qs.sel == 0 ? gc[0] : qs.sel == 1 ? gc[1] : qs.sel == 2 ? gc[2] : gc[3];
-    float da = (qs.a > 0.1f ? 2.f * dden : 0.f) + 2.f * qs.a * gsel;
-    const float dx = (qs.xsel > 0.f) ? da / (2.f * qs.a) : 0.f;   // a = sqrt(x), zero subgradient at x <= 0
-    float d00 = 0, d01 = 0, d02 = 0, d10 = 0, d11 = 0, d12 = 0, d20 = 0, d21 = 0, d22 = 0;
-    switch (qs.sel) {
-    case 0:
-        d00 += dx; d11 += dx; d22 += dx;
-        d21 += gc[1]; d12 -= gc[1]; d02 += gc[2]; d20 -= gc[2]; d10 += gc[3]; d01 -= gc[3];
-        break;
-    case 1:
-        d00 += dx; d11 -= dx; d22 -= dx;
-        d21 += gc[0]; d12 -= gc[0]; d10 += gc[2]; d01 += gc[2]; d02 += gc[3]; d20 += gc[3];
-        break;
-    case 2:
-        d00 -= dx; d11 += dx; d22 -= dx;
-        d02 += gc[0]; d20 -= gc[0]; d10 += gc[1]; d01 += gc[1]; d12 += gc[3]; d21 += gc[3];
-        break;
-    default:
-        d00 -= dx; d11 -= dx; d22 += dx;
-        d10 += gc[0]; d01 -= gc[0]; d20 += gc[1]; d02 += gc[1]; d21 += gc[2]; d12 += gc[2];
-        break;
-    }
-    // m[i][j] = v_j[i]
-    V3 g0 = {d00, d10, d20}, g1 = {d01, d11, d21}, g2 = {d02, d12, d22};
+    V3 g0, g1, g2;
+    quat_backward(qs, G.dq, g0, g1, g2);
 
     // ---- scales
     float g_v1n = G.ds1 * 0.5f;                       // s1 = v1n / 2

@@ -30,6 +30,7 @@
 
 #include "gms_blend.h"
 #include "gms_mesh.h"
+#include "gms_points.h"
 #include <atomic>
 #include <vector>
 #include <chrono>
@@ -137,12 +138,16 @@ __device__ __forceinline__ void sh_colour(const float *row_lds, float x, float y
 // Gaussian from the mesh -- barycentric centre, face frame -> activated scale and unit quaternion, sigmoid opacity, the statements
 // of mesh_fwd_kernel (gms_mesh.h::splat_from_face) -- instead of loading means3D / scales / rotations / opacities: those four
 // tensors (44 bytes per Gaussian written by K0 and read back here, plus K0's raw copies) never reach HBM and the K0 launch is gone.
-template <int SHDEG, bool SPLIT, bool DMA = false, bool K0 = false>
-__device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a)
+// PTS (ABI 9; forward-only frames of the gs_points drivers, scripts/render_points_time_animated.py): the same from the Gaussian's own
+// pseudo-triangle -- 36 bytes of triangle and 4 of raw opacity in, the statements of points_fwd_kernel (gms_points.h) -- `pts` is only
+// read by that instantiation.
+template <int SHDEG, bool SPLIT, bool DMA = false, bool K0 = false, bool PTS = false>
+__device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsPointsArgs &pts = GmsPointsArgs{})
 {
 #pragma clang fp contract(off)
     static_assert(!DMA || (SHDEG >= 0 && SHDEG <= 3 && SPLIT), "the LDS-DMA staging exists for split degree-3 STORAGE (any active degree: the rows come in whole)");
     static_assert(!K0 || DMA, "the fused mesh input rides on the LDS-DMA instantiation");
+    static_assert(!PTS || (DMA && !K0), "the fused points input rides on the LDS-DMA instantiation, without the mesh input");
     static_assert(DMA || !SPLIT || SHDEG != 3, "split degree-3 storage is staged by LDS-DMA (the register-staged rows were measured and removed)");
     // Round 6: the REST rows come in as TWO halves of 32 rows through the same 6 KB of LDS per wave (6 x 1 KiB DMA instructions each,
     // 1 440 of the 1 536 floats used), the 64 x 3 DC floats behind them: 27 KB per block instead of 49.
@@ -172,6 +177,8 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a)
     float op_in = 0.f;
     SplatInputs k0in = {};
     if (K0 && valid) splat_inputs_load(a.mesh, (int64_t)i, k0in);          // (in front of the SH rows' DMA: see gms_mesh.h)
+    PointsInputs ptin = {};
+    if (PTS && valid) points_inputs_load(pts, (int64_t)i, ptin);           // (likewise)
     if (SHDEG >= 0) {
         const int g0 = blockIdx.x * BLOCK + wave * WAVE;
         const int rows = min(WAVE, a.P - g0);
@@ -208,7 +215,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a)
                 dcv[j] = e < rows * 3 ? a.shs[(size_t)g0 * 3 + e] : 0.f;
             }
         }
-        if (valid && !K0) {
+        if (valid && !K0 && !PTS) {
             op_in = a.opac[i];
             if (!a.cov3Dp) {
                 s_in[0] = a.scales[3 * (size_t)i]; s_in[1] = a.scales[3 * (size_t)i + 1]; s_in[2] = a.scales[3 * (size_t)i + 2];
@@ -235,6 +242,16 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a)
                 *reinterpret_cast<float4 *>(a.k0_rot + 4 * (size_t)i) = q_in;
                 a.k0_opac[i] = op_in;
             }
+            view_transform(a.view, px, py, pz, vx, vy, vz); vis = vz > NEAR_Z;
+        }
+    } else if (PTS) {
+        if (valid) {
+            SplatParams sp;
+            points_from_inputs(pts, ptin, sp, nullptr);
+            px = sp.xyz[0]; py = sp.xyz[1]; pz = sp.xyz[2];
+            s_in[0] = sp.scale[0]; s_in[1] = sp.scale[1]; s_in[2] = sp.scale[2];
+            q_in = make_float4(sp.q[0], sp.q[1], sp.q[2], sp.q[3]);
+            op_in = sp.opacity;
             view_transform(a.view, px, py, pz, vx, vy, vz); vis = vz > NEAR_Z;
         }
     } else if (valid) {
@@ -467,6 +484,12 @@ template <bool K0, int DEG = 3>
 __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5))) preprocess_fwd_dma_kernel(PreArgs a)
 {
     preprocess_fwd_body<DEG, true, true, K0>(a);
+}
+// ... the frame straight from pseudo-triangles (GmsRasterForwardArgs.points): the same launch bounds and occupancy as the mesh one
+template <int DEG>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5))) preprocess_fwd_points_kernel(PreArgs a, GmsPointsArgs pts)
+{
+    preprocess_fwd_body<DEG, true, true, false, true>(a, pts);
 }
 
 // ------------------------------------------------------------------------------------ K2
@@ -1429,7 +1452,25 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
     const int P = A->P, W = A->width, H = A->height;
     const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, T = gx * gy;
     const GmsMeshArgs *mesh = A->mesh;          // forward-only frame straight from a mesh (gmsplat.h): K0 runs inside the preprocess thread
-    if (P > 0 && mesh) {
+    const GmsPointsArgs *points = A->points;    // ... or straight from pseudo-triangles (ABI 9)
+    if (mesh && points) {
+        set_error("gms_rasterize_forward: set at most one of mesh / points");
+        return GMS_ERR_INVALID_ARGUMENT;
+    }
+    if (P > 0 && points) {
+        const int32_t prc = check_points_args(points);
+        if (prc != GMS_OK) return prc;
+        if (points->P != (int64_t)P || !points->_opacity || !A->shs || !A->shs_rest || A->M != 16 || A->D < 0 || A->D > 3 || A->colors_precomp ||
+            A->cov3D_precomp || (((uintptr_t)A->shs) & 15u) || (((uintptr_t)A->shs_rest) & 15u)) {
+            set_error("gms_rasterize_forward: the fused points input needs a complete GmsPointsArgs (P equal, _opacity set), split degree-3 SH "
+                      "storage (shs + shs_rest, M = 16, active degree 0 .. 3, 16-byte aligned) and no precomputed colours / covariances");
+            return GMS_ERR_INVALID_ARGUMENT;
+        }
+        if (!A->viewmatrix || !A->projmatrix || !A->campos || !A->radii || !A->geom_alloc || !A->binning_alloc || !A->image_alloc) {
+            set_error("gms_rasterize_forward: null input pointer or callback");
+            return GMS_ERR_INVALID_ARGUMENT;
+        }
+    } else if (P > 0 && mesh) {
         // the thread of a Gaussian reads faces / vertices / _alpha through the same tables as the K0 launch: same checks
         const int32_t mrc = check_mesh_args(mesh, false);
         if (mrc != GMS_OK) return mrc;
@@ -1528,6 +1569,9 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
     pa.scales = A->scales; pa.rots = A->rotations; pa.cov3Dp = A->cov3D_precomp; pa.view = A->viewmatrix;
     pa.proj = A->projmatrix; pa.campos = A->campos; pa.mod = A->scale_modifier; pa.tanx = A->tan_fovx;
     pa.tany = A->tan_fovy; pa.aa = A->antialiasing; pa.radii = A->radii; pa.visible = A->visible; pa.geom = geom; pa.tile_count = img.tile_count;
+    if (mesh || points) {
+        pa.means3D = nullptr; pa.opac = nullptr; pa.scales = nullptr; pa.rots = nullptr; pa.cov3Dp = nullptr;
+    }
     if (mesh) {
         pa.mesh = *mesh; pa.means3D = nullptr; pa.opac = nullptr; pa.scales = nullptr; pa.rots = nullptr; pa.cov3Dp = nullptr;
         pa.k0_xyz = A->mesh_out_xyz; pa.k0_scale = A->mesh_out_scaling_act; pa.k0_rot = A->mesh_out_rotation_unit; pa.k0_opac = A->mesh_out_opacity_act;
@@ -1546,13 +1590,20 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
     const unsigned pblocks = (unsigned)((P + BLOCK - 1) / BLOCK);
     const bool split = A->shs_rest != nullptr;
     const bool sh_fast = A->shs && A->M == 16 && (((uintptr_t)A->shs) & 15u) == 0 && (((uintptr_t)A->shs_rest) & 15u) == 0 &&
-                         (mesh || A->cov3D_precomp || (((uintptr_t)A->rotations) & 15u) == 0);
+                         (mesh || points || A->cov3D_precomp || (((uintptr_t)A->rotations) & 15u) == 0);
     if (split && !sh_fast) {
         set_error("split SH storage (shs_rest) needs M == 16 and 16-byte aligned pointers");
         return GMS_ERR_INVALID_ARGUMENT;
     }
 #define GMS_PRE(DEG, SP) GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_kernel<DEG, SP><<<pblocks, BLOCK, 0, stream>>>(pa)))
-    if (mesh) {          // (validated above: split degree-3 storage; the active degree picks the instantiation)
+    if (points) {        // (validated above: split degree-3 storage; the active degree picks the instantiation)
+        switch (A->D) {
+        case 0: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_points_kernel<0><<<pblocks, BLOCK, 0, stream>>>(pa, *points))); break;
+        case 1: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_points_kernel<1><<<pblocks, BLOCK, 0, stream>>>(pa, *points))); break;
+        case 2: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_points_kernel<2><<<pblocks, BLOCK, 0, stream>>>(pa, *points))); break;
+        default: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_points_kernel<3><<<pblocks, BLOCK, 0, stream>>>(pa, *points))); break;
+        }
+    } else if (mesh) {   // (validated above: split degree-3 storage; the active degree picks the instantiation)
         switch (A->D) {
         case 0: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<true, 0><<<pblocks, BLOCK, 0, stream>>>(pa))); break;
         case 1: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<true, 1><<<pblocks, BLOCK, 0, stream>>>(pa))); break;

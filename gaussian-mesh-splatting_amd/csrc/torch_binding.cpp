@@ -124,11 +124,12 @@ Forward forward_core(const Tensor &bg_, const Tensor &means3D_, const Tensor &sh
                      const Tensor &opac_, const Tensor &scales_, const Tensor &rots_, const Tensor &cov_, const Tensor &view_,
                      const Tensor &proj_, const Tensor &campos_, int64_t H, int64_t W, double tanx, double tany, double mod, int64_t D,
                      bool prefiltered, bool aa, bool debug, const Tensor &visible, bool use_hint, const GmsMeshArgs *mesh = nullptr,
-                     const MeshOut *mesh_out = nullptr, bool may_defer = false)
+                     const MeshOut *mesh_out = nullptr, bool may_defer = false, const GmsPointsArgs *points = nullptr)
 {
     // (`mesh`: the forward-only frame straight from a mesh, gmsplat.h; `means3D_` then only carries the device and P -- the SH DC tensor)
     require_gpu(means3D_); require_gpu(bg_); require_gpu(view_); require_gpu(proj_); require_gpu(campos_);
-    TORCH_CHECK(mesh || (means3D_.dim() == 2 && means3D_.size(1) == 3), "means3D must have dimensions (num_points, 3)");
+    // (`points`: the same, straight from pseudo-triangles, ABI 9)
+    TORCH_CHECK(mesh || points || (means3D_.dim() == 2 && means3D_.size(1) == 3), "means3D must have dimensions (num_points, 3)");
     const auto dev = means3D_.device();
     c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
     const int64_t P = means3D_.size(0);
@@ -180,7 +181,8 @@ Forward forward_core(const Tensor &bg_, const Tensor &means3D_, const Tensor &sh
     a.num_units_out = &num_units;
     a.no_host_wait = capturing ? 1 : 0;
     a.mesh = mesh;
-    if (mesh) { a.means3D = nullptr; a.opacities = nullptr; a.scales = nullptr; a.rotations = nullptr; }
+    a.points = points;
+    if (mesh || points) { a.means3D = nullptr; a.opacities = nullptr; a.scales = nullptr; a.rotations = nullptr; }
     if (mesh && mesh_out) {
         a.mesh_out_xyz = mf(mesh_out->xyz); a.mesh_out_scaling_act = mf(mesh_out->scaling_act);
         a.mesh_out_rotation_unit = mf(mesh_out->rotation_unit); a.mesh_out_opacity_act = mf(mesh_out->opacity_act);
@@ -642,6 +644,119 @@ std::vector<Tensor> mesh_to_gaussians(const Tensor &vertices, const Tensor &face
                          at::GradMode::is_enabled() && vertices.requires_grad());
 }
 
+// ---------------------------------------------------------------------------------------------- pseudo-triangle -> Gaussian (gs_points)
+GmsPointsArgs points_args(const Tensor &triangles, const Tensor &_opacity, double eps, double eps_s0)
+{
+    GmsPointsArgs a{};
+    a.P = triangles.size(0); a.triangles = cf(triangles); a._opacity = cf(_opacity); a.eps = (float)eps; a.eps_s0 = (float)eps_s0;
+    return a;
+}
+
+Tensor points_triangles(const Tensor &triangles_, const char *what)
+{
+    require_gpu(triangles_);
+    TORCH_CHECK(triangles_.dim() == 3 && triangles_.size(1) == 3 && triangles_.size(2) == 3, what, ": triangles must have dimensions (P, 3, 3)");
+    return f32c(triangles_);
+}
+
+// prepare_vertices (games/flat_splatting/scene/points_gaussian_model.py:28-58): (xyz [P,3], _scaling [P,2|3], _rotation [P,4]) -> [P,3,3]
+Tensor points_prepare_vertices(const Tensor &xyz_, const Tensor &scaling_, const Tensor &rotation_)
+{
+    require_gpu(xyz_); require_gpu(scaling_); require_gpu(rotation_);
+    Tensor xyz = f32c(xyz_), scaling = f32c(scaling_), rotation = f32c(rotation_);
+    const int64_t P = xyz.size(0);
+    TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3 && scaling.dim() == 2 && (scaling.size(1) == 2 || scaling.size(1) == 3) && rotation.dim() == 2 &&
+                rotation.size(1) == 4 && scaling.size(0) == P && rotation.size(0) == P,
+                "points_prepare_vertices: xyz [P,3], scaling [P,2] or [P,3], rotation [P,4]");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(xyz.device());
+    Tensor out = torch::empty({P, 3, 3}, xyz.options().dtype(torch::kFloat));
+    check_rc(gms_points_prepare_vertices(P, cf(xyz), cf(scaling), (int32_t)scaling.size(1), cf(rotation), mf(out), stream_of(xyz)),
+             "gms_points_prepare_vertices");
+    return out;
+}
+
+class PointsFn : public torch::autograd::Function<PointsFn> {
+public:
+    // -> xyz, scaling_raw [P,2], rotation_raw [P,4], scaling_act [P,3], rotation_unit [P,4][, opacity_act [P,1]]; the raw storage is not
+    // differentiable (the gradient reaches the triangles through the getters' outputs, as the reference's renderer reads them)
+    static variable_list forward(AutogradContext *ctx, Tensor triangles_, Tensor opacity_, double eps, double eps_s0)
+    {
+        ctx->set_materialize_grads(false);
+        Tensor triangles = points_triangles(triangles_, "points_to_gaussians");
+        require_gpu(opacity_);
+        const auto dev = triangles.device();
+        c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+        const int64_t P = triangles.size(0);
+        const bool has_op = opacity_.defined() && opacity_.numel() > 0;
+        Tensor _opacity = f32c(opacity_);
+        if (has_op) TORCH_CHECK(_opacity.numel() == P && _opacity.device() == dev, "points_to_gaussians: _opacity must hold P values on the triangles' device");
+        auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
+        Tensor xyz = torch::empty({P, 3}, fopt), scaling = torch::empty({P, 2}, fopt), rotation = torch::empty({P, 4}, fopt);
+        Tensor sact = torch::empty({P, 3}, fopt), runit = torch::empty({P, 4}, fopt), oact;
+        if (has_op) oact = torch::empty_like(_opacity);
+        GmsPointsArgs a = points_args(triangles, _opacity, eps, eps_s0);
+        check_rc(gms_points_to_gaussians_forward(&a, mf(xyz), mf(scaling), mf(rotation), mf(sact), mf(runit), mf(oact), stream_of(triangles)),
+                 "gms_points_to_gaussians_forward");
+        ctx->save_for_backward({triangles, has_op ? _opacity : torch::empty({0}, fopt)});
+        ctx->saved_data["eps"] = eps; ctx->saved_data["eps_s0"] = eps_s0;
+        ctx->mark_non_differentiable({scaling, rotation});
+        if (has_op) return {xyz, scaling, rotation, sact, runit, oact};
+        return {xyz, scaling, rotation, sact, runit};
+    }
+
+    static variable_list backward(AutogradContext *ctx, variable_list g)
+    {
+        auto s = ctx->get_saved_variables();
+        const Tensor &triangles = s[0];
+        Tensor _opacity = s[1].numel() ? s[1] : Tensor();
+        const auto dev = triangles.device();
+        c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+        const int64_t P = triangles.size(0);
+        auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
+        auto gz = [&](const Tensor &t, int64_t c) { return t.defined() ? f32c(t) : torch::zeros({P, c}, fopt); };
+        Tensor g_xyz = gz(g[0], 3), g_scaling = gz(g.size() > 3 ? g[3] : Tensor(), 3), g_rot = gz(g.size() > 4 ? g[4] : Tensor(), 4);
+        Tensor g_op = g.size() > 5 ? g[5] : Tensor();
+        const bool want_op = _opacity.defined() && g_op.defined();
+        Tensor d_tri = torch::empty_like(triangles), d_opacity;
+        if (want_op) { g_op = f32c(g_op); d_opacity = torch::empty_like(_opacity); }
+        GmsPointsArgs a = points_args(triangles, _opacity, ctx->saved_data["eps"].toDouble(), ctx->saved_data["eps_s0"].toDouble());
+        check_rc(gms_points_to_gaussians_backward(&a, cf(g_xyz), cf(g_scaling), cf(g_rot), want_op ? cf(g_op) : nullptr, mf(d_tri),
+                                                  want_op ? mf(d_opacity) : nullptr, stream_of(triangles)),
+                 "gms_points_to_gaussians_backward");
+        return {d_tri, d_opacity, Tensor(), Tensor()};
+    }
+};
+
+std::vector<Tensor> points_to_gaussians(const Tensor &triangles, const Tensor &_opacity, double eps, double eps_s0)
+{
+    return PointsFn::apply(triangles, _opacity, eps, eps_s0);
+}
+
+// Forward-only frame of the gs_points render drivers (games_hip.render.render_points_animated): pseudo-triangles -> image in the
+// rasterizer's own launches, the points op inside the preprocess thread (GmsRasterForwardArgs.points).  Returns (image, radii,
+// inverse depth, radii > 0).
+std::tuple<Tensor, Tensor, Tensor, Tensor> render_points_forward(const Tensor &triangles_, const Tensor &_opacity, const Tensor &sh_dc,
+                                                         const Tensor &sh_rest, const Tensor &bg, const Tensor &view, const Tensor &proj,
+                                                         const Tensor &campos, int64_t H, int64_t W, double tanx, double tany, double mod,
+                                                         bool aa, bool debug, int64_t sh_degree, double eps, double eps_s0)
+{
+    Tensor tri = points_triangles(triangles_, "render_points_forward");
+    require_gpu(_opacity); require_gpu(sh_dc); require_gpu(sh_rest);
+    Tensor op = f32c(_opacity);
+    const int64_t P = tri.size(0);
+    TORCH_CHECK(sh_degree >= 0 && sh_degree <= 3, "render_points_forward: active SH degree ", sh_degree, " (storage is degree 3: 0 .. 3)");
+    TORCH_CHECK(op.numel() == P && sh_dc.size(0) == P && sh_rest.size(0) == P, "render_points_forward: P mismatch");
+    TORCH_CHECK(tri.device() == sh_dc.device() && op.device() == sh_dc.device(), "render_points_forward: triangles and SH tensors live on different devices");
+    TORCH_CHECK(sh_dc.dim() == 3 && sh_dc.size(1) == 1 && sh_rest.dim() == 3 && sh_rest.size(1) == 15, "render_points_forward needs split degree-3 SH storage ([P,1,3] + [P,15,3])");
+    GmsPointsArgs pa = points_args(tri, op, eps, eps_s0);
+    // (P stands in for means3D: forward_core reads the device and the count from its first tensor argument)
+    Tensor stand_in = sh_dc.view({P, 3});
+    Tensor visible = torch::empty({P}, sh_dc.options().dtype(torch::kBool));          // radii > 0, written by the preprocess kernel
+    Forward f = forward_core(bg, stand_in, sh_dc, sh_rest, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), view, proj, campos, H, W, tanx, tany, mod,
+                             sh_degree, false, aa, debug, visible, true, nullptr, nullptr, false, &pa);
+    return std::make_tuple(f.color, f.radii, f.invdepth, visible);
+}
+
 // ---------------------------------------------------------------------------------------------- training frame straight from the mesh
 // train.py:100-108 with the K0 launch of train.py:154-157 folded into the rasterizer's preprocess thread (GmsRasterForwardArgs.mesh +
 // mesh_out_*, ABI 6): ONE autograd node from (vertices, _alpha, _scale, _opacity, SH) to the image.  Forward: no K0 launch -- the
@@ -872,6 +987,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("rasterize", &rasterize, "differentiable rasterization (autograd node in C++)", nogil());
     m.def("mesh_to_gaussians", &mesh_to_gaussians, "differentiable mesh-face -> Gaussian parameterization", nogil());
     m.def("render_mesh_forward", &render_mesh_forward, "forward-only frame straight from a mesh (K0 inside the preprocess thread)", nogil());
+    m.def("points_to_gaussians", &points_to_gaussians, "differentiable pseudo-triangle -> Gaussian: [xyz, scaling_raw, rotation_raw, scaling_act, rotation_unit(, opacity_act)]", nogil());
+    m.def("points_prepare_vertices", &points_prepare_vertices, "Gaussian -> pseudo-triangle [P,3,3] (prepare_vertices)", nogil());
+    m.def("render_points_forward", &render_points_forward, "forward-only frame straight from pseudo-triangles (the points op inside the preprocess thread)", nogil());
     m.def("render_mesh", &render_mesh, "differentiable frame straight from a mesh: [image, radii, invdepth, xyz, scaling_act, rotation_unit, opacity_act]", nogil());
     m.def("l1_ssim", &l1_ssim, "differentiable w_l1 * L1 + w_ssim * SSIM + bias; returns (value [0-dim], [l1, ssim])", nogil());
     m.def("adam_step", &adam_step, nogil());

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("GMSPLAT_LIB", os.path.join(os.path.dirname(_HERE), "l
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 
-GMS_ABI_VERSION = 8
+GMS_ABI_VERSION = 9
 GMS_ALPHA_RELU, GMS_ALPHA_SOFTMAX = 0, 1
 ERRORS = {-1: "invalid argument", -2: "scratch allocation failed", -3: "HIP runtime error", -4: "capacity"}
 
@@ -38,6 +38,7 @@ class RasterForwardArgs(C.Structure):
         # ABI 6: what the fused frame derived, stored for the backward (all NULL: a forward-only frame)
         ("mesh_out_xyz", C.c_void_p), ("mesh_out_scaling_act", C.c_void_p), ("mesh_out_rotation_unit", C.c_void_p), ("mesh_out_opacity_act", C.c_void_p),
         ("count_ticket_out", C.c_void_p),          # ABI 7: host int64*, deferred read-back of the frame's counts (gms_rasterize_forward_counts)
+        ("points", C.c_void_p),        # ABI 9: const GmsPointsArgs * (frame straight from pseudo-triangles) or NULL
     ]
 
 
@@ -70,6 +71,13 @@ class MeshArgs(C.Structure):
         ("vertices", C.c_void_p), ("faces", C.c_void_p), ("face_splat_offset", C.c_void_p), ("splat_face", C.c_void_p),
         ("_alpha", C.c_void_p), ("_scale", C.c_void_p), ("fused_activations", C.c_int32), ("_opacity", C.c_void_p),
         ("prezero", C.c_void_p), ("prezero_count", C.c_int64), ("vertex_grad_prezeroed", C.c_int32),
+    ]
+
+
+class PointsArgs(C.Structure):
+    """GmsPointsArgs (include/gmsplat.h, ABI 9)."""
+    _fields_ = [
+        ("P", C.c_int64), ("triangles", C.c_void_p), ("_opacity", C.c_void_p), ("eps", C.c_float), ("eps_s0", C.c_float),
     ]
 
 
@@ -106,8 +114,9 @@ EXPORTS = (
     "gms_sh_grad_expand", "gms_set_fault", "gms_get_fault", "gms_set_deterministic", "gms_get_deterministic",
     "gms_image_counts_offset", "gms_last_launched_units", "gms_last_used_micro",
     "gms_set_upstream_scale_mod_grad", "gms_get_upstream_scale_mod_grad", "gms_profile_event_overhead_us",
+    "gms_points_prepare_vertices", "gms_points_to_gaussians_forward", "gms_points_to_gaussians_backward",
 )
-K_COUNT = 17
+K_COUNT = 20
 
 _lock = threading.Lock()
 _lib = None
@@ -137,6 +146,12 @@ def load():
         lib.gms_mesh_to_gaussians_forward.argtypes = [C.POINTER(MeshArgs)] + [C.c_void_p] * 8
         lib.gms_mesh_to_gaussians_backward.restype = C.c_int32
         lib.gms_mesh_to_gaussians_backward.argtypes = [C.POINTER(MeshArgs)] + [C.c_void_p] * 9
+        lib.gms_points_prepare_vertices.restype = C.c_int32
+        lib.gms_points_prepare_vertices.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gms_points_to_gaussians_forward.restype = C.c_int32
+        lib.gms_points_to_gaussians_forward.argtypes = [C.POINTER(PointsArgs)] + [C.c_void_p] * 7
+        lib.gms_points_to_gaussians_backward.restype = C.c_int32
+        lib.gms_points_to_gaussians_backward.argtypes = [C.POINTER(PointsArgs)] + [C.c_void_p] * 7
         lib.gms_abi_version.restype = C.c_int32
         lib.gms_last_error.restype = C.c_char_p
         for n in ("gms_geom_bytes", "gms_image_bytes", "gms_binning_bytes", "gms_image_n_contrib_offset"):

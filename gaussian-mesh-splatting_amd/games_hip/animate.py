@@ -20,7 +20,7 @@ from typing import Callable, Iterable, List, Optional
 
 import torch
 
-from .render import _fused_frame_ok, render, render_animated, render_mesh_frame
+from .render import _fused_frame_ok, render, render_animated, render_mesh_frame, render_points_animated
 
 
 def _sel(idxs):
@@ -153,21 +153,21 @@ class GraphedAnimation:
         dev = triangles.device
         self.static_tri = triangles.detach().clone()
         W, H = int(self.view.image_width), int(self.view.image_height)
-        P = int(self.pc._alpha.shape[0] * self.pc._alpha.shape[1])
+        P = self._num_gaussians()
         self.stream.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(self.stream):
             for _ in range(max(self.warmup, 1)):          # ordinary frames: hints, pools, the library's per-stream buffers
-                render_animated(None, self.static_tri, self.view, self.pc, self.pipe, self.bg)
+                self._frame(self.static_tri)
             if slack > 1.0:                                # a re-capture after an overflow: leave room above this frame's count
                 n = int(dgr.last_stats()["num_rendered"])
                 dgr.set_capacity_hint(dev.index if dev.index is not None else torch.cuda.current_device(), W, H, P, int(n * slack))
-                render_animated(None, self.static_tri, self.view, self.pc, self.pipe, self.bg)
+                self._frame(self.static_tri)
             self.stream.synchronize()
             kept = bool(getattr(dgr, "_keep_buffers", False))      # (the caller's own setting is restored below)
             dgr.keep_buffers(True)                         # the captured frame's image scratch holds its counts: keep the handle
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, stream=self.stream):
-                self.out = render_animated(None, self.static_tri, self.view, self.pc, self.pipe, self.bg)["render"]
+                self.out = self._frame(self.static_tri)["render"]
             st = dict(dgr._C.last_stats())
             if not kept:
                 dgr.keep_buffers(False)
@@ -177,6 +177,13 @@ class GraphedAnimation:
         self._counts_off = int(dgr._C.image_counts_offset(W, H))
         self.captures += 1
         torch.cuda.current_stream(dev).wait_stream(self.stream)
+
+    # ---- what one frame is (GraphedPointsAnimation renders pseudo-triangles instead)
+    def _frame(self, triangles: torch.Tensor) -> dict:
+        return render_animated(None, triangles, self.view, self.pc, self.pipe, self.bg)
+
+    def _num_gaussians(self) -> int:
+        return int(self.pc._alpha.shape[0] * self.pc._alpha.shape[1])
 
     def status(self) -> dict:
         """Counts of the most recent replayed frame (device -> host copy of 16 bytes) and whether it fitted the capture."""
@@ -207,3 +214,52 @@ class GraphedAnimation:
                 self.graph.replay()
         torch.cuda.current_stream(dev).wait_stream(self.stream)
         return self.out
+
+
+# ---------------------------------------------------------------------------------------------- gs_points (pseudo-mesh workflow)
+def transform_hotdog(triangles, t):                        # scripts/render_points_time_animated.py:27-30 (copy)
+    triangles_new = triangles.clone()
+    triangles_new[:, :, 2] += 0.3 * torch.sin(triangles[:, :, 0] * torch.pi + float(t))
+    return triangles_new
+
+
+@torch.no_grad()
+def render_points_time_animated(gaussians, views: Iterable, pipeline, background: torch.Tensor, transform: Callable = transform_hotdog,
+                                out_dir: Optional[str] = None, t_max: float = 10 * math.pi, frame_index: Optional[int] = 43) -> List[torch.Tensor]:
+    """scripts/render_points_time_animated.py:33-48 (render_set) + :51-57: prepare_vertices / prepare_scaling_rot once, then per view
+    the pseudo-triangles are deformed by `transform(triangles, t)` and rendered with `render_points_animated` -- straight from the
+    triangles inside the rasterizer where the fused path applies.  `frame_index`: the reference renders every view at t[43] of
+    linspace(0, 10 pi, len(views)); None deforms view k with t[k] instead.  Returns the frames (device tensors [3,H,W])."""
+    views = list(views)
+    if hasattr(gaussians, "prepare_vertices"):
+        gaussians.prepare_vertices()
+    if hasattr(gaussians, "prepare_scaling_rot"):
+        gaussians.prepare_scaling_rot()
+    ts = torch.linspace(0, t_max, max(len(views), 1))
+    triangles = torch.stack([gaussians.v1, gaussians.v2, gaussians.v3], dim=1)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+    frames = []
+    for k, view in enumerate(views):
+        t = ts[frame_index] if frame_index is not None and frame_index < len(ts) else ts[k]
+        img = render_points_animated(transform(triangles, t), view, gaussians, pipeline, background)["render"]
+        frames.append(img)
+        if out_dir:
+            _save(img, os.path.join(out_dir, f"{k:05d}.png"))
+    return frames
+
+
+class GraphedPointsAnimation(GraphedAnimation):
+    """GraphedAnimation for gs_points frames: one frame = deformed pseudo-triangles [P,3,3] -> `render_points_animated` (the fused
+    points frame, or the points op + rasterizer where that does not apply), captured once and replayed.
+
+        anim = GraphedPointsAnimation(gaussians, view, pipeline, background)
+        for k in range(n_frames):
+            img = anim.render(transform_hotdog(triangles, t[k]), check=True)
+    """
+
+    def _frame(self, triangles: torch.Tensor) -> dict:
+        return render_points_animated(triangles, self.view, self.pc, self.pipe, self.bg)
+
+    def _num_gaussians(self) -> int:
+        return int(self.static_tri.shape[0])

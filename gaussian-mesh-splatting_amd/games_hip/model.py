@@ -7,6 +7,10 @@ nothing else (dataset readers, optimizer groups, PLY I/O stay the host class's):
   HipMultiMeshMixin  GaussianMultiMeshModel   games/multi_mesh_splatting/scene/gaussian_multi_mesh_model.py:99-199
   HipFlameMixin      GaussianFlameModel       games/flame_splatting/scene/gaussian_flame_model.py:123-207
 
+A fourth, `HipPointsMixin`, does the same for the pseudo-mesh workflow's `PointsGaussianModel`
+(games/flat_splatting/scene/points_gaussian_model.py:28-109: prepare_vertices, prepare_scaling_rot and the getters) and is installed
+separately by `install_points()`.
+
 `install()` puts them into both registries of games/__init__.py:35-51 (`gaussianModel` used by train.py,
 `gaussianModelRender` used by scripts/render.py:22,41).  The stand-alone classes at the bottom
 (`HipGaussianMeshModel`, `HipGaussianMultiMeshModel`, `HipGaussianFlameModel`) carry the same mixins on minimal hosts
@@ -22,6 +26,7 @@ import torch
 from torch import nn
 
 from .mesh_op import mesh_to_gaussians, triangles_to_gaussians
+from .points_op import points_prepare_vertices, points_to_gaussians
 
 
 class _Stamp:
@@ -325,6 +330,61 @@ class HipMultiMeshMixin(_HipGetters):
 
 # ---------------------------------------------------------------------------------------------------------------
 # Stand-alone hosts (no dependency on the reference tree) used by bench.py / the GPU tests
+class HipPointsMixin(_HipGetters):
+    """PointsGaussianModel (games/flat_splatting/scene/points_gaussian_model.py): the pseudo-triangle <-> Gaussian arithmetic on the
+    points kernels (csrc/points.hip).  Host class provides _xyz [P,3], _scaling [P,2] (gs_flat storage) or [P,3], _rotation [P,4],
+    _opacity [P,1].  Both methods set the attributes the reference sets, with its shapes and dtypes: prepare_vertices -> v1 / v2 / v3
+    [P,3] and triangles [P,3,3]; prepare_scaling_rot -> _scaling [P,2] and _rotation [P,4]; the getters then serve the kernel's
+    activated outputs (get_scaling [P,3] with the constant eps_s0 column, get_rotation, get_opacity).  With grad enabled the
+    triangles and `_opacity` receive their gradients through one autograd node, as through the reference's torch graph.  Tensors
+    that are not on a GPU take the host class's own methods."""
+
+    eps_s0 = 1e-8
+
+    @staticmethod
+    def _hip_on_gpu(*tensors):
+        return all(torch.is_tensor(t) and t.is_cuda for t in tensors)
+
+    def prepare_vertices(self):
+        xyz, scaling, rotation = self._xyz, self._scaling, self._rotation
+        differentiated = torch.is_grad_enabled() and any(t.requires_grad for t in (xyz, scaling, rotation) if torch.is_tensor(t))
+        if not self._hip_on_gpu(xyz, scaling, rotation) or differentiated or scaling.dim() != 2 or scaling.shape[1] not in (2, 3):
+            return super().prepare_vertices()
+        tri = points_prepare_vertices(xyz, scaling, rotation)
+        self.v1, self.v2, self.v3 = tri[:, 0], tri[:, 1], tri[:, 2]
+        self.triangles = tri
+
+    def prepare_scaling_rot(self, triangles=None, eps=1e-8):
+        if triangles is None:
+            triangles = self.triangles
+        if not self._hip_on_gpu(triangles):
+            return super().prepare_scaling_rot(triangles, eps)
+        opa = getattr(self, "_opacity", None)
+        fuse_opacity = self._hip_on_gpu(opa) and opa.numel() == triangles.shape[0]
+        out = points_to_gaussians(triangles, opa if fuse_opacity else None, eps, float(self.eps_s0))
+        xyz, scaling, rotation, scaling_act, rotation_unit = out[:5]
+        self._scaling = scaling
+        self._rotation = rotation
+        self.__dict__["_hip_activated"] = (scaling, rotation, scaling_act, rotation_unit)
+        self.__dict__["_hip_opacity"] = (opa, opa._version, out[5]) if fuse_opacity else None
+        self.__dict__["_hip_points_xyz"] = (triangles, xyz)
+
+    def _hip_points_centre(self, triangles):
+        """triangles[:, 0] as the points op returned it (differentiable through its node) when `triangles` is the tensor the last
+        prepare_scaling_rot() ran on, else the slice itself."""
+        cached = self.__dict__.get("_hip_points_xyz")
+        return cached[1] if cached is not None and cached[0] is triangles else triangles[:, 0]
+
+    @property
+    def get_scaling(self):
+        act = self.__dict__.get("_hip_activated")
+        if act is not None and act[0] is self._scaling:
+            return act[2]
+        s = self._scaling        # points_gaussian_model.py:107-109
+        s0 = torch.full((s.shape[0], 1), float(self.eps_s0), dtype=s.dtype, device=s.device)
+        return torch.cat([s0, torch.exp(s[:, [-2, -1]])], dim=1)
+
+
 class _StandaloneBase:
     def __init__(self, sh_degree: int = 3):
         self.active_sh_degree = 0
@@ -615,7 +675,37 @@ class HipGaussianFlameModel(HipFlameMixin, _StandaloneBase):
             self.prepare_scaling_rot()
 
 
+class HipPointsGaussianModel(HipPointsMixin, _StandaloneBase):
+    """gs_points (games/flat_splatting/scene/points_gaussian_model.py) on the points kernels: a trained gs_flat point cloud (two
+    `scale_*` columns), its pseudo-triangles (prepare_vertices) and per-frame Gaussians from deformed triangles (prepare_scaling_rot)."""
+
+    @classmethod
+    def from_tensors(cls, xyz, scaling, rotation, opacity, features_dc, features_rest, active_sh_degree=3, device="cuda"):
+        m = cls(3)
+        m.active_sh_degree = int(active_sh_degree)
+        t = lambda a: nn.Parameter(a.detach().to(device).float().contiguous())
+        m._xyz, m._scaling, m._rotation, m._opacity = t(xyz), t(scaling), t(rotation), t(opacity.reshape(-1, 1))
+        m._features_dc, m._features_rest = t(features_dc), t(features_rest)
+        return m
+
+    @classmethod
+    def from_free_scene(cls, scene, device="cuda"):
+        """A gs_flat-like synthetic scene (games_hip.synthetic.flat_scene: activated scales with the pinned 1e-8 first axis)."""
+        op = scene.opacities.clamp(1e-6, 1 - 1e-6)
+        return cls.from_tensors(scene.means3D, torch.log(scene.scales[:, 1:]), scene.rotations, torch.log(op / (1 - op)),
+                                scene.shs[:, :1], scene.shs[:, 1:], scene.sh_degree, device)
+
+    def load_ply(self, path, device="cuda"):
+        """point_cloud.ply of a gs_flat model (scene/gaussian_model.py:229-268 with two scale columns)."""
+        pc = self._load_point_cloud(path, device)
+        par = lambda a: nn.Parameter(a.requires_grad_(True))
+        self._xyz, self._scaling, self._rotation = par(pc["xyz"]), par(pc["scaling"]), par(pc["rotation"])
+        self._opacity, self._features_dc, self._features_rest = par(pc["opacity"]), par(pc["features_dc"]), par(pc["features_rest"])
+        self.active_sh_degree = self.max_sh_degree
+
+
 _MIXINS = {"gs_mesh": HipMeshMixin, "gs_multi_mesh": HipMultiMeshMixin, "gs_flame": HipFlameMixin}
+_POINTS_MIXINS = {"gs_points": HipPointsMixin}
 
 
 def install(games_module=None):
@@ -624,10 +714,22 @@ def install(games_module=None):
     class, dataset reader, optimizer groups and PLY I/O; only update_alpha / prepare_scaling_rot (+ the fused property
     getters) are overridden.  Call after `import games` in an environment that has the reference on sys.path.
     Returns {name: patched class}; `uninstall(games_module, returned)` restores the originals."""
+    return _install(games_module, _MIXINS)
+
+
+def install_points(games_module=None):
+    """The same for the pseudo-mesh workflow: `gs_points` (PointsGaussianModel) in both registries gets HipPointsMixin
+    (prepare_vertices / prepare_scaling_rot / the getters on the points kernels); the reference's renderer
+    renderer/gaussian_points_animated_renderer and scripts/render_points_time_animated.py run on it unchanged.  Kept apart from
+    `install()`, whose set stays the three mesh-bound models.  Returns {name: patched class} for `uninstall`."""
+    return _install(games_module, _POINTS_MIXINS)
+
+
+def _install(games_module, mixins):
     if games_module is None:
         import games as games_module  # type: ignore
     out = {}
-    for name, mixin in _MIXINS.items():
+    for name, mixin in mixins.items():
         base = games_module.gaussianModel[name]
         if issubclass(base, mixin):            # already installed
             out[name] = base

@@ -237,3 +237,54 @@ def render_animated(idxs, triangles, viewpoint_camera, pc, pipe, bg_color: torch
             return getattr(pc, name)
         get_xyz = xyz
     return render(viewpoint_camera, _View(), pipe, bg_color, scaling_modifier, override_color)
+
+
+def _points_frame_ok(pc, pipe, override_color) -> bool:
+    """Can this forward-only gs_points frame take the fused pseudo-triangles -> image path (GmsRasterForwardArgs.points)?  Nothing to
+    differentiate, the rasterizer's native SH / cov3D stages, split degree-3 SH storage (any active degree), and the model's cache of
+    the kernel sigmoid current (the unfused frame reads get_opacity: the kernel's sigmoid then, else torch.sigmoid, which this path
+    does not reproduce bit for bit).  `GMS_ANIMATE_FUSED=0` keeps the two-launch route, as for mesh frames."""
+    import os
+    import diff_gaussian_rasterization as dgr
+    if dgr._C is None or not hasattr(dgr._C, "render_points_forward") or os.environ.get("GMS_ANIMATE_FUSED", "1") == "0":
+        return False
+    if torch.is_grad_enabled() or override_color is not None or pipe.compute_cov3D_python or pipe.convert_SHs_python:
+        return False
+    fr, dc, op = getattr(pc, "_features_rest", None), getattr(pc, "_features_dc", None), getattr(pc, "_opacity", None)
+    if not (torch.is_tensor(fr) and fr.dim() == 3 and fr.shape[1] == 15 and fr.is_cuda and torch.is_tensor(dc) and torch.is_tensor(op)):
+        return False
+    cached = pc.__dict__.get("_hip_opacity") if hasattr(pc, "__dict__") else None
+    cache_ok = cached is not None and cached[0] is op and cached[1] == op._version
+    return 0 <= int(pc.active_sh_degree) <= 3 and cache_ok and dc.is_contiguous() and fr.is_contiguous()
+
+
+def render_points_frame(triangles: torch.Tensor, viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, eps=1e-8):
+    """One forward-only frame straight from pseudo-triangles [P,3,3]: the triangle -> Gaussian arithmetic runs inside the rasterizer's
+    preprocess thread (no points launch, no per-Gaussian tensors).  Same image, bit for bit, as the points op followed by the
+    rasterizer on its outputs; callers check `_points_frame_ok`.  As with `render_mesh_frame`, `pc._scaling` / `pc._rotation` keep the
+    values of the last prepare_scaling_rot() and `viewspace_points` is None."""
+    import diff_gaussian_rasterization as dgr
+    H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
+    color, radii, invdepth, visible = dgr._C.render_points_forward(
+        triangles, pc._opacity, pc._features_dc, pc._features_rest, bg_color, viewpoint_camera.world_view_transform,
+        viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W, math.tan(viewpoint_camera.FoVx * 0.5),
+        math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing), bool(pipe.debug), int(pc.active_sh_degree),
+        float(eps), float(getattr(pc, "eps_s0", 1e-8)))
+    return {"render": color, "viewspace_points": None, "visibility_filter": visible, "radii": radii, "depth": invdepth}
+
+
+def render_points_animated(triangles, viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None):
+    """renderer/gaussian_points_animated_renderer/__init__.py:21-115 with its signature and return dict: centres are `triangles[:, 0]`
+    (:61), scale / rotation come from `pc.prepare_scaling_rot(triangles)` (:66).  Forward-only frames the fused path supports go
+    pseudo-triangles -> image in the rasterizer's own launches (`render_points_frame`); everything else runs the model's
+    prepare_scaling_rot (the points op on a HipPointsMixin model, differentiable to the triangles) and then `render()`."""
+    if _points_frame_ok(pc, pipe, override_color):
+        return render_points_frame(triangles, viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
+    pc.prepare_scaling_rot(triangles)
+    centre = pc._hip_points_centre(triangles) if hasattr(pc, "_hip_points_centre") else triangles[:, 0]
+
+    class _View:       # same model, centres from the triangles (the reference passes them as means3D)
+        def __getattr__(self, name):
+            return getattr(pc, name)
+        get_xyz = centre
+    return render(viewpoint_camera, _View(), pipe, bg_color, scaling_modifier, override_color)

@@ -46,13 +46,15 @@
 extern "C" {
 #endif
 
-#define GMS_ABI_VERSION 8   /* 3: GmsRasterBackwardArgs gained factor_campos_row + sh_factor_mode (explicit mode flag), GMS_K_COUNT 17;
+#define GMS_ABI_VERSION 9   /* 3: GmsRasterBackwardArgs gained factor_campos_row + sh_factor_mode (explicit mode flag), GMS_K_COUNT 17;
                              4: GmsRasterForwardArgs gained no_host_wait (stream-capturable forward), gms_image_counts_offset;
                              5: GmsRasterForwardArgs.mesh (forward-only frame straight from a mesh);
                              6: GmsRasterForwardArgs.mesh_out_* (the fused frame exports what the backward needs: training frames too);
                              7: GmsRasterForwardArgs.count_ticket_out + gms_rasterize_forward_counts (the instance count is read back at the
                                 START OF THE BACKWARD instead of inside the forward);
-                             8: GmsRasterBackwardArgs.mesh + mesh_dL_* (the mesh backward inside preprocess_bwd for frames rendered from a mesh) */
+                             8: GmsRasterBackwardArgs.mesh + mesh_dL_* (the mesh backward inside preprocess_bwd for frames rendered from a mesh);
+                             9: GmsPointsArgs + gms_points_* (pseudo-triangle -> Gaussian), GmsRasterForwardArgs.points (forward-only frame
+                                straight from pseudo-triangles), GMS_K_POINTS_* / GMS_K_COUNT 20 */
 
 /* error codes (negative return values) */
 #define GMS_OK 0
@@ -68,6 +70,7 @@ extern "C" {
 typedef void *(*gms_alloc_fn)(void *ctx, size_t bytes);
 
 struct GmsMeshArgs;
+struct GmsPointsArgs;
 typedef struct GmsRasterForwardArgs {
     /* sizes */
     int32_t P;          /* number of Gaussians */
@@ -153,6 +156,13 @@ typedef struct GmsRasterForwardArgs {
      * frame in this form: its image is incomplete and its backward must not be trusted.  At most sixteen tickets of a forward thread may be
      * outstanding. */
     int64_t *count_ticket_out;      /* -> int64_t[2] */
+    /* Optional (ABI 9): a forward-only frame rendered straight from PSEUDO-TRIANGLES -- the gs_points render loops of
+     * scripts/render_points_time_animated.py / scripts/render_from_object.py, where every frame deforms the triangles and nothing is
+     * differentiated.  When non-NULL the preprocess thread derives its Gaussian from the Gaussian's own triangle (centre = first corner,
+     * activated scale, unit quaternion, sigmoid opacity: the arithmetic of gms_points_to_gaussians_forward, bit for bit) and `means3D`,
+     * `opacities`, `scales`, `rotations` are ignored (may be NULL).  Needs `mesh` NULL, points->P == P, points->_opacity, split degree-3
+     * SH STORAGE (shs + shs_rest, M = 16; the ACTIVE degree D is 0 .. 3) and no precomputed colours / covariances. */
+    const struct GmsPointsArgs *points;
 } GmsRasterForwardArgs;
 
 /* Returns the number of (Gaussian, tile) instances rendered (>= 0) or a negative error code. */
@@ -304,6 +314,35 @@ int32_t gms_mesh_to_gaussians_backward(const GmsMeshArgs *args, const float *dL_
                                        float *dL_dvertices, float *dL_dalpha, float *dL_dscale,
                                        float *dL_d_opacity /* or NULL */, void *stream);
 
+/* ---- pseudo-triangle <-> Gaussian (the gs_points pseudo-mesh workflow) ------------------
+ * Replaces PointsGaussianModel.prepare_scaling_rot + get_scaling / get_rotation / get_opacity and prepare_vertices
+ * (games/flat_splatting/scene/points_gaussian_model.py:28-109).  Every Gaussian owns one triangle [3,3]; nothing is shared. */
+typedef struct GmsPointsArgs {
+    int64_t P;                    /* Gaussians = triangles */
+    const float *triangles;       /* [P,3,3] (corner-major: triangles[p][k] is corner k) */
+    const float *_opacity;        /* [P] raw opacities or NULL: fuses get_opacity = sigmoid(_opacity) */
+    float eps;                    /* prepare_scaling_rot's eps (default 1e-8) */
+    float eps_s0;                 /* the constant first column of get_scaling (1e-8 in the reference) */
+} GmsPointsArgs;
+
+/* prepare_vertices: out_triangles [P,3,3] = (xyz, v2, v3) built from xyz [P,3], the LAST TWO columns of scaling_raw [P,scaling_cols]
+ * (scaling_cols 2 or 3; exp'd as get_scaling does) and rotation [P,4] (normalised as build_rotation does). */
+int32_t gms_points_prepare_vertices(int64_t P, const float *xyz, const float *scaling_raw, int32_t scaling_cols, const float *rotation,
+                                    float *out_triangles, void *stream);
+
+/* Outputs: xyz [P,3] = triangles[:, 0], scaling_raw [P,2] = log|[s2, s3]|, rotation_raw [P,4] (the quaternion rot_to_quat_batch
+ * returns); optional activated getters: scaling_activated [P,3] = [eps_s0, exp(scaling_raw)], rotation_unit [P,4] = normalize
+ * (rotation_raw), opacity_activated [P] = sigmoid(_opacity) (needs args->_opacity). */
+int32_t gms_points_to_gaussians_forward(const GmsPointsArgs *args, float *xyz, float *scaling_raw, float *rotation_raw,
+                                        float *scaling_activated /* or NULL */, float *rotation_unit /* or NULL */,
+                                        float *opacity_activated /* or NULL */, void *stream);
+
+/* Gradients w.r.t. the activated getters (xyz, scaling_activated, rotation_unit[, opacity_activated]) -> (triangles[, _opacity]).
+ * Every output is a plain store of the Gaussian's own entries (no atomics: bit-identical run to run). */
+int32_t gms_points_to_gaussians_backward(const GmsPointsArgs *args, const float *dL_dxyz, const float *dL_dscaling_activated,
+                                         const float *dL_drotation_unit, const float *dL_dopacity_activated /* or NULL */,
+                                         float *dL_dtriangles, float *dL_d_opacity /* or NULL */, void *stream);
+
 /* ---- exact 3-NN mean squared distance ---------------------------------
  * Replaces the un-vendored `simple_knn._C.distCUDA2(points)` (.gitmodules:1-3) called at
  * scene/gaussian_model.py:134 and games/flat_splatting/scene/flat_gaussian_model.py:47 to size the initial
@@ -376,7 +415,10 @@ int32_t gms_adam_step(const GmsAdamTensor *tensors /* HOST array */, int32_t cou
 #define GMS_K_ADAM 14
 #define GMS_K_SH_EXPAND 15
 #define GMS_K_MICRO_FILTER 16
-#define GMS_K_COUNT 17
+#define GMS_K_POINTS_FWD 17
+#define GMS_K_POINTS_BWD 18
+#define GMS_K_POINTS_VERTS 19
+#define GMS_K_COUNT 20
 void gms_profile_enable(int32_t on);
 void gms_profile_reset(void);
 int32_t gms_profile_read(int32_t kernel_id, double *total_ms, int64_t *launches);
