@@ -1417,20 +1417,56 @@ extern "C" size_t gms_image_counts_offset(int32_t w, int32_t h)
 }
 static thread_local int64_t t_last_launched_units = 0;
 // Launch-size hints learnt from earlier frames, per (host thread, device, stream, W, H, P)
-struct FrameState { int device; hipStream_t stream; int W, H, P; uint32_t deepest_seen, units_hint; };
+struct FrameKey { int device; hipStream_t stream; int W, H, P; };
+static bool operator==(const FrameKey &a, const FrameKey &b) { return a.device == b.device && a.stream == b.stream && a.W == b.W && a.H == b.H && a.P == b.P; }
+struct FrameState { FrameKey key; uint32_t deepest_seen, units_hint; };
 static thread_local std::vector<FrameState> t_frames;
-// what a redeemed ticket learnt about a frame (gms_rasterize_forward_counts, possibly on another host thread): picked up by the next forward
-// of the same (device, stream, W, H, P)
-struct HintMail { int device; hipStream_t stream; int W, H, P; uint32_t deepest, units; };
-static std::mutex g_mail_mu;
-static std::vector<HintMail> g_mail;
-static FrameState *frame_state(int device, hipStream_t stream, int W, int H, int P)
+static FrameState *frame_state(const FrameKey &key)
 {
-    for (auto &f : t_frames) if (f.device == device && f.stream == stream && f.W == W && f.H == H && f.P == P) return &f;
+    for (auto &f : t_frames) if (f.key == key) return &f;
     if (t_frames.size() >= 64) t_frames.erase(t_frames.begin());
-    t_frames.push_back({device, stream, W, H, P, 0u, 0u});
+    t_frames.push_back({key, 0u, 0u});
     return &t_frames.back();
 }
+// slowly decaying maximum of a frame's work-unit counts (views differ)
+static uint32_t decayed_units(uint32_t hint, uint32_t units) { return max(units, (uint32_t)(0.97 * hint)); }
+
+// What a redeemed ticket learnt about a frame (gms_rasterize_forward_counts, possibly on another host thread): picked up by the next
+// forward of the same key.  Tickets are redeemed on any thread, so this one table is shared and locked; FrameState stays thread-local.
+struct HintMail { FrameKey key; uint32_t deepest, units; };
+static std::mutex g_mail_mu;
+static std::vector<HintMail> g_mail;
+static void post_mail(const FrameKey &key, uint32_t deepest, uint32_t units)
+{
+    std::lock_guard<std::mutex> lk(g_mail_mu);
+    for (auto &m : g_mail)
+        if (m.key == key) { m.deepest = deepest; m.units = units; return; }
+    if (g_mail.size() >= 64) g_mail.erase(g_mail.begin());
+    g_mail.push_back({key, deepest, units});
+}
+static void take_mail(FrameState *fs)
+{
+    std::lock_guard<std::mutex> lk(g_mail_mu);
+    for (size_t k = 0; k < g_mail.size(); k++)
+        if (g_mail[k].key == fs->key) {
+            fs->deepest_seen = g_mail[k].deepest;
+            fs->units_hint = decayed_units(fs->units_hint, g_mail[k].units);
+            g_mail.erase(g_mail.begin() + (long)k);
+            return;
+        }
+}
+
+// Wait for the counts of call `seq` in `slot`, then learn from them for the next frame of this shape
+static int32_t take_counts(int32_t *slot, int32_t seq, hipStream_t stream, FrameState *fs, int64_t *N, uint32_t *units)
+{
+    const int32_t rc = wait_for_count(slot, seq, stream, N);
+    if (rc != GMS_OK) return rc;
+    fs->deepest_seen = t_last_deepest = deepest_tile(slot);
+    *units = unit_count(slot);
+    fs->units_hint = decayed_units(fs->units_hint, *units);
+    return GMS_OK;
+}
+
 extern "C" int64_t gms_last_launched_units(void) { return t_last_launched_units; }
 static thread_local int32_t t_last_used_micro = 0;
 extern "C" int32_t gms_last_used_micro(void) { return t_last_used_micro; }
@@ -1440,77 +1476,91 @@ extern "C" size_t gms_binning_bytes(int64_t n, int32_t w, int32_t h)
     return BinningState::bytes((size_t)(n > 0 ? n : 0), T, seg_len_min(), micro_mode());
 }
 
-extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *stream_)
+static bool aligned16(const void *p) { return (((uintptr_t)p) & 15u) == 0; }
+// SH rows the DMA / split instantiations can read (the fused inputs always qualify: validate_forward)
+static bool sh_fast_layout(const GmsRasterForwardArgs *A)
 {
-    gms::TraceRange trace_range("gms_rasterize_forward");
-    hipStream_t stream = (hipStream_t)stream_;
-    g_err[0] = 0;
+    return A->shs && A->M == 16 && aligned16(A->shs) && aligned16(A->shs_rest) &&
+           (A->mesh || A->points || A->cov3D_precomp || aligned16(A->rotations));
+}
+
+// Every argument check of gms_rasterize_forward, before anything is allocated or launched
+static int32_t validate_forward(const GmsRasterForwardArgs *A)
+{
     if (!A || A->P < 0 || A->width <= 0 || A->height <= 0 || !A->out_color || !A->out_invdepth || !A->background) {
         set_error("gms_rasterize_forward: invalid sizes or null output/background pointer");
         return GMS_ERR_INVALID_ARGUMENT;
     }
-    const int P = A->P, W = A->width, H = A->height;
-    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, T = gx * gy;
-    const GmsMeshArgs *mesh = A->mesh;          // forward-only frame straight from a mesh (gmsplat.h): K0 runs inside the preprocess thread
-    const GmsPointsArgs *points = A->points;    // ... or straight from pseudo-triangles (ABI 9)
-    if (mesh && points) {
-        set_error("gms_rasterize_forward: set at most one of mesh / points");
-        return GMS_ERR_INVALID_ARGUMENT;
-    }
-    if (P > 0 && points) {
-        const int32_t prc = check_points_args(points);
-        if (prc != GMS_OK) return prc;
-        if (points->P != (int64_t)P || !points->_opacity || !A->shs || !A->shs_rest || A->M != 16 || A->D < 0 || A->D > 3 || A->colors_precomp ||
-            A->cov3D_precomp || (((uintptr_t)A->shs) & 15u) || (((uintptr_t)A->shs_rest) & 15u)) {
-            set_error("gms_rasterize_forward: the fused points input needs a complete GmsPointsArgs (P equal, _opacity set), split degree-3 SH "
-                      "storage (shs + shs_rest, M = 16, active degree 0 .. 3, 16-byte aligned) and no precomputed colours / covariances");
+    const GmsMeshArgs *mesh = A->mesh;
+    const GmsPointsArgs *points = A->points;
+    if (mesh && points) { set_error("gms_rasterize_forward: set at most one of mesh / points"); return GMS_ERR_INVALID_ARGUMENT; }
+    if (A->P == 0) return GMS_OK;
+    const bool fused = mesh || points;
+    if (fused) {
+        // the thread of a Gaussian reads the mesh / triangles through the same tables as the standalone launches: same checks first
+        const int32_t rc = mesh ? check_mesh_args(mesh, false) : check_points_args(points);
+        if (rc != GMS_OK) return rc;
+        if (mesh) {
+            const int outs = (A->mesh_out_xyz != nullptr) + (A->mesh_out_scaling_act != nullptr) + (A->mesh_out_rotation_unit != nullptr) +
+                             (A->mesh_out_opacity_act != nullptr);
+            if (outs != 0 && (outs != 4 || !aligned16(A->mesh_out_rotation_unit))) {
+                set_error("gms_rasterize_forward: mesh_out_* must be all NULL (forward-only frame) or all set (rotation_unit 16-byte aligned)");
+                return GMS_ERR_INVALID_ARGUMENT;
+            }
+        }
+        const bool complete = mesh ? mesh->P == (int64_t)A->P && mesh->vertices && mesh->faces && mesh->_alpha && mesh->_scale && mesh->_opacity &&
+                                         (mesh->splats_per_face > 0 || mesh->splat_face)
+                                   : points->P == (int64_t)A->P && points->_opacity;
+        if (!complete || !A->shs || !A->shs_rest || A->M != 16 || A->D < 0 || A->D > 3 || A->colors_precomp || A->cov3D_precomp ||
+            !aligned16(A->shs) || !aligned16(A->shs_rest)) {
+            set_error("gms_rasterize_forward: the fused %s input needs a complete %s (P equal, _opacity set), split degree-3 SH "
+                      "storage (shs + shs_rest, M = 16, active degree 0 .. 3, 16-byte aligned) and no precomputed colours / covariances",
+                      mesh ? "mesh" : "points", mesh ? "GmsMeshArgs" : "GmsPointsArgs");
             return GMS_ERR_INVALID_ARGUMENT;
         }
-        if (!A->viewmatrix || !A->projmatrix || !A->campos || !A->radii || !A->geom_alloc || !A->binning_alloc || !A->image_alloc) {
-            set_error("gms_rasterize_forward: null input pointer or callback");
-            return GMS_ERR_INVALID_ARGUMENT;
-        }
-    } else if (P > 0 && mesh) {
-        // the thread of a Gaussian reads faces / vertices / _alpha through the same tables as the K0 launch: same checks
-        const int32_t mrc = check_mesh_args(mesh, false);
-        if (mrc != GMS_OK) return mrc;
-        const int outs = (A->mesh_out_xyz != nullptr) + (A->mesh_out_scaling_act != nullptr) + (A->mesh_out_rotation_unit != nullptr) + (A->mesh_out_opacity_act != nullptr);
-        if (outs != 0 && (outs != 4 || (((uintptr_t)A->mesh_out_rotation_unit) & 15u))) {
-            set_error("gms_rasterize_forward: mesh_out_* must be all NULL (forward-only frame) or all set (rotation_unit 16-byte aligned)");
-            return GMS_ERR_INVALID_ARGUMENT;
-        }
-        if (mesh->P != (int64_t)P || !mesh->vertices || !mesh->faces || !mesh->_alpha || !mesh->_scale || !mesh->_opacity ||
-            (mesh->splats_per_face <= 0 && !mesh->splat_face) || !A->shs || !A->shs_rest || A->M != 16 || A->D < 0 || A->D > 3 || A->colors_precomp ||
-            A->cov3D_precomp || (((uintptr_t)A->shs) & 15u) || (((uintptr_t)A->shs_rest) & 15u)) {
-            set_error("gms_rasterize_forward: the fused mesh input needs a complete GmsMeshArgs (P equal, _opacity set), split degree-3 SH "
-                      "storage (shs + shs_rest, M = 16, active degree 0 .. 3, 16-byte aligned) and no precomputed colours / covariances");
-            return GMS_ERR_INVALID_ARGUMENT;
-        }
-        if (!A->viewmatrix || !A->projmatrix || !A->campos || !A->radii || !A->geom_alloc || !A->binning_alloc || !A->image_alloc) {
-            set_error("gms_rasterize_forward: null input pointer or callback");
-            return GMS_ERR_INVALID_ARGUMENT;
-        }
-    } else if (P > 0) {
-        if ((A->shs == nullptr) == (A->colors_precomp == nullptr)) {
-            set_error("provide exactly one of shs / colors_precomp");
-            return GMS_ERR_INVALID_ARGUMENT;
-        }
+    } else {
+        if ((A->shs == nullptr) == (A->colors_precomp == nullptr)) { set_error("provide exactly one of shs / colors_precomp"); return GMS_ERR_INVALID_ARGUMENT; }
         const bool sr = A->scales && A->rotations;
         if (sr == (A->cov3D_precomp != nullptr) || (!sr && (A->scales || A->rotations))) {
             set_error("provide exactly one of (scales, rotations) / cov3D_precomp");
             return GMS_ERR_INVALID_ARGUMENT;
         }
-        if (!A->means3D || !A->opacities || !A->viewmatrix || !A->projmatrix || !A->campos || !A->radii ||
-            !A->geom_alloc || !A->binning_alloc || !A->image_alloc) {
-            set_error("gms_rasterize_forward: null input pointer or callback");
-            return GMS_ERR_INVALID_ARGUMENT;
-        }
-        if (A->shs && (A->D < 0 || A->D > 3 || (A->D + 1) * (A->D + 1) > A->M)) {
-            set_error("SH degree %d needs %d coefficients but M = %d (degrees 0..3 supported)", A->D,
-                      (A->D + 1) * (A->D + 1), A->M);
-            return GMS_ERR_INVALID_ARGUMENT;
-        }
     }
+    if ((!fused && (!A->means3D || !A->opacities)) || !A->viewmatrix || !A->projmatrix || !A->campos || !A->radii || !A->geom_alloc ||
+        !A->binning_alloc || !A->image_alloc) {
+        set_error("gms_rasterize_forward: null input pointer or callback");
+        return GMS_ERR_INVALID_ARGUMENT;
+    }
+    if (!fused && A->shs && (A->D < 0 || A->D > 3 || (A->D + 1) * (A->D + 1) > A->M)) {
+        set_error("SH degree %d needs %d coefficients but M = %d (degrees 0..3 supported)", A->D, (A->D + 1) * (A->D + 1), A->M);
+        return GMS_ERR_INVALID_ARGUMENT;
+    }
+    if (A->shs_rest && !sh_fast_layout(A)) { set_error("split SH storage (shs_rest) needs M == 16 and 16-byte aligned pointers"); return GMS_ERR_INVALID_ARGUMENT; }
+    if (A->no_host_wait && A->binning_capacity_hint <= 0) { set_error("no_host_wait needs a binning capacity hint (render the shape once without it first)"); return GMS_ERR_INVALID_ARGUMENT; }
+    return GMS_OK;
+}
+
+// The fused inputs hold split degree-3 storage (validate_forward): the active degree alone picks the preprocess instantiation
+template <typename Launch> static void dispatch_degree(int D, Launch &&launch)
+{
+    switch (D) {
+    case 0: launch(std::integral_constant<int, 0>()); break;
+    case 1: launch(std::integral_constant<int, 1>()); break;
+    case 2: launch(std::integral_constant<int, 2>()); break;
+    default: launch(std::integral_constant<int, 3>()); break;
+    }
+}
+
+extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *stream_)
+{
+    gms::TraceRange trace_range("gms_rasterize_forward");
+    hipStream_t stream = (hipStream_t)stream_;
+    g_err[0] = 0;
+    if (const int32_t rc = validate_forward(A)) return rc;
+    const int P = A->P, W = A->width, H = A->height;
+    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, T = gx * gy;
+    const GmsMeshArgs *mesh = A->mesh;          // forward-only frame straight from a mesh (gmsplat.h): K0 runs inside the preprocess thread
+    const GmsPointsArgs *points = A->points;    // ... or straight from pseudo-triangles
     const size_t HW = (size_t)W * H;
     if (P == 0) {   // nothing to draw: background image, no scratch
         fill_background_kernel<<<(unsigned)((HW + 255) / 256), 256, 0, stream>>>(W, H, A->background, A->out_color,
@@ -1547,86 +1597,57 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
     img.tile_count = ctr->buf;
     // Launch-size hints learnt from earlier frames, per (device, stream, W, H, P): two scenes of different size
     // interleaved on one thread (or one scene on two devices) do not disturb each other's hints
-    FrameState *fs = frame_state(device, stream, W, H, P);
-    {
-        std::lock_guard<std::mutex> lk(g_mail_mu);
-        for (size_t k = 0; k < g_mail.size(); k++) {
-            const HintMail &m = g_mail[k];
-            if (m.device == device && m.stream == stream && m.W == W && m.H == H && m.P == P) {
-                fs->deepest_seen = m.deepest;
-                fs->units_hint = max(m.units, (uint32_t)(0.97 * fs->units_hint));
-                g_mail.erase(g_mail.begin() + (long)k);
-                break;
-            }
-        }
-    }
-    uint32_t &deepest_seen = fs->deepest_seen;      // deepest tile of the previous frame of this shape
-    uint32_t &units_hint = fs->units_hint;          // slowly decaying maximum of its work-unit counts (views differ)
+    FrameState *fs = frame_state({device, stream, W, H, P});
+    take_mail(fs);
 
-    PreArgs pa{};          // (zero-initialised: `mesh` is only filled for the K0 instantiation)
+    PreArgs pa{};          // (zero-initialised: the fused inputs leave the tensor inputs NULL, only K0 fills `mesh` and k0_*)
     pa.P = P; pa.D = A->D; pa.M = A->M; pa.W = W; pa.H = H; pa.gx = gx; pa.gy = gy;
-    pa.means3D = A->means3D; pa.shs = A->shs; pa.shs_rest = A->shs_rest; pa.colors = A->colors_precomp; pa.opac = A->opacities;
-    pa.scales = A->scales; pa.rots = A->rotations; pa.cov3Dp = A->cov3D_precomp; pa.view = A->viewmatrix;
+    pa.shs = A->shs; pa.shs_rest = A->shs_rest; pa.colors = A->colors_precomp; pa.view = A->viewmatrix;
     pa.proj = A->projmatrix; pa.campos = A->campos; pa.mod = A->scale_modifier; pa.tanx = A->tan_fovx;
     pa.tany = A->tan_fovy; pa.aa = A->antialiasing; pa.radii = A->radii; pa.visible = A->visible; pa.geom = geom; pa.tile_count = img.tile_count;
-    if (mesh || points) {
-        pa.means3D = nullptr; pa.opac = nullptr; pa.scales = nullptr; pa.rots = nullptr; pa.cov3Dp = nullptr;
+    if (!mesh && !points) {
+        pa.means3D = A->means3D; pa.opac = A->opacities; pa.scales = A->scales; pa.rots = A->rotations; pa.cov3Dp = A->cov3D_precomp;
     }
     if (mesh) {
-        pa.mesh = *mesh; pa.means3D = nullptr; pa.opac = nullptr; pa.scales = nullptr; pa.rots = nullptr; pa.cov3Dp = nullptr;
+        pa.mesh = *mesh;
         pa.k0_xyz = A->mesh_out_xyz; pa.k0_scale = A->mesh_out_scaling_act; pa.k0_rot = A->mesh_out_rotation_unit; pa.k0_opac = A->mesh_out_opacity_act;
     }
+    const uint64_t hint = A->binning_capacity_hint > 0 ? (uint64_t)A->binning_capacity_hint : 0;
+    const uint32_t frame_L = seg_len_for_frame(hint, T);      // 0: the scan chooses from the depth
     // Inline tile scan (see emit_instances_kernel): on the capacity-hint path, when the segment length is known up front and the
     // tile table fits the emit blocks' LDS.  GMS_INLINE_SCAN=0 keeps the separate tile_scan launch.
     static int inline_env = -1;
     if (inline_env < 0) { const char *e = getenv("GMS_INLINE_SCAN"); inline_env = e ? (atoi(e) != 0) : 1; }
-    const uint32_t frame_L_pre = seg_len_for_frame((uint64_t)A->binning_capacity_hint, T);
     // (every emit block repeats the scan and holds the offsets in LDS, 29 KB per block instead of 12: it pays while the emit blocks
     // are one resident round -- headline scene: 2 354 -> 2 434 it/s -- and loses beyond, config-5 size: emit 117 -> 141 us)
-    const bool inline_scan = inline_env && A->binning_capacity_hint > 0 && frame_L_pre != 0 && T <= INLINE_SCAN_MAX_T &&
-                             (P + BLOCK - 1) / BLOCK <= 1536;
+    const bool inline_scan = inline_env && hint > 0 && frame_L != 0 && T <= INLINE_SCAN_MAX_T && (P + BLOCK - 1) / BLOCK <= 1536;
     pa.zero_cursor = inline_scan ? img.tile_cursor : nullptr; pa.T = T;
     pa.zero_cmax = micro_mode() ? img.tile_cmax : nullptr;
     const unsigned pblocks = (unsigned)((P + BLOCK - 1) / BLOCK);
-    const bool split = A->shs_rest != nullptr;
-    const bool sh_fast = A->shs && A->M == 16 && (((uintptr_t)A->shs) & 15u) == 0 && (((uintptr_t)A->shs_rest) & 15u) == 0 &&
-                         (mesh || points || A->cov3D_precomp || (((uintptr_t)A->rotations) & 15u) == 0);
-    if (split && !sh_fast) {
-        set_error("split SH storage (shs_rest) needs M == 16 and 16-byte aligned pointers");
-        return GMS_ERR_INVALID_ARGUMENT;
-    }
+    if (points) {
+        dispatch_degree(A->D, [&](auto d) { GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_points_kernel<d.value><<<pblocks, BLOCK, 0, stream>>>(pa, *points))); });
+    } else if (mesh) {
+        dispatch_degree(A->D, [&](auto d) { GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<true, d.value><<<pblocks, BLOCK, 0, stream>>>(pa))); });
+    } else {
+        const bool split = A->shs_rest != nullptr;
 #define GMS_PRE(DEG, SP) GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_kernel<DEG, SP><<<pblocks, BLOCK, 0, stream>>>(pa)))
-    if (points) {        // (validated above: split degree-3 storage; the active degree picks the instantiation)
-        switch (A->D) {
-        case 0: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_points_kernel<0><<<pblocks, BLOCK, 0, stream>>>(pa, *points))); break;
-        case 1: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_points_kernel<1><<<pblocks, BLOCK, 0, stream>>>(pa, *points))); break;
-        case 2: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_points_kernel<2><<<pblocks, BLOCK, 0, stream>>>(pa, *points))); break;
-        default: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_points_kernel<3><<<pblocks, BLOCK, 0, stream>>>(pa, *points))); break;
+        switch ((sh_fast_layout(A) ? A->D : -1) * 2 + (split ? 1 : 0)) {
+        case 0: GMS_PRE(0, false); break;
+        case 1: GMS_PRE(0, true); break;
+        case 2: GMS_PRE(1, false); break;
+        case 3: GMS_PRE(1, true); break;
+        case 4: GMS_PRE(2, false); break;
+        case 5: GMS_PRE(2, true); break;
+        case 6: GMS_PRE(3, false); break;
+        case 7: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<false><<<pblocks, BLOCK, 0, stream>>>(pa))); break;
+        default: GMS_PRE(-1, false); break;
         }
-    } else if (mesh) {   // (validated above: split degree-3 storage; the active degree picks the instantiation)
-        switch (A->D) {
-        case 0: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<true, 0><<<pblocks, BLOCK, 0, stream>>>(pa))); break;
-        case 1: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<true, 1><<<pblocks, BLOCK, 0, stream>>>(pa))); break;
-        case 2: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<true, 2><<<pblocks, BLOCK, 0, stream>>>(pa))); break;
-        default: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<true, 3><<<pblocks, BLOCK, 0, stream>>>(pa))); break;
-        }
-    } else
-    switch ((sh_fast ? A->D : -1) * 2 + (split ? 1 : 0)) {
-    case 0: GMS_PRE(0, false); break;
-    case 1: GMS_PRE(0, true); break;
-    case 2: GMS_PRE(1, false); break;
-    case 3: GMS_PRE(1, true); break;
-    case 4: GMS_PRE(2, false); break;
-    case 5: GMS_PRE(2, true); break;
-    case 6: GMS_PRE(3, false); break;
-    case 7: GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<false><<<pblocks, BLOCK, 0, stream>>>(pa))); break;
-    default: GMS_PRE(-1, false); break;
-    }
 #undef GMS_PRE
+    }
     GMS_KERNEL_CHECK(A->debug, stream, "preprocess_fwd");
     const uint32_t L = seg_len_min();         // sizes and carving; the frame's own L is chosen by the scan (scan_out[3])
     // deferred read-back (gmsplat.h, count_ticket_out): this frame's counts go to the next slot of the thread's ring and nobody waits here
-    const bool defer = A->count_ticket_out != nullptr && A->binning_capacity_hint > 0 && !A->no_host_wait;
+    const bool defer = A->count_ticket_out != nullptr && hint > 0 && !A->no_host_wait;
     static thread_local uint32_t defer_counter = 0;
     const int slot_index = defer ? 1 + (int)(defer_counter++ % (uint32_t)DEFER_SLOTS) : 0;
     int32_t *slot = pinned_slot(slot_index);
@@ -1637,10 +1658,9 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
     // merge-path passes for tiles deeper than SORT_BIG_CHUNK keys: as many as the deepest tile of the previous frame
     // (+25 %) needs; a deeper tile than that falls back to the one-block sort and raises the count for the next frame
     int sort_np = 0;
-    if (deepest_seen > (uint32_t)SORT_BIG_CHUNK) sort_np = sort_passes((uint64_t)deepest_seen + deepest_seen / 4);
+    if (fs->deepest_seen > (uint32_t)SORT_BIG_CHUNK) sort_np = sort_passes((uint64_t)fs->deepest_seen + fs->deepest_seen / 4);
     static thread_local int32_t seq_counter = 0;
     const int32_t seq = (seq_counter = seq_counter == 0x7fffffff ? 1 : seq_counter + 1);
-    const uint32_t frame_L = seg_len_for_frame((uint64_t)A->binning_capacity_hint, T);      // 0: the scan chooses from the depth
     if (!inline_scan) {
         GMS_LAUNCH(GMS_K_TILE_SCAN, stream, tile_scan_kernel<<<1, SCAN_THREADS, 0, stream>>>(img.tile_count, img.tile_offset, img.tile_cursor,
                                                                                        img.unit_first, img.mseg_first, img.class_first, T, frame_L,
@@ -1657,13 +1677,12 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
     // Blend launches are sized from the previous frame's unit count (+25 %) instead of the table's capacity (thousands of
     // blocks that only find out they have nothing to do); a frame with more units than launched is re-run like a
     // capacity overflow.
-    uint32_t units_seen = 0;                          // this frame's count once known
     uint32_t launched_units = 0;
     auto enqueue_tail = [&](void *bin_mem, uint64_t capacity, bool exact_fit) -> int32_t {
         BinningState bin = BinningState::carve(bin_mem, (size_t)capacity, (size_t)T, L);
         const uint32_t mu = (uint32_t)BinningState::n_units((size_t)capacity, (size_t)T, L);
         uint32_t mu_launch = mu;
-        if (!exact_fit && units_hint > 0) mu_launch = min(mu, units_hint + units_hint / 4u + 64u);
+        if (!exact_fit && fs->units_hint > 0) mu_launch = min(mu, fs->units_hint + fs->units_hint / 4u + 64u);
         launched_units = blend_grid_units(mu_launch);
         FillUnitsArgs fu;
         fu.class_first = img.class_first; fu.offset = img.tile_offset; fu.mseg_first = img.mseg_first;
@@ -1717,69 +1736,57 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
         return launch_blend_forward(g, bo, mu_launch, A->debug != 0, stream);
     };
 
+    auto alloc_binning = [&](uint64_t capacity) -> void * {
+        void *mem = A->binning_alloc(A->binning_ctx, BinningState::bytes((size_t)capacity, (size_t)T, L, micro_mode()));
+        if (!mem) set_error("binning allocation callback returned NULL");
+        return mem;
+    };
+    if (A->no_host_wait || defer) {
+        // Launches only.  no_host_wait is the capturable form (gmsplat.h): the counts stay on the device (img.scan_out) and overflow
+        // is the caller's to detect.  A deferred frame's device also stores them into the ring slot; the caller redeems the ticket
+        // before its backward.
+        void *bin_mem = alloc_binning(hint);
+        if (!bin_mem) return GMS_ERR_ALLOC;
+        const int32_t rc = enqueue_tail(bin_mem, hint, false);
+        if (rc != GMS_OK) return rc;
+        t_last_launched_units = (int64_t)launched_units;
+        if (defer) {
+            A->count_ticket_out[0] = (int64_t)(uintptr_t)slot;          // (pinned, process-wide: any thread may poll it)
+            A->count_ticket_out[1] = (int64_t)seq;
+        }
+        if (A->num_units_out) *A->num_units_out = 0;
+        return (int64_t)hint;
+    }
     int64_t N;
-    if (A->no_host_wait) {
-        // capturable form (gmsplat.h): launches only.  The counts stay on the device (img.scan_out); overflow is the caller's to detect.
-        if (A->binning_capacity_hint <= 0) { set_error("no_host_wait needs a binning capacity hint (render the shape once without it first)"); return GMS_ERR_INVALID_ARGUMENT; }
-        const uint64_t cap = (uint64_t)A->binning_capacity_hint;
-        void *bin_mem = A->binning_alloc(A->binning_ctx, BinningState::bytes((size_t)cap, (size_t)T, L, micro_mode()));
-        if (!bin_mem) { set_error("binning allocation callback returned NULL"); return GMS_ERR_ALLOC; }
-        const int32_t rc = enqueue_tail(bin_mem, cap, false);
-        if (rc != GMS_OK) return rc;
-        t_last_launched_units = (int64_t)launched_units;
-        if (A->num_units_out) *A->num_units_out = 0;
-        return (int64_t)cap;
-    }
-    if (defer) {
-        // launches + the device's store of the counts into the ring slot; the caller redeems the ticket before its backward
-        const uint64_t cap = (uint64_t)A->binning_capacity_hint;
-        void *bin_mem = A->binning_alloc(A->binning_ctx, BinningState::bytes((size_t)cap, (size_t)T, L, micro_mode()));
-        if (!bin_mem) { set_error("binning allocation callback returned NULL"); return GMS_ERR_ALLOC; }
-        const int32_t rc = enqueue_tail(bin_mem, cap, false);
-        if (rc != GMS_OK) return rc;
-        t_last_launched_units = (int64_t)launched_units;
-        A->count_ticket_out[0] = (int64_t)(uintptr_t)slot;          // (pinned, process-wide: any thread may poll it)
-        A->count_ticket_out[1] = (int64_t)seq;
-        if (A->num_units_out) *A->num_units_out = 0;
-        return (int64_t)cap;
-    }
-    if (A->binning_capacity_hint > 0) {
+    uint32_t units_seen = 0;
+    if (hint > 0) {
         // optimistic path: enqueue the whole tail before looking at N (no pipeline bubble)
-        const uint64_t cap = (uint64_t)A->binning_capacity_hint;
-        void *bin_mem = A->binning_alloc(A->binning_ctx, BinningState::bytes((size_t)cap, (size_t)T, L, micro_mode()));
-        if (!bin_mem) { set_error("binning allocation callback returned NULL"); return GMS_ERR_ALLOC; }
-        int32_t rc = enqueue_tail(bin_mem, cap, false);
+        void *bin_mem = alloc_binning(hint);
+        if (!bin_mem) return GMS_ERR_ALLOC;
+        int32_t rc = enqueue_tail(bin_mem, hint, false);
         if (rc != GMS_OK) return rc;
         t_last_launched_units = (int64_t)launched_units;
-        rc = wait_for_count(slot, seq, stream, &N);
+        rc = take_counts(slot, seq, stream, fs, &N, &units_seen);
         if (rc != GMS_OK) return rc;
-        deepest_seen = deepest_tile(slot);
-        t_last_deepest = deepest_seen;
-        units_seen = unit_count(slot);
-        units_hint = max(units_seen, (uint32_t)(0.97 * units_hint));
-        if ((uint64_t)N <= cap && units_seen > launched_units) {       // enough memory, too few blocks: same buffers, full-size launches
+        if ((uint64_t)N <= hint && units_seen > launched_units) {       // enough memory, too few blocks: same buffers, full-size launches
             GMS_HIP_CHECK(hipMemsetAsync(img.tile_cursor, 0, (size_t)T * 4, stream));
-            rc = enqueue_tail(bin_mem, cap, true);
+            rc = enqueue_tail(bin_mem, hint, true);
             if (rc != GMS_OK) return rc;
         }
-        if ((uint64_t)N > cap) {                         // rare: re-run the tail at the right size
-            bin_mem = A->binning_alloc(A->binning_ctx, BinningState::bytes((size_t)N, (size_t)T, L, micro_mode()));
-            if (!bin_mem) { set_error("binning allocation callback returned NULL"); return GMS_ERR_ALLOC; }
+        if ((uint64_t)N > hint) {                         // rare: re-run the tail at the right size
+            bin_mem = alloc_binning((uint64_t)N);
+            if (!bin_mem) return GMS_ERR_ALLOC;
             GMS_HIP_CHECK(hipMemsetAsync(img.tile_cursor, 0, (size_t)T * 4, stream));
             rc = enqueue_tail(bin_mem, (uint64_t)N, true);
             if (rc != GMS_OK) return rc;
         }
     } else {
-        int32_t rc0 = wait_for_count(slot, seq, stream, &N);
-        if (rc0 != GMS_OK) return rc0;
-        deepest_seen = deepest_tile(slot);
-        t_last_deepest = deepest_seen;
-        units_seen = unit_count(slot);
-        units_hint = max(units_seen, (uint32_t)(0.97 * units_hint));
+        int32_t rc = take_counts(slot, seq, stream, fs, &N, &units_seen);
+        if (rc != GMS_OK) return rc;
         const uint64_t cap = (uint64_t)(N > 0 ? N : 1);
-        void *bin_mem = A->binning_alloc(A->binning_ctx, BinningState::bytes((size_t)cap, (size_t)T, L, micro_mode()));
-        if (!bin_mem) { set_error("binning allocation callback returned NULL"); return GMS_ERR_ALLOC; }
-        int32_t rc = enqueue_tail(bin_mem, cap, true);         // N is exact here, so the table-sized launch is tight
+        void *bin_mem = alloc_binning(cap);
+        if (!bin_mem) return GMS_ERR_ALLOC;
+        rc = enqueue_tail(bin_mem, cap, true);         // N is exact here, so the table-sized launch is tight
         if (rc != GMS_OK) return rc;
     }
     if (A->num_units_out) *A->num_units_out = (int64_t)units_seen;
@@ -1810,16 +1817,7 @@ extern "C" int64_t gms_rasterize_forward_counts(const int64_t *ticket, int32_t w
     const uint32_t units = unit_count(slot), deepest = deepest_tile(slot);
     int device = 0;
     GMS_HIP_CHECK(hipGetDevice(&device));
-    {
-        std::lock_guard<std::mutex> lk(g_mail_mu);
-        bool found = false;
-        for (auto &m : g_mail)
-            if (m.device == device && m.stream == stream && m.W == width && m.H == height && m.P == P) { m.deepest = deepest; m.units = units; found = true; }
-        if (!found) {
-            if (g_mail.size() >= 64) g_mail.erase(g_mail.begin());
-            g_mail.push_back({device, stream, width, height, P, deepest, units});
-        }
-    }
+    post_mail({device, stream, width, height, P}, deepest, units);
     t_last_deepest = deepest;
     if (num_units_out) *num_units_out = (int64_t)units;
     if (deepest_tile_out) *deepest_tile_out = (int64_t)deepest;

@@ -21,6 +21,7 @@
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <optional>
 #include <tuple>
 #include <vector>
 
@@ -32,7 +33,8 @@ using torch::Tensor;
 using torch::autograd::AutogradContext;
 using torch::autograd::variable_list;
 
-inline void *stream_of(const Tensor &t) { return (void *)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(t.device().index()).stream(); }
+inline void *stream_of(c10::Device d) { return (void *)c10::hip::getCurrentHIPStreamMasqueradingAsCUDA(d.index()).stream(); }
+inline void *stream_of(const Tensor &t) { return stream_of(t.device()); }
 inline const float *cf(const Tensor &t) { return (t.defined() && t.numel()) ? t.data_ptr<float>() : nullptr; }
 inline float *mf(const Tensor &t) { return (t.defined() && t.numel()) ? t.data_ptr<float>() : nullptr; }
 
@@ -120,36 +122,43 @@ void set_fused_mesh_backward(bool on) { g_fused_mesh_bwd.store(on ? 1 : 0); }
 // what a frame rendered straight from a mesh stores for its backward (GmsRasterForwardArgs.mesh_out_*, ABI 6)
 struct MeshOut { Tensor xyz, scaling_act, rotation_unit, opacity_act; };
 
-Forward forward_core(const Tensor &bg_, const Tensor &means3D_, const Tensor &sh_, const Tensor &sh_rest_, const Tensor &colors_,
-                     const Tensor &opac_, const Tensor &scales_, const Tensor &rots_, const Tensor &cov_, const Tensor &view_,
-                     const Tensor &proj_, const Tensor &campos_, int64_t H, int64_t W, double tanx, double tany, double mod, int64_t D,
-                     bool prefiltered, bool aa, bool debug, const Tensor &visible, bool use_hint, const GmsMeshArgs *mesh = nullptr,
-                     const MeshOut *mesh_out = nullptr, bool may_defer = false, const GmsPointsArgs *points = nullptr)
+// Camera, image size and flags of one frame; the tensors are on the frame's device as contiguous float32
+struct FrameSettings { Tensor bg, view, proj, campos; int64_t H, W; double tanx, tany, mod; int64_t D; bool prefiltered, aa, debug; };
+FrameSettings frame_settings(c10::Device dev, const Tensor &bg, const Tensor &view, const Tensor &proj, const Tensor &campos, int64_t H,
+                             int64_t W, double tanx, double tany, double mod, int64_t D, bool prefiltered, bool aa, bool debug)
 {
-    // (`mesh`: the forward-only frame straight from a mesh, gmsplat.h; `means3D_` then only carries the device and P -- the SH DC tensor)
-    require_gpu(means3D_); require_gpu(bg_); require_gpu(view_); require_gpu(proj_); require_gpu(campos_);
-    // (`points`: the same, straight from pseudo-triangles, ABI 9)
-    TORCH_CHECK(mesh || points || (means3D_.dim() == 2 && means3D_.size(1) == 3), "means3D must have dimensions (num_points, 3)");
-    const auto dev = means3D_.device();
+    require_gpu(bg); require_gpu(view); require_gpu(proj); require_gpu(campos);
+    return {f32c(bg.to(dev)), f32c(view.to(dev)), f32c(proj.to(dev)), f32c(campos.to(dev)), H, W, tanx, tany, mod, D, prefiltered, aa, debug};
+}
+// Per-Gaussian inputs as contiguous float32.  A frame straight from a mesh or pseudo-triangles passes only the SH tensors.
+struct Gaussians { Tensor sh, sh_rest, means3D, colors, opac, scales, rots, cov; };
+Gaussians tensor_gaussians(const Tensor &means3D, const Tensor &sh, const Tensor &sh_rest, const Tensor &colors, const Tensor &opac,
+                           const Tensor &scales, const Tensor &rots, const Tensor &cov)
+{
+    require_gpu(means3D);
+    TORCH_CHECK(means3D.dim() == 2 && means3D.size(1) == 3, "means3D must have dimensions (num_points, 3)");
+    return {f32c(sh), f32c(sh_rest), f32c(means3D), f32c(colors), f32c(opac), f32c(scales), f32c(rots), f32c(cov)};
+}
+
+// `mesh` / `points`: the forward-only frame straight from a mesh or pseudo-triangles (gmsplat.h); `g` then holds only the SH tensors
+Forward forward_core(const FrameSettings &s, int64_t P, c10::Device dev, const Gaussians &g, const Tensor &visible, bool use_hint,
+                     const GmsMeshArgs *mesh = nullptr, const MeshOut *mesh_out = nullptr, bool may_defer = false, const GmsPointsArgs *points = nullptr)
+{
     c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
-    const int64_t P = means3D_.size(0);
-    Tensor means3D = f32c(means3D_), sh = f32c(sh_), sh_rest = f32c(sh_rest_), colors = f32c(colors_), opac = f32c(opac_);
-    Tensor scales = f32c(scales_), rots = f32c(rots_), cov = f32c(cov_);
-    Tensor bg = f32c(bg_.to(dev)), view = f32c(view_.to(dev)), proj = f32c(proj_.to(dev)), campos = f32c(campos_.to(dev));
-    const bool has_sh = sh.defined() && sh.numel() > 0;
-    if (has_sh) TORCH_CHECK(sh.dim() == 3 && sh.size(0) == P && sh.size(2) == 3, "sh must have dimensions (num_points, num_coeffs, 3)");
-    int64_t M = has_sh ? sh.size(1) : 0;
-    const bool split = sh_rest.defined() && sh_rest.numel() > 0;
-    if (split) M = sh.size(1) + sh_rest.size(1);
+    const bool has_sh = g.sh.defined() && g.sh.numel() > 0;
+    if (has_sh) TORCH_CHECK(g.sh.dim() == 3 && g.sh.size(0) == P && g.sh.size(2) == 3, "sh must have dimensions (num_points, num_coeffs, 3)");
+    int64_t M = has_sh ? g.sh.size(1) : 0;
+    const bool split = g.sh_rest.defined() && g.sh_rest.numel() > 0;
+    if (split) M = g.sh.size(1) + g.sh_rest.size(1);
 
     auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
     Forward f;
-    f.color = torch::empty({3, H, W}, fopt);
-    f.invdepth = torch::empty({1, H, W}, fopt);
+    f.color = torch::empty({3, s.H, s.W}, fopt);
+    f.invdepth = torch::empty({1, s.H, s.W}, fopt);
     f.radii = torch::empty({P}, fopt.dtype(torch::kInt));
 
     int64_t hint = 0;
-    const auto key = std::make_tuple((int)dev.index(), (int)W, (int)H, P);
+    const auto key = std::make_tuple((int)dev.index(), (int)s.W, (int)s.H, P);
     // deterministic mode (gmsplat.h): no capacity hint -- the segment length and the choice of compositing kernels then depend on the
     // frame alone (the exact instance count), not on what earlier frames of this shape looked like: run 1 == run 2 bit for bit
     if (use_hint && !gms_get_deterministic()) {
@@ -159,20 +168,21 @@ Forward forward_core(const Tensor &bg_, const Tensor &means3D_, const Tensor &sh
     }
     // Stream capture (torch.cuda.graph): the forward must not touch the host.  gms_rasterize_forward is then asked for its
     // launches-only form; the frame's counts stay on the device (games_hip.animate.GraphedAnimation reads them after a replay).
+    void *stream = stream_of(dev);
     hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
-    const bool capturing = hipStreamIsCapturing((hipStream_t)stream_of(means3D_), &cap_status) == hipSuccess && cap_status != hipStreamCaptureStatusNone;
+    const bool capturing = hipStreamIsCapturing((hipStream_t)stream, &cap_status) == hipSuccess && cap_status != hipStreamCaptureStatusNone;
     if (capturing)
         TORCH_CHECK(hint > 0 && P > 0, "rasterizing inside a stream capture needs the capacity hint of this shape: render it at least once on the "
                                         "same stream before the capture (not in deterministic mode)");
     Slot geom{Tensor(), dev, false}, binning{Tensor(), dev, false}, image{Tensor(), dev, false};
     int64_t num_units = 0;
     GmsRasterForwardArgs a{};
-    a.P = (int32_t)P; a.D = (int32_t)D; a.M = (int32_t)M; a.width = (int32_t)W; a.height = (int32_t)H;
-    a.background = cf(bg); a.means3D = cf(means3D); a.shs = cf(sh); a.shs_rest = split ? cf(sh_rest) : nullptr;
-    a.colors_precomp = cf(colors); a.opacities = cf(opac); a.scales = cf(scales); a.rotations = cf(rots);
-    a.cov3D_precomp = cf(cov); a.viewmatrix = cf(view); a.projmatrix = cf(proj); a.campos = cf(campos);
-    a.scale_modifier = (float)mod; a.tan_fovx = (float)tanx; a.tan_fovy = (float)tany;
-    a.prefiltered = prefiltered; a.antialiasing = aa; a.debug = debug;
+    a.P = (int32_t)P; a.D = (int32_t)s.D; a.M = (int32_t)M; a.width = (int32_t)s.W; a.height = (int32_t)s.H;
+    a.background = cf(s.bg); a.means3D = cf(g.means3D); a.shs = cf(g.sh); a.shs_rest = split ? cf(g.sh_rest) : nullptr;
+    a.colors_precomp = cf(g.colors); a.opacities = cf(g.opac); a.scales = cf(g.scales); a.rotations = cf(g.rots);
+    a.cov3D_precomp = cf(g.cov); a.viewmatrix = cf(s.view); a.projmatrix = cf(s.proj); a.campos = cf(s.campos);
+    a.scale_modifier = (float)s.mod; a.tan_fovx = (float)s.tanx; a.tan_fovy = (float)s.tany;
+    a.prefiltered = s.prefiltered; a.antialiasing = s.aa; a.debug = s.debug;
     a.out_color = mf(f.color); a.out_invdepth = mf(f.invdepth); a.radii = P ? f.radii.data_ptr<int32_t>() : nullptr;
     a.geom_alloc = alloc_cb; a.geom_ctx = &geom; a.binning_alloc = alloc_cb; a.binning_ctx = &binning;
     a.image_alloc = alloc_cb; a.image_ctx = &image;
@@ -182,7 +192,6 @@ Forward forward_core(const Tensor &bg_, const Tensor &means3D_, const Tensor &sh
     a.no_host_wait = capturing ? 1 : 0;
     a.mesh = mesh;
     a.points = points;
-    if (mesh || points) { a.means3D = nullptr; a.opacities = nullptr; a.scales = nullptr; a.rotations = nullptr; }
     if (mesh && mesh_out) {
         a.mesh_out_xyz = mf(mesh_out->xyz); a.mesh_out_scaling_act = mf(mesh_out->scaling_act);
         a.mesh_out_rotation_unit = mf(mesh_out->rotation_unit); a.mesh_out_opacity_act = mf(mesh_out->opacity_act);
@@ -190,7 +199,7 @@ Forward forward_core(const Tensor &bg_, const Tensor &means3D_, const Tensor &sh
     int64_t ticket[2] = {0, 0};
     const bool defer = may_defer && hint > 0 && !capturing && P > 0 && deferred_counts();
     if (defer) a.count_ticket_out = ticket;
-    const int64_t n = gms_rasterize_forward(&a, stream_of(means3D));
+    const int64_t n = gms_rasterize_forward(&a, stream);
     TORCH_CHECK(!(geom.failed || binning.failed || image.failed), "scratch allocation failed (out of device memory?)");
     check_rc(n, "gms_rasterize_forward");
     f.num_rendered = n; f.num_units = num_units;
@@ -201,30 +210,10 @@ Forward forward_core(const Tensor &bg_, const Tensor &means3D_, const Tensor &sh
         std::lock_guard<std::mutex> lk(g_mu);
         int64_t &c = g_capacity[key];
         if (!capturing && !defer) c = std::max(n, (int64_t)(0.97 * (double)c));      // (a captured / deferred call returns the capacity, not a count)
-        g_last.num_rendered = n; g_last.num_units = num_units; g_last.hint = hint; g_last.P = P; g_last.W = (int)W; g_last.H = (int)H;
+        g_last.num_rendered = n; g_last.num_units = num_units; g_last.hint = hint; g_last.P = P; g_last.W = (int)s.W; g_last.H = (int)s.H;
         if (g_keep_buffers.load()) { g_last.radii = f.radii; g_last.image = f.image; g_last.binning = f.binning; g_last.geom = f.geom; }
     }
     return f;
-}
-
-// Start of a backward whose forward deferred its counts: wait for them (they arrived long ago on a GPU-bound loop), check that the frame
-// fitted what it was launched for, feed the capacity hint.  Returns {instances, work units}.
-std::pair<int64_t, int64_t> redeem_counts(const int64_t *ticket, int64_t capacity, int64_t launched_units, const Tensor &like, int64_t W, int64_t H, int64_t P)
-{
-    int64_t units = 0, deepest = 0;
-    const int64_t n = gms_rasterize_forward_counts(ticket, (int32_t)W, (int32_t)H, (int32_t)P, &units, &deepest, stream_of(like));
-    check_rc(n, "gms_rasterize_forward_counts");
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        int64_t &c = g_capacity[std::make_tuple((int)like.device().index(), (int)W, (int)H, P)];
-        c = std::max(n, (int64_t)(0.97 * (double)c));
-        g_last.num_rendered = n; g_last.num_units = units;
-    }
-    TORCH_CHECK(n <= capacity && units <= launched_units,
-                "GMS_DEFERRED_OVERFLOW: the frame held ", n, " instances / ", units, " work units but was launched for ", capacity, " / ", launched_units,
-                " (deferred read-back of the instance count: diff_gaussian_rasterization.set_deferred_counts): its image is incomplete -- "
-                "redo this step (the capacity hint has been raised; or render it with set_deferred_counts(False))");
-    return {n, units};
 }
 
 struct Backward { Tensor dmeans2D, dcolors, dopacity, dmeans3D, dcov3D, dsh, dsh_rest, dscales, drots; };
@@ -243,44 +232,39 @@ static std::atomic<bool> g_sh_factor{false};
 static std::map<int, std::vector<Tensor>> g_factors;
 constexpr size_t MAX_QUEUED_FACTORS = 256;
 
-Backward alloc_backward(const Tensor &means3D, const Tensor &opac, const Tensor &sh, const Tensor &sh_rest, const Tensor &cov)
+Backward alloc_backward(const Gaussians &g)
 {
-    const int64_t P = means3D.size(0);
-    auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(means3D.device());
-    const bool has_sh = sh.defined() && sh.numel() > 0, split = sh_rest.defined() && sh_rest.numel() > 0;
-    const bool has_cov = cov.defined() && cov.numel() > 0;
+    const int64_t P = g.means3D.size(0);
+    auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(g.means3D.device());
+    const bool has_sh = g.sh.defined() && g.sh.numel() > 0, split = g.sh_rest.defined() && g.sh_rest.numel() > 0;
+    const bool has_cov = g.cov.defined() && g.cov.numel() > 0;
     Backward b;
     b.dmeans2D = torch::empty({P, 3}, fopt);
-    b.dopacity = torch::empty(opac.sizes(), fopt);
+    b.dopacity = torch::empty(g.opac.sizes(), fopt);
     b.dmeans3D = torch::empty({P, 3}, fopt);
     const bool factor = has_sh && g_sh_factor.load();
     if (!has_sh) b.dcolors = torch::empty({P, 3}, fopt);
     if (factor) b.dcolors = torch::empty({P + 1, 3}, fopt);
-    if (has_sh && !factor) b.dsh = torch::empty(sh.sizes(), fopt);
-    if (split && !factor) b.dsh_rest = torch::empty(sh_rest.sizes(), fopt);
+    if (has_sh && !factor) b.dsh = torch::empty(g.sh.sizes(), fopt);
+    if (split && !factor) b.dsh_rest = torch::empty(g.sh_rest.sizes(), fopt);
     if (has_cov) b.dcov3D = torch::empty({P, 6}, fopt);
     else { b.dscales = torch::empty({P, 3}, fopt); b.drots = torch::empty({P, 4}, fopt); }
     return b;
 }
 
-Backward backward_core(const Tensor &bg, const Tensor &means3D, const Tensor &radii, const Tensor &colors, const Tensor &opac,
-                       const Tensor &scales, const Tensor &rots, double mod, const Tensor &cov, const Tensor &view, const Tensor &proj,
-                       double tanx, double tany, const Tensor &dL_dcolor_, const Tensor &dL_dinvd_, const Tensor &sh, const Tensor &sh_rest,
-                       int64_t D, const Tensor &campos, const Tensor &geom, int64_t R, int64_t capacity, int64_t num_units,
-                       const Tensor &binning, const Tensor &image, bool aa, bool debug, const Backward *prealloc = nullptr,
-                       const GmsMeshArgs *mesh = nullptr, const MeshGrads *mesh_grads = nullptr)
+// `f`: the forward's radii, scratch tensors and counts
+Backward backward_core(const FrameSettings &s, const Gaussians &g, const Forward &f, const Tensor &dL_dcolor_, const Tensor &dL_dinvd_,
+                       const Backward *prealloc = nullptr, const GmsMeshArgs *mesh = nullptr, const MeshGrads *mesh_grads = nullptr)
 {
-    const auto dev = means3D.device();
+    const auto dev = g.means3D.device();
     c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
-    const int64_t P = means3D.size(0);
-    const bool has_sh = sh.defined() && sh.numel() > 0, split = sh_rest.defined() && sh_rest.numel() > 0;
-    const bool has_cov = cov.defined() && cov.numel() > 0;
-    int64_t M = has_sh ? sh.size(1) : 0;
-    if (split) M = sh.size(1) + sh_rest.size(1);
-    const int64_t H = dL_dcolor_.defined() ? dL_dcolor_.size(-2) : 0, W = dL_dcolor_.defined() ? dL_dcolor_.size(-1) : 0;
+    const int64_t P = g.means3D.size(0);
+    const bool has_sh = g.sh.defined() && g.sh.numel() > 0, split = g.sh_rest.defined() && g.sh_rest.numel() > 0;
+    int64_t M = has_sh ? g.sh.size(1) : 0;
+    if (split) M = g.sh.size(1) + g.sh_rest.size(1);
     auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
     Tensor gcol = f32c(dL_dcolor_), ginv = f32c(dL_dinvd_);
-    void *stream = stream_of(means3D);
+    void *stream = stream_of(dev);
     Tensor accum;
     const auto akey = std::make_tuple((int)dev.index(), stream, P);
     {
@@ -289,23 +273,23 @@ Backward backward_core(const Tensor &bg, const Tensor &means3D, const Tensor &ra
         if (it != g_accum.end()) { accum = it->second; g_accum.erase(it); }
     }
     if (!accum.defined()) accum = torch::zeros({std::max<int64_t>(P, 1), 16}, fopt);
-    Backward b = prealloc ? *prealloc : alloc_backward(means3D, opac, sh, sh_rest, cov);
+    Backward b = prealloc ? *prealloc : alloc_backward(g);
     GmsRasterBackwardArgs a{};
-    a.P = (int32_t)P; a.D = (int32_t)D; a.M = (int32_t)M; a.width = (int32_t)W; a.height = (int32_t)H;
-    a.num_rendered = R; a.binning_capacity = capacity;
-    a.background = cf(bg); a.means3D = cf(means3D); a.shs = cf(sh); a.shs_rest = split ? cf(sh_rest) : nullptr;
-    a.colors_precomp = cf(colors); a.opacities = cf(opac); a.scales = cf(scales); a.rotations = cf(rots); a.cov3D_precomp = cf(cov);
-    a.viewmatrix = cf(view); a.projmatrix = cf(proj); a.campos = cf(campos);
-    a.scale_modifier = (float)mod; a.tan_fovx = (float)tanx; a.tan_fovy = (float)tany; a.antialiasing = aa; a.debug = debug;
-    a.radii = P ? radii.data_ptr<int32_t>() : nullptr;
-    a.geom_buffer = geom.numel() ? geom.data_ptr() : nullptr;
-    a.binning_buffer = binning.numel() ? binning.data_ptr() : nullptr;
-    a.image_buffer = image.numel() ? image.data_ptr() : nullptr;
+    a.P = (int32_t)P; a.D = (int32_t)s.D; a.M = (int32_t)M; a.width = (int32_t)s.W; a.height = (int32_t)s.H;
+    a.num_rendered = f.num_rendered; a.binning_capacity = f.capacity;
+    a.background = cf(s.bg); a.means3D = cf(g.means3D); a.shs = cf(g.sh); a.shs_rest = split ? cf(g.sh_rest) : nullptr;
+    a.colors_precomp = cf(g.colors); a.opacities = cf(g.opac); a.scales = cf(g.scales); a.rotations = cf(g.rots); a.cov3D_precomp = cf(g.cov);
+    a.viewmatrix = cf(s.view); a.projmatrix = cf(s.proj); a.campos = cf(s.campos);
+    a.scale_modifier = (float)s.mod; a.tan_fovx = (float)s.tanx; a.tan_fovy = (float)s.tany; a.antialiasing = s.aa; a.debug = s.debug;
+    a.radii = P ? f.radii.data_ptr<int32_t>() : nullptr;
+    a.geom_buffer = f.geom.numel() ? f.geom.data_ptr() : nullptr;
+    a.binning_buffer = f.binning.numel() ? f.binning.data_ptr() : nullptr;
+    a.image_buffer = f.image.numel() ? f.image.data_ptr() : nullptr;
     a.dL_dout_color = cf(gcol); a.dL_dout_invdepth = cf(ginv);
     a.grad_accum = mf(accum); a.dL_dmeans2D = mf(b.dmeans2D); a.dL_dopacity = mf(b.dopacity); a.dL_dcolors = mf(b.dcolors);
     a.dL_dmeans3D = mf(b.dmeans3D); a.dL_dcov3D = mf(b.dcov3D); a.dL_dsh = mf(b.dsh); a.dL_dsh_rest = mf(b.dsh_rest);
     a.dL_dscales = mf(b.dscales); a.dL_drotations = mf(b.drots);
-    a.grad_accum_rezero = 1; a.num_units = num_units;
+    a.grad_accum_rezero = 1; a.num_units = f.num_units;
     if (mesh && mesh_grads) {
         a.mesh = mesh; a.mesh_dL_dvertices = mf(mesh_grads->d_vertices); a.mesh_dL_dalpha = mf(mesh_grads->d_alpha);
         a.mesh_dL_dscale = mf(mesh_grads->d_scale); a.mesh_dL_d_opacity = mf(mesh_grads->d_opacity);
@@ -339,9 +323,10 @@ rasterize_gaussians(const Tensor &background, const Tensor &means3D, const Tenso
 {
     // synchronous sizing (no capacity hint): the binning buffer is laid out for exactly `rendered` instances, which is all
     // the upstream-shaped backward call below knows about it
-    Forward f = forward_core(background, means3D, sh, Tensor(), colors, opacity, scales, rotations, cov3D_precomp, viewmatrix,
-                             projmatrix, campos, image_height, image_width, tan_fovx, tan_fovy, scale_modifier, degree, prefiltered,
-                             antialiasing, debug, Tensor(), false);
+    const Gaussians g = tensor_gaussians(means3D, sh, Tensor(), colors, opacity, scales, rotations, cov3D_precomp);
+    const FrameSettings s = frame_settings(means3D.device(), background, viewmatrix, projmatrix, campos, image_height, image_width, tan_fovx,
+                                           tan_fovy, scale_modifier, degree, prefiltered, antialiasing, debug);
+    Forward f = forward_core(s, means3D.size(0), means3D.device(), g, Tensor(), false);
     return std::make_tuple(f.num_rendered, f.color, f.radii, f.geom, f.binning, f.image, f.invdepth);
 }
 
@@ -353,10 +338,13 @@ rasterize_gaussians_backward(const Tensor &background, const Tensor &means3D, co
                              int64_t degree, const Tensor &campos, const Tensor &geomBuffer, int64_t R, const Tensor &binningBuffer,
                              const Tensor &imageBuffer, bool antialiasing, bool debug)
 {
-    Backward b = backward_core(f32c(background), f32c(means3D), radii, f32c(colors), f32c(opacities), f32c(scales), f32c(rotations),
-                               scale_modifier, f32c(cov3D_precomp), f32c(viewmatrix), f32c(projmatrix), tan_fovx, tan_fovy, dL_dout_color,
-                               dL_dout_invdepth, f32c(sh), Tensor(), degree, f32c(campos), geomBuffer, R, R > 0 ? R : 1, 0, binningBuffer,
-                               imageBuffer, antialiasing, debug);
+    const Gaussians g = tensor_gaussians(means3D, sh, Tensor(), colors, opacities, scales, rotations, cov3D_precomp);
+    const int64_t H = dL_dout_color.defined() ? dL_dout_color.size(-2) : 0, W = dL_dout_color.defined() ? dL_dout_color.size(-1) : 0;
+    const FrameSettings s = frame_settings(means3D.device(), background, viewmatrix, projmatrix, campos, H, W, tan_fovx, tan_fovy,
+                                           scale_modifier, degree, false, antialiasing, debug);
+    Forward f;
+    f.radii = radii; f.geom = geomBuffer; f.binning = binningBuffer; f.image = imageBuffer; f.num_rendered = R; f.capacity = R > 0 ? R : 1;
+    Backward b = backward_core(s, g, f, dL_dout_color, dL_dout_invdepth);
     return std::make_tuple(b.dmeans2D, b.dcolors, b.dopacity, b.dmeans3D, b.dcov3D, b.dsh, b.dscales, b.drots);
 }
 
@@ -372,6 +360,78 @@ Tensor mark_visible(const Tensor &means3D, const Tensor &viewmatrix, const Tenso
 }
 
 // ---------------------------------------------------------------------------------------------- autograd fast path
+// What an autograd node keeps of its frame: the settings and the forward's radii / scratch go to the end of its saved tensors, the
+// scalars and the frame record (counts, capacity, deferred ticket) to saved_data
+void save_frame(AutogradContext *ctx, std::vector<Tensor> tensors, const FrameSettings &s, const Forward &f)
+{
+    tensors.insert(tensors.end(), {f.radii, f.geom, f.binning, f.image, s.bg, s.view, s.proj, s.campos});
+    ctx->save_for_backward(tensors);
+    auto &d = ctx->saved_data;
+    d["H"] = s.H; d["W"] = s.W; d["tanx"] = s.tanx; d["tany"] = s.tany; d["mod"] = s.mod; d["D"] = s.D; d["aa"] = s.aa; d["debug"] = s.debug;
+    d["R"] = f.num_rendered; d["units"] = f.num_units; d["cap"] = f.capacity;
+    d["ticket0"] = f.ticket[0]; d["ticket1"] = f.ticket[1]; d["launched"] = f.launched_units;
+}
+std::pair<FrameSettings, Forward> load_frame(AutogradContext *ctx, const variable_list &saved)
+{
+    auto &d = ctx->saved_data;
+    const size_t k = saved.size() - 8;
+    FrameSettings s{saved[k + 4], saved[k + 5], saved[k + 6], saved[k + 7], d["H"].toInt(), d["W"].toInt(), d["tanx"].toDouble(),
+                    d["tany"].toDouble(), d["mod"].toDouble(), d["D"].toInt(), false, d["aa"].toBool(), d["debug"].toBool()};
+    Forward f;
+    f.radii = saved[k]; f.geom = saved[k + 1]; f.binning = saved[k + 2]; f.image = saved[k + 3];
+    f.num_rendered = d["R"].toInt(); f.num_units = d["units"].toInt(); f.capacity = d["cap"].toInt();
+    f.ticket[0] = d["ticket0"].toInt(); f.ticket[1] = d["ticket1"].toInt(); f.launched_units = d["launched"].toInt();
+    return {s, f};
+}
+
+// Start of a backward whose forward deferred its counts: wait for them (they arrived long ago on a GPU-bound loop), check that the frame
+// fitted what it was launched for, feed the capacity hint.  The counts replace the ticket in `f` and in saved_data, so a second backward
+// through a retained graph does not redeem it again.
+void redeem_counts(AutogradContext *ctx, const FrameSettings &s, Forward &f, const Tensor &means3D)
+{
+    if (f.ticket[0] == 0) return;
+    const auto dev = means3D.device();
+    const int64_t P = means3D.size(0);
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+    int64_t units = 0, deepest = 0;
+    const int64_t n = gms_rasterize_forward_counts(f.ticket, (int32_t)s.W, (int32_t)s.H, (int32_t)P, &units, &deepest, stream_of(dev));
+    check_rc(n, "gms_rasterize_forward_counts");
+    {
+        std::lock_guard<std::mutex> lk(g_mu);
+        int64_t &c = g_capacity[std::make_tuple((int)dev.index(), (int)s.W, (int)s.H, P)];
+        c = std::max(n, (int64_t)(0.97 * (double)c));
+        g_last.num_rendered = n; g_last.num_units = units;
+    }
+    TORCH_CHECK(n <= f.capacity && units <= f.launched_units,
+                "GMS_DEFERRED_OVERFLOW: the frame held ", n, " instances / ", units, " work units but was launched for ", f.capacity, " / ", f.launched_units,
+                " (deferred read-back of the instance count: diff_gaussian_rasterization.set_deferred_counts): its image is incomplete -- "
+                "redo this step (the capacity hint has been raised; or render it with set_deferred_counts(False))");
+    f.ticket[0] = 0; f.num_rendered = n; f.num_units = units;
+    ctx->saved_data["ticket0"] = (int64_t)0; ctx->saved_data["R"] = n; ctx->saved_data["units"] = units;
+}
+
+// The backward's outputs, allocated in the forward (see Backward) and handed out once: a second backward through a retained graph
+// allocates its own
+Tensor Backward::*const kBackwardFields[9] = {&Backward::dmeans2D, &Backward::dcolors, &Backward::dopacity, &Backward::dmeans3D, &Backward::dcov3D,
+                                              &Backward::dsh, &Backward::dsh_rest, &Backward::dscales, &Backward::drots};
+void stash_backward(AutogradContext *ctx, const Backward &b)
+{
+    for (int k = 0; k < 9; k++)
+        if ((b.*kBackwardFields[k]).defined()) ctx->saved_data[std::string("pre") + char('0' + k)] = b.*kBackwardFields[k];
+    ctx->saved_data["pre"] = true;
+}
+std::optional<Backward> take_backward(AutogradContext *ctx)
+{
+    if (!ctx->saved_data.count("pre")) return std::nullopt;
+    Backward b;
+    for (int k = 0; k < 9; k++) {
+        const std::string key = std::string("pre") + char('0' + k);
+        if (ctx->saved_data.count(key)) { b.*kBackwardFields[k] = ctx->saved_data[key].toTensor(); ctx->saved_data.erase(key); }
+    }
+    ctx->saved_data.erase("pre");
+    return b;
+}
+
 class RasterizeFn : public torch::autograd::Function<RasterizeFn> {
 public:
     static variable_list forward(AutogradContext *ctx, Tensor means3D, Tensor means2D, Tensor sh, Tensor sh_rest, Tensor colors,
@@ -380,61 +440,27 @@ public:
                                  bool aa, bool debug, Tensor visible_out, bool use_hint, bool will_backward)
     {
         ctx->set_materialize_grads(false);      // an unused output (inverse depth in train.py) arrives undefined: its channel is skipped
-        if (will_backward && means3D.is_cuda()) {
-            c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(means3D.device());
-            Backward pre = alloc_backward(means3D, opacities, sh, sh_rest, cov3D);
-            const Tensor *ts[9] = {&pre.dmeans2D, &pre.dcolors, &pre.dopacity, &pre.dmeans3D, &pre.dcov3D, &pre.dsh, &pre.dsh_rest,
-                                   &pre.dscales, &pre.drots};
-            for (int k = 0; k < 9; k++)
-                if (ts[k]->defined()) ctx->saved_data[std::string("pre") + char('0' + k)] = *ts[k];
-            ctx->saved_data["pre"] = true;
-        }
-        Forward f = forward_core(bg, means3D, sh, sh_rest, colors, opacities, scales, rotations, cov3D, view, proj, campos, H, W, tanx,
-                                 tany, mod, D, prefiltered, aa, debug, visible_out, use_hint, nullptr, nullptr, will_backward && use_hint);
-        ctx->saved_data["ticket0"] = f.ticket[0]; ctx->saved_data["ticket1"] = f.ticket[1]; ctx->saved_data["launched"] = f.launched_units;
+        const Gaussians g = tensor_gaussians(means3D, sh, sh_rest, colors, opacities, scales, rotations, cov3D);
         const auto dev = means3D.device();
-        ctx->save_for_backward({f32c(means3D), f32c(sh), f32c(sh_rest), f32c(colors), f32c(opacities), f32c(scales), f32c(rotations),
-                                f32c(cov3D), f.radii, f.geom, f.binning, f.image, f32c(bg.to(dev)), f32c(view.to(dev)),
-                                f32c(proj.to(dev)), f32c(campos.to(dev))});
-        ctx->saved_data["R"] = f.num_rendered; ctx->saved_data["units"] = f.num_units; ctx->saved_data["cap"] = f.capacity;
-        ctx->saved_data["tanx"] = tanx; ctx->saved_data["tany"] = tany; ctx->saved_data["mod"] = mod; ctx->saved_data["D"] = D;
-        ctx->saved_data["aa"] = aa; ctx->saved_data["debug"] = debug; ctx->saved_data["H"] = H; ctx->saved_data["W"] = W;
+        const FrameSettings s = frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, D, prefiltered, aa, debug);
+        if (will_backward && means3D.is_cuda()) { c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev); stash_backward(ctx, alloc_backward(g)); }
+        Forward f = forward_core(s, means3D.size(0), dev, g, visible_out, use_hint, nullptr, nullptr, will_backward && use_hint);
+        save_frame(ctx, {g.sh, g.sh_rest, g.means3D, g.colors, g.opac, g.scales, g.rots, g.cov}, s, f);
         ctx->mark_non_differentiable({f.radii});
         return {f.color, f.radii, f.invdepth};
     }
 
     static variable_list backward(AutogradContext *ctx, variable_list grads)
     {
-        auto s = ctx->get_saved_variables();
-        const Tensor &means3D = s[0], &sh = s[1], &sh_rest = s[2], &colors = s[3], &opac = s[4], &scales = s[5], &rots = s[6], &cov = s[7];
-        const Tensor &radii = s[8], &geom = s[9], &binning = s[10], &image = s[11], &bg = s[12], &view = s[13], &proj = s[14], &campos = s[15];
-        const int64_t H = ctx->saved_data["H"].toInt(), W = ctx->saved_data["W"].toInt();
-        Tensor gcol = grads[0].defined() ? grads[0] : torch::zeros({3, H, W}, means3D.options());
-        Backward pre;
-        const bool have_pre = ctx->saved_data.count("pre") > 0;
-        if (have_pre) {        // handed out once: a second backward through a retained graph allocates its own outputs
-            Tensor *ts[9] = {&pre.dmeans2D, &pre.dcolors, &pre.dopacity, &pre.dmeans3D, &pre.dcov3D, &pre.dsh, &pre.dsh_rest, &pre.dscales,
-                             &pre.drots};
-            for (int k = 0; k < 9; k++) {
-                const std::string key = std::string("pre") + char('0' + k);
-                if (ctx->saved_data.count(key)) { *ts[k] = ctx->saved_data[key].toTensor(); ctx->saved_data.erase(key); }
-            }
-            ctx->saved_data.erase("pre");
-        }
-        int64_t R = ctx->saved_data["R"].toInt(), units = ctx->saved_data["units"].toInt();
-        if (ctx->saved_data["ticket0"].toInt() != 0) {
-            c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(means3D.device());
-            const int64_t ticket[2] = {ctx->saved_data["ticket0"].toInt(), ctx->saved_data["ticket1"].toInt()};
-            std::tie(R, units) = redeem_counts(ticket, ctx->saved_data["cap"].toInt(), ctx->saved_data["launched"].toInt(), means3D, W, H, means3D.size(0));
-            ctx->saved_data["ticket0"] = (int64_t)0; ctx->saved_data["R"] = R; ctx->saved_data["units"] = units;      // (a second backward through a retained graph)
-        }
-        Backward b = backward_core(bg, means3D, radii, colors, opac, scales, rots, ctx->saved_data["mod"].toDouble(), cov, view, proj,
-                                   ctx->saved_data["tanx"].toDouble(), ctx->saved_data["tany"].toDouble(), gcol, grads[2], sh, sh_rest,
-                                   ctx->saved_data["D"].toInt(), campos, geom, R, ctx->saved_data["cap"].toInt(),
-                                   units, binning, image, ctx->saved_data["aa"].toBool(),
-                                   ctx->saved_data["debug"].toBool(), have_pre ? &pre : nullptr);
+        auto saved = ctx->get_saved_variables();
+        const Gaussians g{saved[0], saved[1], saved[2], saved[3], saved[4], saved[5], saved[6], saved[7]};
+        auto [s, f] = load_frame(ctx, saved);
+        Tensor gcol = grads[0].defined() ? grads[0] : torch::zeros({3, s.H, s.W}, g.means3D.options());
+        std::optional<Backward> pre = take_backward(ctx);
+        redeem_counts(ctx, s, f, g.means3D);
+        Backward b = backward_core(s, g, f, gcol, grads[2], pre ? &*pre : nullptr);
         Tensor none;
-        if (sh.defined() && sh.numel() > 0) b.dcolors = none;          // (factorised mode: the factor is not a gradient of `colors`)
+        if (g.sh.defined() && g.sh.numel() > 0) b.dcolors = none;          // (factorised mode: the factor is not a gradient of `colors`)
         return {b.dmeans3D, b.dmeans2D, b.dsh, b.dsh_rest, b.dcolors, b.dopacity, b.dscales, b.drots, b.dcov3D,
                 none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none};
     }
@@ -534,6 +560,28 @@ GmsMeshArgs mesh_args(const Tensor &vertices, const Tensor &faces, const Tensor 
     return a;
 }
 
+void check_split_sh(const char *what, const Tensor &sh_dc, const Tensor &sh_rest)
+{
+    TORCH_CHECK(sh_dc.dim() == 3 && sh_dc.size(1) == 1 && sh_rest.dim() == 3 && sh_rest.size(1) == 15, what,
+                " needs split degree-3 SH storage ([P,1,3] + [P,15,3])");
+}
+// The inputs of a frame rendered straight from a mesh (`what` names the caller in the messages).  Returns P.
+int64_t check_mesh_frame(const char *what, const Tensor &vertices, const Tensor &faces, const Tensor &_alpha, const Tensor &_scale,
+                         const Tensor &_opacity, int64_t spf, const Tensor &splat_face, const Tensor &sh_dc, const Tensor &sh_rest)
+{
+    require_gpu(vertices); require_gpu(_alpha); require_gpu(_scale); require_gpu(_opacity); require_gpu(sh_dc); require_gpu(sh_rest);
+    TORCH_CHECK(faces.scalar_type() == torch::kInt64 && faces.is_contiguous() && faces.is_cuda(), "faces must be a contiguous int64 device tensor");
+    const int64_t P = _scale.numel();
+    TORCH_CHECK(_alpha.numel() == 3 * P && _opacity.numel() == P && sh_dc.size(0) == P && sh_rest.size(0) == P, what, ": P mismatch");
+    TORCH_CHECK(faces.dim() == 2 && faces.size(1) == 3, "faces must have dimensions (num_faces, 3)");
+    TORCH_CHECK(vertices.dim() == 2 && vertices.size(1) == 3, "vertices must have dimensions (num_vertices, 3)");
+    TORCH_CHECK(faces.device() == sh_dc.device() && vertices.device() == sh_dc.device(), what, ": mesh and SH tensors live on different devices");
+    if (spf > 0) { TORCH_CHECK(faces.size(0) * spf == P, what, ": ", faces.size(0), " faces x ", spf, " splats per face != ", P, " Gaussians"); }
+    else { TORCH_CHECK(splat_face.defined() && splat_face.numel() == P, what, ": non-uniform splat counts need splat_face [P]"); }
+    check_split_sh(what, sh_dc, sh_rest);
+    return P;
+}
+
 // Forward-only frame of the animated render drivers (games_hip.animate): mesh -> image in the rasterizer's own launches, K0 inside
 // the preprocess thread (GmsRasterForwardArgs.mesh).  Returns (image, radii, inverse depth, radii > 0).
 std::tuple<Tensor, Tensor, Tensor, Tensor> render_mesh_forward(const Tensor &vertices, const Tensor &faces, const Tensor &_alpha, const Tensor &_scale,
@@ -542,23 +590,13 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> render_mesh_forward(const Tensor &ver
                                                        const Tensor &proj, const Tensor &campos, int64_t H, int64_t W, double tanx, double tany,
                                                        double mod, bool aa, bool debug)
 {
-    require_gpu(vertices); require_gpu(_alpha); require_gpu(_scale); require_gpu(_opacity); require_gpu(sh_dc); require_gpu(sh_rest);
-    TORCH_CHECK(faces.scalar_type() == torch::kInt64 && faces.is_contiguous() && faces.is_cuda(), "faces must be a contiguous int64 device tensor");
+    const int64_t P = check_mesh_frame("render_mesh_forward", vertices, faces, _alpha, _scale, _opacity, spf, splat_face, sh_dc, sh_rest);
     Tensor v = f32c(vertices), al = f32c(_alpha), sc = f32c(_scale), op = f32c(_opacity);
-    const int64_t P = sc.numel();
-    TORCH_CHECK(al.numel() == 3 * P && op.numel() == P && sh_dc.size(0) == P && sh_rest.size(0) == P, "render_mesh_forward: P mismatch");
-    TORCH_CHECK(faces.dim() == 2 && faces.size(1) == 3, "faces must have dimensions (num_faces, 3)");
-    TORCH_CHECK(v.dim() == 2 && v.size(1) == 3, "vertices must have dimensions (num_vertices, 3)");
-    TORCH_CHECK(faces.device() == sh_dc.device() && v.device() == sh_dc.device(), "render_mesh_forward: mesh and SH tensors live on different devices");
-    if (spf > 0) { TORCH_CHECK(faces.size(0) * spf == P, "render_mesh_forward: ", faces.size(0), " faces x ", spf, " splats per face != ", P, " Gaussians"); }
-    else { TORCH_CHECK(splat_face.defined() && splat_face.numel() == P, "render_mesh_forward: non-uniform splat counts need splat_face [P]"); }
-    TORCH_CHECK(sh_dc.dim() == 3 && sh_dc.size(1) == 1 && sh_rest.dim() == 3 && sh_rest.size(1) == 15, "render_mesh_forward needs split degree-3 SH storage ([P,1,3] + [P,15,3])");
     GmsMeshArgs m = mesh_args(v, faces, al, sc, mode, spf, Tensor(), splat_face, true, op);
-    // (P stands in for means3D: forward_core reads the device and the count from its first tensor argument)
-    Tensor stand_in = sh_dc.view({P, 3});
     Tensor visible = torch::empty({P}, sh_dc.options().dtype(torch::kBool));          // radii > 0, written by the preprocess kernel
-    Forward f = forward_core(bg, stand_in, sh_dc, sh_rest, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), view, proj, campos, H, W, tanx, tany, mod,
-                             3, false, aa, debug, visible, true, &m);
+    const auto dev = sh_dc.device();
+    Forward f = forward_core(frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, 3, false, aa, debug), P, dev,
+                             {f32c(sh_dc), f32c(sh_rest)}, visible, true, &m);
     return std::make_tuple(f.color, f.radii, f.invdepth, visible);
 }
 
@@ -747,13 +785,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> render_points_forward(const Tensor &t
     TORCH_CHECK(sh_degree >= 0 && sh_degree <= 3, "render_points_forward: active SH degree ", sh_degree, " (storage is degree 3: 0 .. 3)");
     TORCH_CHECK(op.numel() == P && sh_dc.size(0) == P && sh_rest.size(0) == P, "render_points_forward: P mismatch");
     TORCH_CHECK(tri.device() == sh_dc.device() && op.device() == sh_dc.device(), "render_points_forward: triangles and SH tensors live on different devices");
-    TORCH_CHECK(sh_dc.dim() == 3 && sh_dc.size(1) == 1 && sh_rest.dim() == 3 && sh_rest.size(1) == 15, "render_points_forward needs split degree-3 SH storage ([P,1,3] + [P,15,3])");
+    check_split_sh("render_points_forward", sh_dc, sh_rest);
     GmsPointsArgs pa = points_args(tri, op, eps, eps_s0);
-    // (P stands in for means3D: forward_core reads the device and the count from its first tensor argument)
-    Tensor stand_in = sh_dc.view({P, 3});
     Tensor visible = torch::empty({P}, sh_dc.options().dtype(torch::kBool));          // radii > 0, written by the preprocess kernel
-    Forward f = forward_core(bg, stand_in, sh_dc, sh_rest, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), view, proj, campos, H, W, tanx, tany, mod,
-                             sh_degree, false, aa, debug, visible, true, nullptr, nullptr, false, &pa);
+    const auto dev = sh_dc.device();
+    Forward f = forward_core(frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, sh_degree, false, aa, debug), P, dev,
+                             {f32c(sh_dc), f32c(sh_rest)}, visible, true, nullptr, nullptr, false, &pa);
     return std::make_tuple(f.color, f.radii, f.invdepth, visible);
 }
 
@@ -763,6 +800,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> render_points_forward(const Tensor &t
 // preprocess thread derives its Gaussian from the face and stores xyz / activated scale / unit quaternion / sigmoid opacity (44 bytes
 // per Gaussian instead of K0's 84 written + 44 read back).  Backward: gms_rasterize_backward on those four tensors, then
 // gms_mesh_to_gaussians_backward on its gradients -- the same two kernels groups as the two-node graph, one node's worth of host work.
+// the Gaussians a mesh frame stores for its backward, as the rasterizer's backward reads them
+Gaussians stored_gaussians(const MeshOut &mo, const Tensor &dc, const Tensor &rest)
+{
+    return {dc, rest, mo.xyz, Tensor(), mo.opacity_act, mo.scaling_act, mo.rotation_unit, Tensor()};
+}
+
 class RenderMeshFn : public torch::autograd::Function<RenderMeshFn> {
 public:
     static variable_list forward(AutogradContext *ctx, Tensor vertices_, Tensor faces, Tensor alpha_, Tensor scale_, Tensor opacity_,
@@ -772,46 +815,24 @@ public:
     {
         ctx->set_materialize_grads(false);
         TORCH_CHECK(sh_degree >= 0 && sh_degree <= 3, "render_mesh: active SH degree ", sh_degree, " (storage is degree 3: 0 .. 3)");
-        require_gpu(vertices_); require_gpu(alpha_); require_gpu(scale_); require_gpu(opacity_); require_gpu(sh_dc); require_gpu(sh_rest);
-        TORCH_CHECK(faces.scalar_type() == torch::kInt64 && faces.is_contiguous() && faces.is_cuda(), "faces must be a contiguous int64 device tensor");
+        const int64_t P = check_mesh_frame("render_mesh", vertices_, faces, alpha_, scale_, opacity_, spf, splat_face, sh_dc, sh_rest);
         const auto dev = vertices_.device();
         c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
         Tensor v = f32c(vertices_), al = f32c(alpha_), sc = f32c(scale_), op = f32c(opacity_), dc = f32c(sh_dc), rest = f32c(sh_rest);
-        const int64_t P = sc.numel();
-        TORCH_CHECK(al.numel() == 3 * P && op.numel() == P && dc.size(0) == P && rest.size(0) == P, "render_mesh: P mismatch");
-        TORCH_CHECK(dc.dim() == 3 && dc.size(1) == 1 && rest.dim() == 3 && rest.size(1) == 15, "render_mesh needs split degree-3 SH storage ([P,1,3] + [P,15,3])");
-        TORCH_CHECK(faces.dim() == 2 && faces.size(1) == 3, "faces must have dimensions (num_faces, 3)");
-        TORCH_CHECK(v.dim() == 2 && v.size(1) == 3, "vertices must have dimensions (num_vertices, 3)");
-        if (spf > 0) { TORCH_CHECK(faces.size(0) * spf == P, "render_mesh: ", faces.size(0), " faces x ", spf, " splats per face != ", P, " Gaussians"); }
-        else { TORCH_CHECK(splat_face.defined() && splat_face.numel() == P, "render_mesh: non-uniform splat counts need splat_face [P]"); }
         auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
         MeshOut mo{torch::empty({P, 3}, fopt), torch::empty({P, 3}, fopt), torch::empty({P, 4}, fopt), torch::empty_like(op)};
-        Tensor vgrad;
-        if (will_backward && vertex_grad) vgrad = torch::empty_like(v);
-        if (will_backward) {          // the backward's outputs, allocated while the host is ahead of the GPU (see RasterizeFn)
-            Backward pre = alloc_backward(mo.xyz, mo.opacity_act, dc, rest, Tensor());
-            const Tensor *ts[9] = {&pre.dmeans2D, &pre.dcolors, &pre.dopacity, &pre.dmeans3D, &pre.dcov3D, &pre.dsh, &pre.dsh_rest, &pre.dscales, &pre.drots};
-            for (int k = 0; k < 9; k++)
-                if (ts[k]->defined()) ctx->saved_data[std::string("pre") + char('0' + k)] = *ts[k];
-            ctx->saved_data["pre"] = true;
-        }
+        Tensor vgrad = will_backward && vertex_grad ? torch::empty_like(v) : Tensor();
+        if (will_backward) stash_backward(ctx, alloc_backward(stored_gaussians(mo, dc, rest)));      // (see Backward)
         Tensor sf = (splat_face.defined() && splat_face.numel()) ? splat_face.to(torch::kInt).contiguous() : Tensor();
         GmsMeshArgs m = mesh_args(v, faces, al, sc, mode, spf, Tensor(), sf, true, op);
         m.prezero = mf(vgrad); m.prezero_count = vgrad.defined() ? vgrad.numel() : 0;
-        Tensor stand_in = dc.view({P, 3});          // (forward_core reads the device and the count from its first tensor argument)
         // `visibility_filter` (radii > 0, renderer/gaussian_renderer/__init__.py:108) out of the preprocess kernel, as on the two-node route
         Tensor visible = torch::empty({P}, fopt.dtype(torch::kBool));
-        Forward f = forward_core(bg, stand_in, dc, rest, Tensor(), Tensor(), Tensor(), Tensor(), Tensor(), view, proj, campos, H, W, tanx, tany, mod,
-                                 sh_degree, false, aa, debug, visible, true, &m, &mo, will_backward);
-        ctx->saved_data["D"] = sh_degree;
-        ctx->saved_data["ticket0"] = f.ticket[0]; ctx->saved_data["ticket1"] = f.ticket[1]; ctx->saved_data["launched"] = f.launched_units;
-        ctx->save_for_backward({v, faces, al, sc, op, sf.defined() ? sf : torch::empty({0}, fopt), vgrad.defined() ? vgrad : torch::empty({0}, fopt),
-                                mo.xyz, mo.scaling_act, mo.rotation_unit, mo.opacity_act, dc, rest, f.radii, f.geom, f.binning, f.image,
-                                f32c(bg.to(dev)), f32c(view.to(dev)), f32c(proj.to(dev)), f32c(campos.to(dev))});
-        ctx->saved_data["R"] = f.num_rendered; ctx->saved_data["units"] = f.num_units; ctx->saved_data["cap"] = f.capacity;
-        ctx->saved_data["tanx"] = tanx; ctx->saved_data["tany"] = tany; ctx->saved_data["mod"] = mod; ctx->saved_data["aa"] = aa;
-        ctx->saved_data["debug"] = debug; ctx->saved_data["H"] = H; ctx->saved_data["W"] = W; ctx->saved_data["mode"] = mode;
-        ctx->saved_data["spf"] = spf; ctx->saved_data["used"] = false;
+        const FrameSettings s = frame_settings(dc.device(), bg, view, proj, campos, H, W, tanx, tany, mod, sh_degree, false, aa, debug);
+        Forward f = forward_core(s, P, dc.device(), {dc, rest}, visible, true, &m, &mo, will_backward);
+        save_frame(ctx, {v, faces, al, sc, op, sf.defined() ? sf : torch::empty({0}, fopt), vgrad.defined() ? vgrad : torch::empty({0}, fopt),
+                         mo.xyz, mo.scaling_act, mo.rotation_unit, mo.opacity_act, dc, rest}, s, f);
+        ctx->saved_data["mode"] = mode; ctx->saved_data["spf"] = spf; ctx->saved_data["used"] = false;
         // the stored Gaussians are by-products for the model's attributes: gradients reach the mesh parameters through THIS node
         ctx->mark_non_differentiable({f.radii, mo.xyz, mo.scaling_act, mo.rotation_unit, mo.opacity_act, visible});
         return {f.color, f.radii, f.invdepth, mo.xyz, mo.scaling_act, mo.rotation_unit, mo.opacity_act, visible};
@@ -819,34 +840,19 @@ public:
 
     static variable_list backward(AutogradContext *ctx, variable_list grads)
     {
-        auto s = ctx->get_saved_variables();
-        const Tensor &v = s[0], &faces = s[1], &al = s[2], &sc = s[3], &op = s[4];
-        Tensor sf = s[5].numel() ? s[5] : Tensor();
-        const Tensor &xyz = s[7], &sact = s[8], &runit = s[9], &oact = s[10], &dc = s[11], &rest = s[12];
-        const Tensor &radii = s[13], &geom = s[14], &binning = s[15], &image = s[16], &bg = s[17], &view = s[18], &proj = s[19], &campos = s[20];
+        auto saved = ctx->get_saved_variables();
+        const Tensor &v = saved[0], &faces = saved[1], &al = saved[2], &sc = saved[3], &op = saved[4];
+        Tensor sf = saved[5].numel() ? saved[5] : Tensor();
+        const Gaussians g = stored_gaussians({saved[7], saved[8], saved[9], saved[10]}, saved[11], saved[12]);
+        auto [s, f] = load_frame(ctx, saved);
         const auto dev = v.device();
         c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
-        const int64_t H = ctx->saved_data["H"].toInt(), W = ctx->saved_data["W"].toInt();
-        Tensor gcol = grads[0].defined() ? grads[0] : torch::zeros({3, H, W}, xyz.options());
-        Backward pre;
-        const bool have_pre = ctx->saved_data.count("pre") > 0;
-        if (have_pre) {
-            Tensor *ts[9] = {&pre.dmeans2D, &pre.dcolors, &pre.dopacity, &pre.dmeans3D, &pre.dcov3D, &pre.dsh, &pre.dsh_rest, &pre.dscales, &pre.drots};
-            for (int k = 0; k < 9; k++) {
-                const std::string key = std::string("pre") + char('0' + k);
-                if (ctx->saved_data.count(key)) { *ts[k] = ctx->saved_data[key].toTensor(); ctx->saved_data.erase(key); }
-            }
-            ctx->saved_data.erase("pre");
-        }
-        int64_t R = ctx->saved_data["R"].toInt(), units = ctx->saved_data["units"].toInt();
-        if (ctx->saved_data["ticket0"].toInt() != 0) {
-            const int64_t ticket[2] = {ctx->saved_data["ticket0"].toInt(), ctx->saved_data["ticket1"].toInt()};
-            std::tie(R, units) = redeem_counts(ticket, ctx->saved_data["cap"].toInt(), ctx->saved_data["launched"].toInt(), xyz, W, H, xyz.size(0));
-            ctx->saved_data["ticket0"] = (int64_t)0; ctx->saved_data["R"] = R; ctx->saved_data["units"] = units;
-        }
+        Tensor gcol = grads[0].defined() ? grads[0] : torch::zeros({3, s.H, s.W}, g.means3D.options());
+        std::optional<Backward> pre = take_backward(ctx);
+        redeem_counts(ctx, s, f, g.means3D);
         Tensor d_vertices;
         bool prezeroed = false;
-        if (s[6].numel() && !ctx->saved_data["used"].toBool()) { d_vertices = s[6]; prezeroed = true; ctx->saved_data["used"] = true; }
+        if (saved[6].numel() && !ctx->saved_data["used"].toBool()) { d_vertices = saved[6]; prezeroed = true; ctx->saved_data["used"] = true; }
         else d_vertices = torch::empty_like(v);
         Tensor d_alpha = torch::empty_like(al), d_scale = torch::empty_like(sc), d_opacity = torch::empty_like(op);
         GmsMeshArgs a = mesh_args(v, faces, al, sc, ctx->saved_data["mode"].toInt(), ctx->saved_data["spf"].toInt(), Tensor(), sf, true, op);
@@ -856,24 +862,14 @@ public:
         // gradient buffer the forward cleared, 1-4 splats per face, float-atomics mode.  GMS_TRAIN_FUSED_BWD=0 keeps the two launches.
         const bool fused_bwd = fused_mesh_backward() && prezeroed && a.splats_per_face > 0 && a.splats_per_face <= 4 && !gms_get_deterministic() && !g_sh_factor.load();
         MeshGrads mg{d_vertices, d_alpha, d_scale, d_opacity};
-        Backward b = backward_core(bg, xyz, radii, Tensor(), oact, sact, runit, ctx->saved_data["mod"].toDouble(), Tensor(), view, proj,
-                                   ctx->saved_data["tanx"].toDouble(), ctx->saved_data["tany"].toDouble(), gcol, grads[2], dc, rest,
-                                   ctx->saved_data["D"].toInt(), campos, geom,
-                                   R, ctx->saved_data["cap"].toInt(), units, binning, image,
-                                   ctx->saved_data["aa"].toBool(), ctx->saved_data["debug"].toBool(), have_pre ? &pre : nullptr,
-                                   fused_bwd ? &a : nullptr, fused_bwd ? &mg : nullptr);
-        if (fused_bwd) {
-            Tensor none;
-            return {d_vertices, none, d_alpha, d_scale, d_opacity, b.dsh, b.dsh_rest, b.dmeans2D,
-                    none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none};
+        Backward b = backward_core(s, g, f, gcol, grads[2], pre ? &*pre : nullptr, fused_bwd ? &a : nullptr, fused_bwd ? &mg : nullptr);
+        if (!fused_bwd) {
+            // ... else through the mesh -> Gaussian parameterization as a launch of its own (fused activations: gradients w.r.t. exp / normalize /
+            // sigmoid outputs).  Non-uniform splat counts: the per-face part of the mesh backward walks CSR offsets this node does not carry.
+            TORCH_CHECK(a.splats_per_face > 0, "render_mesh backward: non-uniform splat counts take the two-node graph (mesh_to_gaussians + rasterize)");
+            check_rc(gms_mesh_to_gaussians_backward(&a, cf(b.dmeans3D), cf(b.dscales), cf(b.drots), cf(b.dopacity), mf(d_vertices), mf(d_alpha),
+                                                    mf(d_scale), mf(d_opacity), stream_of(v)), "gms_mesh_to_gaussians_backward");
         }
-        // ... else through the mesh -> Gaussian parameterization as a launch of its own (fused activations: gradients w.r.t. exp / normalize / sigmoid outputs)
-        if (a.splats_per_face <= 0) {
-            // (non-uniform splat counts: the per-face part of the mesh backward walks CSR offsets this node does not carry)
-            TORCH_CHECK(false, "render_mesh backward: non-uniform splat counts take the two-node graph (mesh_to_gaussians + rasterize)");
-        }
-        check_rc(gms_mesh_to_gaussians_backward(&a, cf(b.dmeans3D), cf(b.dscales), cf(b.drots), cf(b.dopacity), mf(d_vertices), mf(d_alpha),
-                                                mf(d_scale), mf(d_opacity), stream_of(v)), "gms_mesh_to_gaussians_backward");
         Tensor none;
         return {d_vertices, none, d_alpha, d_scale, d_opacity, b.dsh, b.dsh_rest, b.dmeans2D,
                 none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none};
