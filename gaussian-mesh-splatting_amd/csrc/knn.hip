@@ -8,41 +8,9 @@
 // exact, independent of the order of points inside a cell.  All phases are HBM/atomic bound and run once at
 // model initialisation (not on the per-iteration hot path).
 #include "gms_common.h"
+#include "gms_grid.h"
 
 namespace gms {
-
-__device__ __forceinline__ int float_to_ordered(float f)
-{
-    int i = __float_as_int(f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__device__ __forceinline__ float ordered_to_float(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
-
-// Lives at the head of the workspace; filled on the device so the host never waits for the bounding box.
-struct KnnHeader {
-    int bbox_i[6];        // ordered-int encoded min xyz, max xyz
-    int G[3];             // cells per axis
-    int ncell;
-    float lo[3], h[3], inv_h[3];
-    float slack;          // absolute rounding allowance of a cell-boundary coordinate
-};
-
-struct CellMap {
-    float lo[3], inv_h[3], h[3], slack;
-    int G[3];
-    __device__ __forceinline__ explicit CellMap(const KnnHeader *hd)
-    {
-        slack = hd->slack;
-#pragma unroll
-        for (int k = 0; k < 3; k++) { lo[k] = hd->lo[k]; inv_h[k] = hd->inv_h[k]; h[k] = hd->h[k]; G[k] = hd->G[k]; }
-    }
-    __device__ __forceinline__ void cell_of(const float p[3], int c[3]) const
-    {
-#pragma unroll
-        for (int k = 0; k < 3; k++) c[k] = min(G[k] - 1, max(0, (int)((p[k] - lo[k]) * inv_h[k])));
-    }
-    __device__ __forceinline__ uint32_t flat(int x, int y, int z) const { return (uint32_t)((z * G[1] + y) * G[0] + x); }
-};
 
 __global__ void knn_init_kernel(KnnHeader *hd, uint32_t *cell_count, int max_cell)
 {
@@ -216,20 +184,46 @@ __global__ void __launch_bounds__(BLOCK) knn_query_kernel(int N, const float *pt
     out[i] = k >= 3 ? (d0 + d1 + d2) / 3.f : k == 2 ? (d0 + d1) / 2.f : k == 1 ? d0 : 0.f;
 }
 
-}  // namespace gms
-
-using namespace gms;
-
-static size_t knn_max_cells(int N)
+// ---- host side of the grid (gms_grid.h): also what the nearest-face search of bind.hip is built on
+size_t grid_max_cells(int N)
 {
     size_t m = (size_t)(N > 0 ? N : 1) / 2 + 64;      // about twice the N/4 target: room for the ceil() per axis
     return m > (1u << 22) ? (1u << 22) : m;
 }
 
+// counting sort of `points` into the cells of `hd`; cell_count is zero on entry
+static void bin_launches(int N, const float *points, const KnnHeader *hd, const GridBins &b, hipStream_t stream)
+{
+    const unsigned nb = (unsigned)((N + BLOCK - 1) / BLOCK);
+    knn_count_kernel<<<nb, BLOCK, 0, stream>>>(N, points, hd, b.cell_count, b.point_cell);
+    knn_scan_kernel<<<1, 1024, 0, stream>>>(b.cell_count, b.cell_start, b.cell_cursor, hd);
+    knn_scatter_kernel<<<nb, BLOCK, 0, stream>>>(N, points, b.point_cell, b.cell_cursor, b.sorted);
+}
+
+void grid_bin(int N, const float *points, const KnnHeader *hd, size_t max_cells, const GridBins &b, hipStream_t stream)
+{
+    (void)hipMemsetAsync(b.cell_count, 0, (max_cells + 1) * 4, stream);
+    bin_launches(N, points, hd, b, stream);
+}
+
+void grid_build(int N, const float *points, KnnHeader *hd, size_t max_cells, const GridBins &b, hipStream_t stream)
+{
+    const unsigned nb = (unsigned)((N + BLOCK - 1) / BLOCK);
+    knn_init_kernel<<<256, 256, 0, stream>>>(hd, b.cell_count, (int)max_cells);
+    knn_bbox_kernel<<<nb < 1024 ? nb : 1024, BLOCK, 0, stream>>>(N, points, hd);
+    knn_grid_kernel<<<1, 1, 0, stream>>>(N, hd, (int)max_cells);
+    bin_launches(N, points, hd, b, stream);
+}
+
+}  // namespace gms
+
+using namespace gms;
+
+static_assert(sizeof(KnnHeader) <= 256, "header slot");
+
 extern "C" size_t gms_knn_workspace_bytes(int32_t N)
 {
-    const size_t mc = knn_max_cells(N), n = (size_t)(N > 0 ? N : 1);
-    return 256 + align_up((mc + 1) * 4, 256) * 3 + align_up(n * 4, 256) + align_up(n * 16, 256);
+    return 256 + GridBins::bytes(grid_max_cells(N), (size_t)(N > 0 ? N : 1));
 }
 
 extern "C" int32_t gms_knn_mean_dist2(int32_t N, const float *points, float *out, void *workspace, size_t workspace_bytes,
@@ -240,23 +234,11 @@ extern "C" int32_t gms_knn_mean_dist2(int32_t N, const float *points, float *out
     if (N < 0 || (N > 0 && (!points || !out || !workspace))) { set_error("gms_knn_mean_dist2: invalid argument"); return GMS_ERR_INVALID_ARGUMENT; }
     if (N == 0) return GMS_OK;
     if (workspace_bytes < gms_knn_workspace_bytes(N)) { set_error("gms_knn_mean_dist2: workspace too small"); return GMS_ERR_CAPACITY; }
-    const size_t mc = knn_max_cells(N);
-    static_assert(sizeof(KnnHeader) <= 256, "header slot");
-    char *w = (char *)workspace;
-    KnnHeader *hd = (KnnHeader *)w;               w += 256;
-    uint32_t *cell_count = (uint32_t *)w;         w += align_up((mc + 1) * 4, 256);
-    uint32_t *cell_start = (uint32_t *)w;         w += align_up((mc + 1) * 4, 256);
-    uint32_t *cell_cursor = (uint32_t *)w;        w += align_up((mc + 1) * 4, 256);
-    uint32_t *point_cell = (uint32_t *)w;         w += align_up((size_t)N * 4, 256);
-    float4 *sorted = (float4 *)w;
-    const unsigned nb = (unsigned)((N + BLOCK - 1) / BLOCK);
-    knn_init_kernel<<<256, 256, 0, stream>>>(hd, cell_count, (int)mc);
-    knn_bbox_kernel<<<nb < 1024 ? nb : 1024, BLOCK, 0, stream>>>(N, points, hd);
-    knn_grid_kernel<<<1, 1, 0, stream>>>(N, hd, (int)mc);
-    knn_count_kernel<<<nb, BLOCK, 0, stream>>>(N, points, hd, cell_count, point_cell);
-    knn_scan_kernel<<<1, 1024, 0, stream>>>(cell_count, cell_start, cell_cursor, hd);
-    knn_scatter_kernel<<<nb, BLOCK, 0, stream>>>(N, points, point_cell, cell_cursor, sorted);
-    knn_query_kernel<<<nb, BLOCK, 0, stream>>>(N, points, hd, cell_start, sorted, out);
+    const size_t mc = grid_max_cells(N);
+    KnnHeader *hd = (KnnHeader *)workspace;
+    const GridBins b = GridBins::carve((char *)workspace + 256, mc, (size_t)N);
+    grid_build(N, points, hd, mc, b, stream);
+    knn_query_kernel<<<(unsigned)((N + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(N, points, hd, b.cell_start, b.sorted, out);
     GMS_KERNEL_CHECK(0, stream, "knn");
     return GMS_OK;
 }

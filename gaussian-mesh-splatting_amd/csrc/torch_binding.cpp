@@ -944,6 +944,67 @@ std::vector<Tensor> l1_ssim(const Tensor &img, const Tensor &gt, double w_l1, do
     return L1SsimFn::apply(img, gt, w_l1, w_ssim, bias, at::GradMode::is_enabled() && img.requires_grad());
 }
 
+// ---------------------------------------------------------------------------------------------- pseudo-mesh bound to a guide mesh
+// (scripts/edit_pseudomesh_based_on_estimated_mesh.py; csrc/bind.hip)
+struct Guide { Tensor vertices, faces; int32_t V, F; };
+Guide bind_guide(const Tensor &vertices_, const Tensor &faces_, const char *what)
+{
+    require_gpu(vertices_); require_gpu(faces_);
+    TORCH_CHECK(vertices_.dim() == 2 && vertices_.size(1) == 3, what, ": guide vertices must have dimensions (V, 3)");
+    TORCH_CHECK(faces_.dim() == 2 && faces_.size(1) == 3, what, ": guide faces must have dimensions (F, 3)");
+    TORCH_CHECK(faces_.scalar_type() == torch::kInt, what, ": guide faces must be int32 (convert once, outside the frame loop)");
+    TORCH_CHECK(vertices_.size(0) <= INT32_MAX && faces_.size(0) <= INT32_MAX, what, ": guide too large");
+    Guide g{f32c(vertices_), faces_.is_contiguous() ? faces_ : faces_.contiguous(), (int32_t)vertices_.size(0), (int32_t)faces_.size(0)};
+    TORCH_CHECK(g.F == 0 || g.faces.device() == g.vertices.device(), what, ": guide vertices and faces live on different devices");
+    return g;
+}
+
+// -> (face_idx int32 [P], alpha [P,3,3], number of bindings to a face without a frame)
+std::tuple<Tensor, Tensor, int64_t> bind_pseudomesh(const Tensor &triangles_, const Tensor &guide_vertices, const Tensor &guide_faces)
+{
+    Tensor tri = points_triangles(triangles_, "bind_pseudomesh");
+    Guide g = bind_guide(guide_vertices, guide_faces, "bind_pseudomesh");
+    const int64_t P = tri.size(0);
+    const c10::Device dev = P > 0 ? tri.device() : g.vertices.device();
+    TORCH_CHECK(P == 0 || (g.F > 0 && g.vertices.device() == dev), "bind_pseudomesh: the guide must have faces, on the triangles' device");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor face_idx = torch::empty({P}, torch::TensorOptions().dtype(torch::kInt).device(dev));
+    Tensor alpha = torch::empty({P, 3, 3}, torch::TensorOptions().dtype(torch::kFloat).device(dev));
+    if (P == 0) return {face_idx, alpha, 0};
+    const size_t bytes = gms_bind_workspace_bytes(P, g.F);
+    Tensor work = torch::empty({(int64_t)bytes}, torch::TensorOptions().dtype(torch::kUInt8).device(dev));
+    int32_t degenerate = 0;
+    check_rc(gms_bind_pseudomesh(P, cf(tri), g.V, cf(g.vertices), g.F, g.faces.data_ptr<int32_t>(), face_idx.data_ptr<int32_t>(), mf(alpha),
+                                 &degenerate, work.data_ptr(), bytes, stream_of(dev)),
+             "gms_bind_pseudomesh");
+    return {face_idx, alpha, (int64_t)degenerate};
+}
+
+// launches only (no allocation when `out` is given, no host wait): capturable
+Tensor bind_apply(const Tensor &face_idx, const Tensor &alpha, const Tensor &guide_vertices, const Tensor &guide_faces, const std::optional<Tensor> &out_)
+{
+    Guide g = bind_guide(guide_vertices, guide_faces, "bind_apply");
+    require_gpu(face_idx); require_gpu(alpha);
+    const int64_t P = face_idx.numel();
+    TORCH_CHECK(face_idx.scalar_type() == torch::kInt && face_idx.is_contiguous() && alpha.scalar_type() == torch::kFloat && alpha.is_contiguous() &&
+                alpha.numel() == 9 * P, "bind_apply: face_idx int32 [P] and alpha float32 [P,3,3], contiguous");
+    const c10::Device dev = g.vertices.device();
+    TORCH_CHECK(P == 0 || (g.F > 0 && face_idx.device() == dev && alpha.device() == dev), "bind_apply: the guide must have faces, on the binding's device");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+    Tensor out;
+    if (out_.has_value() && out_->defined()) {
+        out = *out_;
+        TORCH_CHECK(out.scalar_type() == torch::kFloat && out.is_contiguous() && out.numel() == 9 * P && (P == 0 || out.device() == dev),
+                    "bind_apply: out must be a contiguous float32 [P,3,3] on the binding's device");
+    } else {
+        out = torch::empty({P, 3, 3}, torch::TensorOptions().dtype(torch::kFloat).device(dev));
+    }
+    if (P == 0) return out;
+    check_rc(gms_bind_apply(P, face_idx.data_ptr<int32_t>(), cf(alpha), g.V, cf(g.vertices), g.F, g.faces.data_ptr<int32_t>(), mf(out), stream_of(dev)),
+             "gms_bind_apply");
+    return out;
+}
+
 // ---------------------------------------------------------------------------------------------- multi-tensor Adam
 void adam_step(const std::vector<Tensor> &params, const std::vector<Tensor> &grads, const std::vector<Tensor> &exp_avg,
                const std::vector<Tensor> &exp_avg_sq, const std::vector<double> &lrs, const std::vector<int64_t> &steps, double beta1,
@@ -986,6 +1047,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("points_to_gaussians", &points_to_gaussians, "differentiable pseudo-triangle -> Gaussian: [xyz, scaling_raw, rotation_raw, scaling_act, rotation_unit(, opacity_act)]", nogil());
     m.def("points_prepare_vertices", &points_prepare_vertices, "Gaussian -> pseudo-triangle [P,3,3] (prepare_vertices)", nogil());
     m.def("render_points_forward", &render_points_forward, "forward-only frame straight from pseudo-triangles (the points op inside the preprocess thread)", nogil());
+    m.def("bind_pseudomesh", &bind_pseudomesh, "bind pseudo-triangles [P,3,3] to the nearest faces of a guide mesh: (face_idx int32 [P], alpha [P,3,3], n_degenerate)", nogil());
+    m.def("bind_apply", &bind_apply, "pseudo-triangles [P,3,3] of a binding on (edited) guide vertices; launches only", py::arg("face_idx"), py::arg("alpha"),
+          py::arg("guide_vertices"), py::arg("guide_faces"), py::arg("out") = py::none(), nogil());
     m.def("render_mesh", &render_mesh, "differentiable frame straight from a mesh: [image, radii, invdepth, xyz, scaling_act, rotation_unit, opacity_act]", nogil());
     m.def("l1_ssim", &l1_ssim, "differentiable w_l1 * L1 + w_ssim * SSIM + bias; returns (value [0-dim], [l1, ssim])", nogil());
     m.def("adam_step", &adam_step, nogil());

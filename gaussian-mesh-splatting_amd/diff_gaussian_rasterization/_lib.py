@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("GMSPLAT_LIB", os.path.join(os.path.dirname(_HERE), "l
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_size_t)
 
-GMS_ABI_VERSION = 9
+GMS_ABI_VERSION = 10
 GMS_ALPHA_RELU, GMS_ALPHA_SOFTMAX = 0, 1
 ERRORS = {-1: "invalid argument", -2: "scratch allocation failed", -3: "HIP runtime error", -4: "capacity"}
 
@@ -115,8 +115,9 @@ EXPORTS = (
     "gms_image_counts_offset", "gms_last_launched_units", "gms_last_used_micro",
     "gms_set_upstream_scale_mod_grad", "gms_get_upstream_scale_mod_grad", "gms_profile_event_overhead_us",
     "gms_points_prepare_vertices", "gms_points_to_gaussians_forward", "gms_points_to_gaussians_backward",
+    "gms_bind_workspace_bytes", "gms_bind_pseudomesh", "gms_bind_apply",
 )
-K_COUNT = 20
+K_COUNT = 23
 
 _lock = threading.Lock()
 _lib = None
@@ -168,6 +169,13 @@ def load():
         lib.gms_knn_workspace_bytes.argtypes = [C.c_int32]
         lib.gms_knn_mean_dist2.restype = C.c_int32
         lib.gms_knn_mean_dist2.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.gms_bind_workspace_bytes.restype = C.c_size_t
+        lib.gms_bind_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+        lib.gms_bind_pseudomesh.restype = C.c_int32
+        lib.gms_bind_pseudomesh.argtypes = [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.gms_bind_apply.restype = C.c_int32
+        lib.gms_bind_apply.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.gms_l1_ssim_partials.restype = C.c_size_t
         lib.gms_l1_ssim_partials.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         lib.gms_l1_ssim_forward.restype = C.c_int32

@@ -263,3 +263,57 @@ class GraphedPointsAnimation(GraphedAnimation):
 
     def _num_gaussians(self) -> int:
         return int(self.static_tri.shape[0])
+
+
+# ---------------------------------------------------------------------------------------------- gs_points driven by a guide mesh
+@torch.no_grad()
+def render_points_mesh_animated(gaussians, views: Iterable, pipeline, background: torch.Tensor, binding, guide_faces: torch.Tensor,
+                                vertices_for_frame: Callable, out_dir: Optional[str] = None) -> List[torch.Tensor]:
+    """The gs_points loop with the pseudo-mesh bound to a guide mesh (games_hip.pseudomesh.bind_pseudomesh; the reference edits the
+    pseudo-mesh with scripts/edit_pseudomesh_based_on_estimated_mesh.py and renders the saved triangles): per view k,
+    `vertices_for_frame(k)` -> guide vertices [V,3], `deform_pseudomesh` -> pseudo-triangles, `render_points_animated`.  `guide_faces`:
+    the guide's faces [F,3] (converted to int32 on the device once).  Returns the frames (device tensors [3,H,W])."""
+    from .pseudomesh import deform_pseudomesh, guide_faces_int32
+    faces = guide_faces_int32(guide_faces, binding.face_idx.device)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+    frames = []
+    for k, view in enumerate(views):
+        triangles = deform_pseudomesh(binding, vertices_for_frame(k), faces)
+        img = render_points_animated(triangles, view, gaussians, pipeline, background)["render"]
+        frames.append(img)
+        if out_dir:
+            _save(img, os.path.join(out_dir, f"{k:05d}.png"))
+    return frames
+
+
+class GraphedBoundAnimation(GraphedPointsAnimation):
+    """GraphedPointsAnimation whose static input is the guide's vertices [V,3] instead of the pseudo-triangles [P,3,3]: the captured
+    frame is `bind_apply` into a static triangle buffer followed by the points frame, so a replay copies 12 B per guide vertex instead
+    of 36 B per Gaussian.  Overflow / re-capture behaviour is GraphedAnimation's.
+
+        binding = bind_pseudomesh(triangles, guide.vertices, guide.faces)
+        anim = GraphedBoundAnimation(gaussians, view, pipeline, background, binding, guide_faces)
+        for k in range(n_frames):
+            img = anim.render(edited_vertices[k], check=True)
+    """
+
+    def __init__(self, gaussians, view, pipeline, background: torch.Tensor, binding, guide_faces: torch.Tensor, warmup: int = 3):
+        super().__init__(gaussians, view, pipeline, background, warmup)
+        from .pseudomesh import deform_pseudomesh, guide_faces_int32
+        self._deform = deform_pseudomesh
+        self.binding = binding
+        self.faces = guide_faces_int32(guide_faces, binding.face_idx.device)
+        self.triangles = torch.empty(binding.P, 3, 3, dtype=torch.float32, device=binding.face_idx.device)     # static: rewritten by every frame
+
+    def _frame(self, vertices: torch.Tensor) -> dict:
+        return render_points_animated(self._deform(self.binding, vertices, self.faces, out=self.triangles), self.view, self.pc, self.pipe, self.bg)
+
+    def _num_gaussians(self) -> int:
+        return self.binding.P
+
+    def render(self, vertices: torch.Tensor, check: bool = True) -> torch.Tensor:
+        """The frame for guide `vertices` [V,3] float32 (GraphedAnimation.render with the vertices as the graph's static input)."""
+        if vertices.dtype != torch.float32 or not vertices.is_contiguous():
+            vertices = vertices.float().contiguous()
+        return super().render(vertices, check)

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define GMS_ABI_VERSION 9   /* 3: GmsRasterBackwardArgs gained factor_campos_row + sh_factor_mode (explicit mode flag), GMS_K_COUNT 17;
+#define GMS_ABI_VERSION 10  /* 3: GmsRasterBackwardArgs gained factor_campos_row + sh_factor_mode (explicit mode flag), GMS_K_COUNT 17;
                              4: GmsRasterForwardArgs gained no_host_wait (stream-capturable forward), gms_image_counts_offset;
                              5: GmsRasterForwardArgs.mesh (forward-only frame straight from a mesh);
                              6: GmsRasterForwardArgs.mesh_out_* (the fused frame exports what the backward needs: training frames too);
@@ -54,7 +54,8 @@ extern "C" {
                                 START OF THE BACKWARD instead of inside the forward);
                              8: GmsRasterBackwardArgs.mesh + mesh_dL_* (the mesh backward inside preprocess_bwd for frames rendered from a mesh);
                              9: GmsPointsArgs + gms_points_* (pseudo-triangle -> Gaussian), GmsRasterForwardArgs.points (forward-only frame
-                                straight from pseudo-triangles), GMS_K_POINTS_* / GMS_K_COUNT 20 */
+                                straight from pseudo-triangles), GMS_K_POINTS_* / GMS_K_COUNT 20;
+                             10: gms_bind_* (pseudo-mesh bound to a guide mesh), GMS_K_BIND_* / GMS_K_COUNT 23 */
 
 /* error codes (negative return values) */
 #define GMS_OK 0
@@ -353,6 +354,29 @@ size_t gms_knn_workspace_bytes(int32_t N);
 int32_t gms_knn_mean_dist2(int32_t N, const float *points /* [N,3] */, float *out /* [N] */, void *workspace,
                            size_t workspace_bytes, void *stream);
 
+/* ---- pseudo-mesh bound to a guide mesh (scripts/edit_pseudomesh_based_on_estimated_mesh.py) ----
+ * gms_bind_pseudomesh, once: every pseudo-triangle p is attached to the guide face whose centroid is nearest to its own, and its
+ * three corners w_k are expressed in that face's frame (unit normal n of (v2 - v1) x (v3 - v1), unit edges e1 = v2 - v1 and
+ * e2 = v3 - v1; origin v1):  [n | e1 | e2] alpha[p,k,:] = w_k - v1.
+ *   - centroid = ((a + b) + c) / 3.0f per component; squared distance (dx*dx + dy*dy) + dz*dz with d = face centroid - query
+ *     centroid, all in float32 without contraction; face_idx[p] = the lexicographic minimum of (squared distance, face index).
+ *     The search is exact for queries anywhere (a uniform grid over the face centroids, walked in shells).
+ *   - *degenerate_count_out (HOST int32, or NULL: not read back) = the bindings whose face has a zero or non-finite area or edge:
+ *     their alpha is not usable.  Reading it back is the call's one stream synchronisation.
+ * gms_bind_apply, per pose: triangles_out[p,k,:] = ((alpha_k0 n' + alpha_k1 e1') + alpha_k2 e2') + v1' on the frame of the same
+ * face of `guide_vertices` (the edited guide).  Launches only: no allocation, no host wait; no atomics (bit-identical run to run).
+ * guide_faces holds int32 vertex indices; an index outside [0, V) is the caller's error (not checked).  P = 0 succeeds and writes
+ * nothing; P > 0 with F = 0 is GMS_ERR_INVALID_ARGUMENT.  `workspace`: caller-owned device scratch of at least
+ * gms_bind_workspace_bytes(P, F) bytes. */
+size_t gms_bind_workspace_bytes(int64_t P, int32_t F);
+int32_t gms_bind_pseudomesh(int64_t P, const float *triangles /* [P,3,3] */, int32_t V, const float *guide_vertices /* [V,3] */,
+                            int32_t F, const int32_t *guide_faces /* [F,3] */, int32_t *face_idx_out /* [P] */,
+                            float *alpha_out /* [P,3,3] */, int32_t *degenerate_count_out /* HOST, or NULL */, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int32_t gms_bind_apply(int64_t P, const int32_t *face_idx /* [P] */, const float *alpha /* [P,3,3] */, int32_t V,
+                       const float *guide_vertices /* [V,3] */, int32_t F, const int32_t *guide_faces /* [F,3] */,
+                       float *triangles_out /* [P,3,3] */, void *stream);
+
 /* ---- fused L1 + SSIM photometric loss ---------------------------------
  * Replaces train.py:106-107 built on utils/loss_utils.py:17-18 (l1_loss) and :33-63 (ssim: 11x11 Gaussian window,
  * sigma 1.5, zero padding, C1=0.01^2, C2=0.03^2, mean over every pixel of every plane):
@@ -418,7 +442,10 @@ int32_t gms_adam_step(const GmsAdamTensor *tensors /* HOST array */, int32_t cou
 #define GMS_K_POINTS_FWD 17
 #define GMS_K_POINTS_BWD 18
 #define GMS_K_POINTS_VERTS 19
-#define GMS_K_COUNT 20
+#define GMS_K_BIND_NEAREST 20
+#define GMS_K_BIND_SOLVE 21
+#define GMS_K_BIND_APPLY 22
+#define GMS_K_COUNT 23
 void gms_profile_enable(int32_t on);
 void gms_profile_reset(void);
 int32_t gms_profile_read(int32_t kernel_id, double *total_ms, int64_t *launches);
