@@ -1005,6 +1005,201 @@ Tensor bind_apply(const Tensor &face_idx, const Tensor &alpha, const Tensor &gui
     return out;
 }
 
+// ---------------------------------------------------------------------------------------------- FLAME layer (csrc/flame.hip)
+// tables = the packed model of games_hip.flame.FlameData.to(device): [v_template [V,3], shapedirs [L,V*3], posedirs [(J-1)*9,V*3],
+// lbs_weights [V,J], joints_template [J,3], joints_shapedirs [L,J*3]].  The joint rotations come as tensors of 3 n floats each with the
+// n joints they drive (FLAME: pose_params -> joints 0 and 2, neck_pose -> 1, eye_pose -> 3 and 4), so no full_pose is assembled.
+struct FlameInputs {
+    std::vector<Tensor> tables;
+    std::vector<int64_t> parents;
+    std::vector<Tensor> rots;
+    std::vector<int64_t> rot_joints;          // the joints of rots[0], then of rots[1], ...
+    Tensor shape, expression, transl, enlargement;
+    double enlargement_scalar = 1.0;
+    bool swap = false;
+};
+
+// checks and normalises `in` (float32, contiguous) and points the C structs at it
+void flame_fill(FlameInputs &in, GmsFlameModel &m, GmsFlameParams &p)
+{
+    TORCH_CHECK(in.tables.size() == 6, "flame: six model tables expected");
+    for (const Tensor &t : in.tables) {
+        require_gpu(t);
+        TORCH_CHECK(t.defined() && t.scalar_type() == torch::kFloat && t.is_contiguous() && t.device() == in.tables[0].device(),
+                    "flame: the model tables must be contiguous float32 tensors on one GPU (FlameData.to(device) packs them)");
+    }
+    const auto dev = in.tables[0].device();
+    const int64_t V = in.tables[0].size(0), J = (int64_t)in.parents.size(), L = in.tables[1].size(0);
+    TORCH_CHECK(J >= 2 && J <= GMS_FLAME_MAX_JOINTS, "flame: ", J, " joints (2 .. ", GMS_FLAME_MAX_JOINTS, " are supported)");
+    TORCH_CHECK(V <= INT32_MAX / 3 && in.tables[0].numel() == V * 3 && in.tables[1].numel() == L * V * 3 && in.tables[2].numel() == (J - 1) * 9 * V * 3 &&
+                in.tables[3].numel() == V * J && in.tables[4].numel() == J * 3 && in.tables[5].numel() == L * J * 3, "flame: model table sizes do not fit together");
+    m = GmsFlameModel{};
+    m.V = (int32_t)V; m.J = (int32_t)J; m.L = (int32_t)L;
+    for (int64_t j = 0; j < J; j++) m.parents[j] = (int32_t)in.parents[j];
+    m.v_template = cf(in.tables[0]); m.shapedirs = cf(in.tables[1]); m.posedirs = cf(in.tables[2]);
+    m.lbs_weights = cf(in.tables[3]); m.joints_template = cf(in.tables[4]); m.joints_shapedirs = cf(in.tables[5]);
+    auto param = [&](Tensor &t, int64_t n, const char *name) {
+        if (!t.defined()) return;
+        require_gpu(t);
+        TORCH_CHECK(t.scalar_type() == torch::kFloat, "flame: ", name, " must be a float32 tensor (the kernels and their gradients are float32), got ",
+                    t.scalar_type());
+        t = f32c(t);
+        TORCH_CHECK(t.numel() == n && (n == 0 || t.device() == dev), "flame: ", name, " must hold ", n, " values on the model's device (batch 1 only)");
+    };
+    TORCH_CHECK(in.shape.defined() && in.expression.defined(), "flame: shape and expression parameters are required");
+    TORCH_CHECK(in.shape.numel() + in.expression.numel() == L, "flame: the model is packed for ", L, " shape + expression columns, got ",
+                in.shape.numel(), " + ", in.expression.numel(), " (batch 1 only)");
+    param(in.shape, in.shape.numel(), "shape_params");
+    param(in.expression, in.expression.numel(), "expression_params");
+    param(in.transl, 3, "transl");
+    param(in.enlargement, V * 3, "enlargement");
+    p = GmsFlameParams{};
+    p.shape = cf(in.shape); p.expression = cf(in.expression);
+    p.n_shape = (int32_t)in.shape.numel(); p.n_expression = (int32_t)in.expression.numel();
+    size_t k = 0;
+    for (Tensor &r : in.rots) {
+        TORCH_CHECK(r.defined() && r.numel() % 3 == 0, "flame: a rotation tensor holds 3 values per joint");
+        param(r, r.numel(), "pose");
+        for (int64_t q = 0; q < r.numel() / 3; q++, k++) {
+            TORCH_CHECK(k < in.rot_joints.size() && in.rot_joints[k] >= 0 && in.rot_joints[k] < J && !p.joint_rot[in.rot_joints[k]],
+                        "flame: every rotation triple needs one joint of its own in [0, J)");
+            p.joint_rot[in.rot_joints[k]] = cf(r) + 3 * q;
+        }
+    }
+    TORCH_CHECK(k == in.rot_joints.size(), "flame: ", in.rot_joints.size(), " joints named for ", k, " rotation triples");
+    p.transl = cf(in.transl);
+    p.enlargement = cf(in.enlargement);
+    p.enlargement_scalar = (float)in.enlargement_scalar;
+    p.swap = in.swap ? 1 : 0;
+}
+
+Tensor flame_run_forward(FlameInputs &in, Tensor *saved)
+{
+    GmsFlameModel m;
+    GmsFlameParams p;
+    flame_fill(in, m, p);
+    const auto dev = in.tables[0].device();
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+    auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
+    Tensor out = torch::empty({(int64_t)m.V, 3}, fopt);
+    if (saved) *saved = torch::empty({(int64_t)GMS_FLAME_SAVED_FLOATS(m.V)}, fopt);
+    check_rc(gms_flame_forward(&m, &p, mf(out), saved ? mf(*saved) : nullptr, stream_of(dev)), "gms_flame_forward");
+    return out;
+}
+
+class FlameFn : public torch::autograd::Function<FlameFn> {
+public:
+    // differentiable inputs, in this order: rots..., shape, expression, transl, enlargement
+    // (an absent tensor is an empty optional: it gets no edge in the graph)
+    static Tensor forward(AutogradContext *ctx, at::TensorList rots, Tensor shape, Tensor expression, std::optional<Tensor> transl,
+                          std::optional<Tensor> enlargement, const FlameInputs *st)
+    {
+        ctx->set_materialize_grads(false);
+        FlameInputs in = *st;
+        in.rots.assign(rots.begin(), rots.end());
+        in.shape = shape; in.expression = expression;
+        in.transl = transl ? *transl : Tensor(); in.enlargement = enlargement ? *enlargement : Tensor();
+        Tensor saved;
+        Tensor out = flame_run_forward(in, &saved);
+        variable_list keep(in.rots.begin(), in.rots.end());
+        auto fopt = out.options();
+        keep.push_back(in.shape); keep.push_back(in.expression);
+        keep.push_back(in.transl.defined() ? in.transl : torch::empty({0}, fopt));
+        keep.push_back(in.enlargement.defined() ? in.enlargement : torch::empty({0}, fopt));
+        keep.push_back(saved);
+        for (const Tensor &t : in.tables) keep.push_back(t);
+        ctx->save_for_backward(keep);
+        ctx->saved_data["n_rots"] = (int64_t)in.rots.size();
+        ctx->saved_data["parents"] = in.parents;
+        ctx->saved_data["rot_joints"] = in.rot_joints;
+        ctx->saved_data["enlargement_scalar"] = in.enlargement_scalar;
+        ctx->saved_data["swap"] = in.swap;
+        return out;
+    }
+
+    static variable_list backward(AutogradContext *ctx, variable_list g)
+    {
+        auto s = ctx->get_saved_variables();
+        const size_t nr = (size_t)ctx->saved_data["n_rots"].toInt();
+        variable_list grads(nr + 5);                       // (+ the FlameInputs pointer)
+        if (!g[0].defined()) return grads;
+        FlameInputs in;
+        in.rots.assign(s.begin(), s.begin() + nr);
+        in.shape = s[nr]; in.expression = s[nr + 1];
+        if (s[nr + 2].numel()) in.transl = s[nr + 2];
+        if (s[nr + 3].numel()) in.enlargement = s[nr + 3];
+        const Tensor &saved = s[nr + 4];
+        in.tables.assign(s.begin() + nr + 5, s.end());
+        in.parents = ctx->saved_data["parents"].toIntVector();
+        in.rot_joints = ctx->saved_data["rot_joints"].toIntVector();
+        in.enlargement_scalar = ctx->saved_data["enlargement_scalar"].toDouble();
+        in.swap = ctx->saved_data["swap"].toBool();
+        GmsFlameModel m;
+        GmsFlameParams p;
+        flame_fill(in, m, p);
+        const auto dev = in.tables[0].device();
+        c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+        Tensor gv = f32c(g[0]);
+        TORCH_CHECK(gv.numel() == (int64_t)m.V * 3 && gv.device() == dev, "flame backward: gradient of the vertices must be [V,3] on the model's device");
+        GmsFlameGrads gr{};
+        size_t k = 0;
+        for (size_t i = 0; i < nr; i++) {
+            const int64_t n = in.rots[i].numel() / 3;
+            if (ctx->needs_input_grad(i)) {
+                grads[i] = torch::empty_like(in.rots[i]);
+                for (int64_t q = 0; q < n; q++) gr.d_joint_rot[in.rot_joints[k + q]] = mf(grads[i]) + 3 * q;
+            }
+            k += (size_t)n;
+        }
+        if (ctx->needs_input_grad(nr) && in.shape.numel()) { grads[nr] = torch::empty_like(in.shape); gr.d_shape = mf(grads[nr]); }
+        if (ctx->needs_input_grad(nr + 1) && in.expression.numel()) { grads[nr + 1] = torch::empty_like(in.expression); gr.d_expression = mf(grads[nr + 1]); }
+        size_t edge = nr + 2;                              // the graph's edges count the tensors that were there
+        if (in.transl.defined() && ctx->needs_input_grad(edge++)) { grads[nr + 2] = torch::empty_like(in.transl); gr.d_transl = mf(grads[nr + 2]); }
+        if (in.enlargement.defined() && ctx->needs_input_grad(edge++)) { grads[nr + 3] = torch::empty_like(in.enlargement); gr.d_enlargement = mf(grads[nr + 3]); }
+        const size_t bytes = gms_flame_workspace_bytes(m.V, m.J, m.L);
+        Tensor work = torch::empty({(int64_t)bytes}, torch::TensorOptions().dtype(torch::kUInt8).device(dev));
+        check_rc(gms_flame_backward(&m, &p, cf(saved), cf(gv), &gr, work.data_ptr(), bytes, stream_of(dev)), "gms_flame_backward");
+        return grads;
+    }
+};
+
+FlameInputs flame_inputs(const std::vector<Tensor> &tables, const std::vector<int64_t> &parents, const std::vector<Tensor> &rots,
+                         const std::vector<std::vector<int64_t>> &rot_joints, const Tensor &shape, const Tensor &expression,
+                         const std::optional<Tensor> &transl, const std::optional<Tensor> &enlargement, double enlargement_scalar, bool swap)
+{
+    TORCH_CHECK(rots.size() == rot_joints.size(), "flame: one list of joints per rotation tensor");
+    FlameInputs in;
+    in.tables = tables; in.parents = parents; in.rots = rots;
+    for (size_t i = 0; i < rots.size(); i++) {
+        TORCH_CHECK(rots[i].defined() && (int64_t)rot_joints[i].size() * 3 == rots[i].numel(), "flame: a rotation tensor holds 3 values for each of its joints (batch 1 only)");
+        in.rot_joints.insert(in.rot_joints.end(), rot_joints[i].begin(), rot_joints[i].end());
+    }
+    in.shape = shape; in.expression = expression;
+    if (transl) in.transl = *transl;
+    if (enlargement) in.enlargement = *enlargement;
+    in.enlargement_scalar = enlargement_scalar; in.swap = swap;
+    return in;
+}
+
+// steps 1-8 of DESIGN.md section 12 as ONE autograd node: -> vertices [V,3]
+Tensor flame_vertices(const std::vector<Tensor> &tables, const std::vector<int64_t> &parents, const std::vector<Tensor> &rots,
+                      const std::vector<std::vector<int64_t>> &rot_joints, const Tensor &shape, const Tensor &expression,
+                      const std::optional<Tensor> &transl, const std::optional<Tensor> &enlargement, double enlargement_scalar, bool swap)
+{
+    FlameInputs in = flame_inputs(tables, parents, rots, rot_joints, shape, expression, transl, enlargement, enlargement_scalar, swap);
+    auto opt = [](const Tensor &t) { return t.defined() ? std::optional<Tensor>(t) : std::nullopt; };
+    return FlameFn::apply(at::TensorList(in.rots), in.shape, in.expression, opt(in.transl), opt(in.enlargement), (const FlameInputs *)&in);
+}
+
+// the same without a graph (one launch, nothing saved)
+Tensor flame_forward(const std::vector<Tensor> &tables, const std::vector<int64_t> &parents, const std::vector<Tensor> &rots,
+                     const std::vector<std::vector<int64_t>> &rot_joints, const Tensor &shape, const Tensor &expression,
+                     const std::optional<Tensor> &transl, const std::optional<Tensor> &enlargement, double enlargement_scalar, bool swap)
+{
+    FlameInputs in = flame_inputs(tables, parents, rots, rot_joints, shape, expression, transl, enlargement, enlargement_scalar, swap);
+    return flame_run_forward(in, nullptr);
+}
+
 // ---------------------------------------------------------------------------------------------- multi-tensor Adam
 void adam_step(const std::vector<Tensor> &params, const std::vector<Tensor> &grads, const std::vector<Tensor> &exp_avg,
                const std::vector<Tensor> &exp_avg_sq, const std::vector<double> &lrs, const std::vector<int64_t> &steps, double beta1,
@@ -1050,6 +1245,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("bind_pseudomesh", &bind_pseudomesh, "bind pseudo-triangles [P,3,3] to the nearest faces of a guide mesh: (face_idx int32 [P], alpha [P,3,3], n_degenerate)", nogil());
     m.def("bind_apply", &bind_apply, "pseudo-triangles [P,3,3] of a binding on (edited) guide vertices; launches only", py::arg("face_idx"), py::arg("alpha"),
           py::arg("guide_vertices"), py::arg("guide_faces"), py::arg("out") = py::none(), nogil());
+    m.def("flame_vertices", &flame_vertices, "differentiable FLAME layer (+ axis swap and enlargement): vertices [V,3], one autograd node", py::arg("tables"),
+          py::arg("parents"), py::arg("rots"), py::arg("rot_joints"), py::arg("shape"), py::arg("expression"), py::arg("transl") = py::none(),
+          py::arg("enlargement") = py::none(), py::arg("enlargement_scalar") = 1.0, py::arg("swap") = false, nogil());
+    m.def("flame_forward", &flame_forward, "the FLAME layer without a graph: one launch", py::arg("tables"), py::arg("parents"), py::arg("rots"),
+          py::arg("rot_joints"), py::arg("shape"), py::arg("expression"), py::arg("transl") = py::none(), py::arg("enlargement") = py::none(),
+          py::arg("enlargement_scalar") = 1.0, py::arg("swap") = false, nogil());
     m.def("render_mesh", &render_mesh, "differentiable frame straight from a mesh: [image, radii, invdepth, xyz, scaling_act, rotation_unit, opacity_act]", nogil());
     m.def("l1_ssim", &l1_ssim, "differentiable w_l1 * L1 + w_ssim * SSIM + bias; returns (value [0-dim], [l1, ssim])", nogil());
     m.def("adam_step", &adam_step, nogil());

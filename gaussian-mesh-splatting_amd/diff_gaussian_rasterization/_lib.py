@@ -104,6 +104,40 @@ class AdamTensor(C.Structure):
     ]
 
 
+FLAME_MAX_JOINTS, FLAME_MAX_COLUMNS = 8, 512
+
+
+class FlameModel(C.Structure):
+    """GmsFlameModel (include/gmsplat.h): the packed FLAME constants."""
+    _fields_ = [
+        ("V", C.c_int32), ("J", C.c_int32), ("L", C.c_int32), ("parents", C.c_int32 * FLAME_MAX_JOINTS),
+        ("v_template", C.c_void_p), ("shapedirs", C.c_void_p), ("posedirs", C.c_void_p), ("lbs_weights", C.c_void_p),
+        ("joints_template", C.c_void_p), ("joints_shapedirs", C.c_void_p),
+    ]
+
+
+class FlameParams(C.Structure):
+    """GmsFlameParams."""
+    _fields_ = [
+        ("shape", C.c_void_p), ("expression", C.c_void_p), ("n_shape", C.c_int32), ("n_expression", C.c_int32),
+        ("joint_rot", C.c_void_p * FLAME_MAX_JOINTS), ("transl", C.c_void_p), ("enlargement", C.c_void_p),
+        ("enlargement_scalar", C.c_float), ("swap", C.c_int32),
+    ]
+
+
+class FlameGrads(C.Structure):
+    """GmsFlameGrads: NULL = not wanted."""
+    _fields_ = [
+        ("d_shape", C.c_void_p), ("d_expression", C.c_void_p), ("d_joint_rot", C.c_void_p * FLAME_MAX_JOINTS),
+        ("d_transl", C.c_void_p), ("d_enlargement", C.c_void_p),
+    ]
+
+
+def flame_saved_floats(V: int) -> int:
+    """GMS_FLAME_SAVED_FLOATS."""
+    return 3 * int(V) + 24 * FLAME_MAX_JOINTS
+
+
 # every symbol include/gmsplat.h declares
 EXPORTS = (
     "gms_rasterize_forward", "gms_rasterize_backward", "gms_mark_visible", "gms_mesh_to_gaussians_forward",
@@ -116,6 +150,7 @@ EXPORTS = (
     "gms_set_upstream_scale_mod_grad", "gms_get_upstream_scale_mod_grad", "gms_profile_event_overhead_us",
     "gms_points_prepare_vertices", "gms_points_to_gaussians_forward", "gms_points_to_gaussians_backward",
     "gms_bind_workspace_bytes", "gms_bind_pseudomesh", "gms_bind_apply",
+    "gms_flame_workspace_bytes", "gms_flame_forward", "gms_flame_backward",
 )
 K_COUNT = 23
 
@@ -176,6 +211,13 @@ def load():
                                             C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]
         lib.gms_bind_apply.restype = C.c_int32
         lib.gms_bind_apply.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gms_flame_workspace_bytes.restype = C.c_size_t
+        lib.gms_flame_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        lib.gms_flame_forward.restype = C.c_int32
+        lib.gms_flame_forward.argtypes = [C.POINTER(FlameModel), C.POINTER(FlameParams), C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gms_flame_backward.restype = C.c_int32
+        lib.gms_flame_backward.argtypes = [C.POINTER(FlameModel), C.POINTER(FlameParams), C.c_void_p, C.c_void_p, C.POINTER(FlameGrads), C.c_void_p,
+                                           C.c_size_t, C.c_void_p]
         lib.gms_l1_ssim_partials.restype = C.c_size_t
         lib.gms_l1_ssim_partials.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         lib.gms_l1_ssim_forward.restype = C.c_int32

@@ -25,6 +25,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
+from . import flame as _flame
 from .mesh_op import mesh_to_gaussians, triangles_to_gaussians
 from .points_op import points_prepare_vertices, points_to_gaussians
 
@@ -242,18 +243,24 @@ class HipMeshMixin(_HipGetters):
 
 class HipFlameMixin(HipMeshMixin):
     """GaussianFlameModel: softmax barycentric weights (gaussian_flame_model.py:195), vertices produced by the host
-    class's FLAME layer (:196-207, python/torch: linear blend skinning is outside the hot path, SURVEY 8 out-of-scope),
-    scale parameter named `_scales` (:42,:82).  One launch derives alpha / xyz / scaling / rotation from them."""
+    class's FLAME layer (:196-207), scale parameter named `_scales` (:42,:82).  With a `games_hip.flame.HipFlameLayer` as
+    `point_cloud.flame_model` the layer, the transform function and the enlargement are one autograd node on csrc/flame.hip
+    (one launch forward, two backward); any other layer (the reference's smplx one, the synthetic stand-in) runs as it is, in
+    python/torch.  One more launch derives alpha / xyz / scaling / rotation from the vertices."""
 
     alpha_mode = "softmax"
     _hip_scale_attr = "_scales"
 
     def _hip_flame_vertices(self):
         pc = self.point_cloud
+        fn = pc.transform_vertices_function
+        if isinstance(pc.flame_model, _flame.HipFlameLayer) and (fn is _flame.transform_vertices_function or fn is _squeeze_and_enlarge):
+            return pc.flame_model.vertices(self._flame_shape, self._flame_exp, self._flame_pose, self._flame_neck_pose, self._flame_trans,
+                                           enlargement=self._vertices_enlargement, swap=fn is _flame.transform_vertices_function)
         vertices, _ = pc.flame_model(shape_params=self._flame_shape, expression_params=self._flame_exp,
                                      pose_params=self._flame_pose, neck_pose=self._flame_neck_pose,
                                      transl=self._flame_trans)
-        return pc.transform_vertices_function(vertices, self._vertices_enlargement)
+        return fn(vertices, self._vertices_enlargement)
 
     def update_alpha(self):
         self.vertices = self._hip_flame_vertices()
@@ -582,15 +589,23 @@ class HipGaussianFlameModel(HipFlameMixin, _StandaloneBase):
     vertex animation + on-device re-derivation of the face-local rotation / scale."""
 
     @classmethod
-    def from_scene(cls, scene, device="cuda", enlargement=1.0):
+    def from_scene(cls, scene, device="cuda", enlargement=1.0, flame=None):
+        """`flame`: a games_hip.flame.HipFlameLayer whose template is the scene's vertices (synthetic.flame_like_model(template=...))
+        replaces the synthetic generator; the parameter shapes then come from the layer and `_flame_neck_pose` is trained too."""
         m = cls(3)
         m.active_sh_degree = scene.active_sh_degree
         par = lambda t: nn.Parameter(t.to(device).float().contiguous())
         template = scene.vertices.to(device).float()
-        m.point_cloud = _FlameCloud(_SyntheticFlameLayer(template), _squeeze_and_enlarge)
+        if flame is None:
+            m.point_cloud = _FlameCloud(_SyntheticFlameLayer(template), _squeeze_and_enlarge)
+        else:
+            if tuple(flame.v_template.shape) != tuple(template.shape):
+                raise ValueError("from_scene: the FLAME layer's template must have the scene's vertices")
+            m.point_cloud = _FlameCloud(flame.to(device), _squeeze_and_enlarge)
+            m._hip_flame_layer = True
         m.faces = scene.faces.to(device)
-        m._flame_shape = par(torch.zeros(1, 4))
-        m._flame_exp = par(torch.zeros(1, 4))
+        m._flame_shape = par(torch.zeros(1, 4 if flame is None else flame.n_shape))
+        m._flame_exp = par(torch.zeros(1, 4 if flame is None else flame.n_expr))
         m._flame_pose = par(torch.zeros(1, 6))
         m._flame_neck_pose = par(torch.zeros(1, 3))
         m._flame_trans = par(torch.zeros(1, 3))
@@ -605,7 +620,8 @@ class HipGaussianFlameModel(HipFlameMixin, _StandaloneBase):
         return m
 
     def parameters(self):
-        return [self._flame_exp, self._flame_pose, self._flame_trans, self._vertices_enlargement, self._alpha,
+        neck = [self._flame_neck_pose] if getattr(self, "_hip_flame_layer", False) else []
+        return [self._flame_exp, self._flame_pose, *neck, self._flame_trans, self._vertices_enlargement, self._alpha,
                 self._features_dc, self._features_rest, self._opacity, self._scales]
 
     def training_setup(self, flame_shape_lr=0.01, flame_exp_lr=0.001, flame_pose_lr=0.001, flame_neck_pose_lr=0.001,

@@ -271,3 +271,38 @@ def random_scene(P: int, seed: int = 0, extent: float = 1.0, scale_lo: float = 0
 def upstream_grad(image: torch.Tensor) -> torch.Tensor:
     """Deterministic dense dL/dcolor used for fwd+bwd timing and parity: (image - 0.5)/(3HW)."""
     return (image - 0.5) / image.numel()
+
+
+# --------------------------------------------------------------------------- a FLAME-shaped model (the licensed file is not shipped)
+def flame_like_model(V: int = 5023, n_shape_full: int = 300, n_expr_full: int = 100, parents=(-1, 0, 1, 1, 1), seed: int = 0, template=None):
+    """A synthetic model with the shapes of FLAME's (games_hip.flame.FlameData): smooth skinning weights (a softmax over the
+    distances to the joints' centres: rows sum to 1, several joints per vertex), regressor rows that sum to 1, shapedirs and
+    posedirs ~ N(0, 0.01).  `template`: vertices [V,3], (vertices, faces), or an object with `.vertices` / `.faces` (a synthetic
+    scene); its faces are kept, otherwise the faces are the strip (i, i+1, i+2)."""
+    from .flame import FlameData
+    rng = np.random.default_rng(seed)
+    faces = None
+    if template is not None:
+        if isinstance(template, (tuple, list)):
+            template, faces = template
+        elif hasattr(template, "vertices"):
+            template, faces = template.vertices, getattr(template, "faces", None)
+        vt = np.asarray(template.detach().cpu() if torch.is_tensor(template) else template, dtype=np.float64).reshape(-1, 3)
+        V = vt.shape[0]
+    else:
+        d = rng.normal(size=(V, 3))
+        vt = d / np.linalg.norm(d, axis=1, keepdims=True) * (1.0 + 0.1 * rng.normal(size=(V, 1))) * 0.1
+    if faces is None:
+        faces = np.stack([np.arange(max(V - 2, 0)), np.arange(max(V - 2, 0)) + 1, np.arange(max(V - 2, 0)) + 2], axis=1)
+    faces = np.asarray(faces.detach().cpu() if torch.is_tensor(faces) else faces, dtype=np.int64).reshape(-1, 3)
+    J = len(parents)
+    centres = vt[rng.integers(0, V, J)] + 0.05 * vt.std() * rng.normal(size=(J, 3))
+    d2 = ((vt[:, None, :] - centres[None]) ** 2).sum(-1)                               # [V,J]
+    sigma2 = max(float(d2.mean()), 1e-12)
+    w = np.exp(-(d2 - d2.min(axis=1, keepdims=True)) / (0.5 * sigma2))
+    w /= w.sum(axis=1, keepdims=True)
+    jr = np.exp(-(d2.T - d2.T.min(axis=1, keepdims=True)) / (0.1 * sigma2)) * rng.uniform(0.5, 1.0, (J, V))
+    jr /= jr.sum(axis=1, keepdims=True)
+    shapedirs = 0.01 * rng.normal(size=(V, 3, n_shape_full + n_expr_full))
+    posedirs = 0.01 * rng.normal(size=((J - 1) * 9, V * 3))
+    return FlameData.from_arrays(vt, shapedirs, posedirs, jr, np.asarray(parents), w, faces, n_shape_full=n_shape_full)

@@ -417,6 +417,50 @@ typedef struct GmsAdamTensor {
 int32_t gms_adam_step(const GmsAdamTensor *tensors /* HOST array */, int32_t count, double beta1, double beta2, double eps,
                       void *stream);
 
+/* ---- FLAME layer: blend shapes, joint regression, Rodrigues, pose blend shapes, kinematic chain, linear blend skinning ------
+ * (csrc/flame.hip; DESIGN.md section 12 states the arithmetic).  Replaces what `GaussianFlameModel.update_alpha`
+ * (games/flame_splatting/scene/gaussian_flame_model.py:196-207) reaches through games/flame_splatting/FLAME/FLAME.py, plus
+ * `transform_vertices_function` (games/flame_splatting/scene/dataset_readers.py:40-45) and the multiply by the vertex enlargement.
+ * Batch 1.  The forward is one launch, the backward two; both only launch (no allocation, no synchronisation: capturable), every
+ * output is fully overwritten and the gradients are bit-identical from call to call (no float atomics).  Additive to ABI 10: no
+ * existing layout changes; these kernels have no gms_profile_* slot. */
+#define GMS_FLAME_MAX_JOINTS 8
+#define GMS_FLAME_MAX_COLUMNS 512
+typedef struct GmsFlameModel {
+    int32_t V, J, L;                         /* vertices, joints (2 .. GMS_FLAME_MAX_JOINTS), packed blend-shape columns (<= GMS_FLAME_MAX_COLUMNS) */
+    int32_t parents[GMS_FLAME_MAX_JOINTS];   /* parents[0] = -1, 0 <= parents[i] < i */
+    const float *v_template;                 /* device [V,3] */
+    const float *shapedirs;                  /* device [L, V*3]: the columns the parameters can reach, shape columns first */
+    const float *posedirs;                   /* device [(J-1)*9, V*3] */
+    const float *lbs_weights;                /* device [V,J] */
+    const float *joints_template;            /* device [J,3]     = J_regressor . v_template */
+    const float *joints_shapedirs;           /* device [L, J*3]  = J_regressor . shapedirs (both computed in float64, rounded once) */
+} GmsFlameModel;
+typedef struct GmsFlameParams {
+    const float *shape;                      /* device [n_shape] */
+    const float *expression;                 /* device [n_expression]; n_shape + n_expression == L */
+    int32_t n_shape, n_expression;
+    const float *joint_rot[GMS_FLAME_MAX_JOINTS];   /* device [3] axis-angle of joint j, or NULL = zeros */
+    const float *transl;                     /* device [3] or NULL */
+    const float *enlargement;                /* device [V,3] multiplied onto the output, or NULL: enlargement_scalar */
+    float enlargement_scalar;
+    int32_t swap;                            /* 1: output (x, -z, y) before the enlargement */
+} GmsFlameParams;
+typedef struct GmsFlameGrads {               /* device outputs; NULL = not wanted */
+    float *d_shape, *d_expression;           /* [n_shape], [n_expression] */
+    float *d_joint_rot[GMS_FLAME_MAX_JOINTS];/* [3] each */
+    float *d_transl;                         /* [3] */
+    float *d_enlargement;                    /* [V,3] (only with GmsFlameParams.enlargement) */
+} GmsFlameGrads;
+/* floats the forward stores for the backward: v_posed [V,3] and the joints' transforms */
+#define GMS_FLAME_SAVED_FLOATS(V) ((size_t)(V) * 3 + 24 * GMS_FLAME_MAX_JOINTS)
+size_t gms_flame_workspace_bytes(int32_t V, int32_t J, int32_t L);
+/* vertices_out device [V,3]; saved_out device [GMS_FLAME_SAVED_FLOATS(V)] or NULL (forward only). */
+int32_t gms_flame_forward(const GmsFlameModel *model, const GmsFlameParams *params, float *vertices_out, float *saved_out, void *stream);
+/* dL_dvertices device [V,3]; `saved` as written by the forward on the same model and parameters. */
+int32_t gms_flame_backward(const GmsFlameModel *model, const GmsFlameParams *params, const float *saved, const float *dL_dvertices,
+                           const GmsFlameGrads *grads, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- per-kernel timing (HIP events on the launch stream; off by default) ------------------
  * When enabled every kernel launch made by this library is bracketed by two hipEvents on the
  * caller's stream.  gms_profile_read() synchronises the recorded events and returns the summed
