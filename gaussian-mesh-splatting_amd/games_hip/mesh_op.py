@@ -161,13 +161,18 @@ def mesh_to_gaussians(vertices: torch.Tensor, faces: torch.Tensor, _alpha: torch
 _identity_faces = {}
 
 
+def identity_faces(device, F_: int) -> torch.Tensor:
+    """faces [F,3] = 0 .. 3F-1 of a mesh given as explicit triangles (vertices = triangles.reshape(3 F, 3)); built once per size."""
+    key = (device, F_)
+    if key not in _identity_faces:
+        _identity_faces[key] = torch.arange(3 * F_, device=device, dtype=torch.int64).reshape(F_, 3)
+    return _identity_faces[key]
+
+
 def triangles_to_gaussians(triangles: torch.Tensor, _alpha: torch.Tensor, _scale: torch.Tensor, alpha_mode: str = "relu",
                            fused_activations: bool = False):
     """Same op driven by explicit triangles [F,3,3] (the animated renderers replace `pc.triangles`
     per frame: renderer/gaussian_animated_renderer/__init__.py:61-73)."""
     F_ = int(triangles.shape[0])
-    key = (triangles.device, F_)
-    if key not in _identity_faces:
-        _identity_faces[key] = torch.arange(3 * F_, device=triangles.device, dtype=torch.int64).reshape(F_, 3)
-    return mesh_to_gaussians(triangles.reshape(3 * F_, 3), _identity_faces[key], _alpha, _scale, alpha_mode,
+    return mesh_to_gaussians(triangles.reshape(3 * F_, 3), identity_faces(triangles.device, F_), _alpha, _scale, alpha_mode,
                              fused_activations=fused_activations)

@@ -17,8 +17,8 @@ separately by `install_points()`.
 for bench.py / the GPU tests, where the reference tree is absent.
 
 Property getters fused into the op (scene/gaussian_model.py:95-115): get_scaling / get_rotation / get_opacity.
-Caches are validated against the identity AND autograd version of every tensor they were derived from, so editing
-`vertices`, `_scale`, `_alpha` or `_opacity` (an optimizer step, a checkpoint load) can never serve stale values.
+Everything a model derives lives in one `_Derived` record, each entry stamped with the identity AND autograd version of the tensors
+it came from, so editing `vertices`, `_scale`, `_alpha` or `_opacity` (an optimizer step, a checkpoint load) can never serve stale values.
 """
 from __future__ import annotations
 
@@ -31,85 +31,109 @@ from .points_op import points_prepare_vertices, points_to_gaussians
 
 
 class _Stamp:
-    """The tensors a cached value was derived from, with their in-place versions.  Holds the tensors themselves
-    (not their ids: an id can be reused once a tensor is freed), compared by identity + version."""
+    """A derived value with the tensors it came from and their in-place versions (the tensors themselves: an id can be reused once one is freed)."""
 
-    __slots__ = ("items",)
+    __slots__ = ("value", "items")
 
-    def __init__(self, *tensors):
-        self.items = tuple((t, t._version if torch.is_tensor(t) else -1) for t in tensors)
-
-    def __eq__(self, other):
-        return (isinstance(other, _Stamp) and len(self.items) == len(other.items)
-                and all(a is b and va == vb for (a, va), (b, vb) in zip(self.items, other.items)))
-
-    def __ne__(self, other):
-        return not self.__eq__(other)
-
-    __hash__ = None
+    def __init__(self, value, *sources):
+        self.value = value
+        self.items = tuple([(t, getattr(t, "_version", -1)) for t in sources])       # (-1: not a tensor, e.g. faces kept as an array)
 
 
-def _stamp(*tensors):
-    return _Stamp(*tensors)
+def _current(entry, *sources):
+    """The entry's value while `sources` are, by identity and version, the tensors it was derived from; else None.  The one place
+    that decides whether something derived earlier may still be served."""
+    if entry is None or len(sources) != len(entry.items):
+        return None
+    ok = all(t is a and getattr(t, "_version", -1) == v for t, (a, v) in zip(sources, entry.items))
+    return entry.value if ok else None
+
+
+class _Derived:
+    """What one model instance has derived from its mesh (`_HipGetters._hip`).  `pending` is a mark, `tri_external` a tensor somebody
+    assigned; every other entry is a `_Stamp`, read through `_current`."""
+
+    __slots__ = ("pending",         # hip_defer_k0: update_alpha() was deferred, the next differentiated render() derives the Gaussians
+                 "geometry",        # (scaling, rotation, scaling_act, rotation_unit) of the last op call        <- the op's inputs
+                 "activated",       # (scaling_act, rotation_unit) of the tensors assigned to _scaling / _rotation  <- those two
+                 "opacity_act",     # the kernel's sigmoid(_opacity)                                              <- _opacity
+                 "frame",           # (xyz, scaling_act, rotation_unit, opacity_act) of the last fused training frame <- inputs, _opacity
+                 "tri",             # vertices[faces], gathered on first access                                   <- vertices, faces
+                 "tri_external",    # `triangles` as a renderer / loader assigned it; wins over `tri` until the next update_alpha()
+                 "centre",          # HipPointsMixin: triangles[:, 0] as the points op returned it                <- the triangles
+                 "topology")        # HipMultiMeshMixin: (shapes, (faces, face_splat_offset, splat_face))         <- the faces
+
+    def __init__(self):
+        self.pending = False
+        self.geometry = self.activated = self.opacity_act = self.frame = None
+        self.tri = self.tri_external = self.centre = self.topology = None
 
 
 class _HipGetters:
     """get_scaling / get_rotation / get_opacity / get_features on the fused outputs; each falls back to the
     reference's formula when `_scaling` / `_rotation` / `_opacity` is not the tensor the fused value came from."""
 
+    @property
+    def _hip(self) -> _Derived:
+        try:
+            return self.__dict__["_hip_derived"]
+        except KeyError:
+            return self.__dict__.setdefault("_hip_derived", _Derived())
+
+    @property                       # ---- (this and the next two: what games_hip.render asks a model)
+    def hip_k0_pending(self) -> bool:
+        """The next differentiated render() of this model derives its Gaussians inside the rasterizer (HipMeshMixin.hip_defer_k0)."""
+        d = self.__dict__.get("_hip_derived")          # (asked once per render(): no record is made for the question)
+        return d is not None and d.pending
+
+    def hip_opacity_act(self):
+        """The kernel's sigmoid of `_opacity` while that tensor is unchanged, else None (torch.sigmoid differs from it in the last bit)."""
+        return _current(self._hip.opacity_act, getattr(self, "_opacity", None))
+
+    def hip_install_derived(self, scaling, rotation, scaling_act, rotation_unit):
+        """`_scaling` / `_rotation` and what get_scaling / get_rotation serve for them, as one op call derived the four."""
+        self._scaling, self._rotation = scaling, rotation
+        self._hip.activated = _Stamp((scaling_act, rotation_unit), scaling, rotation)
+
     # ---- deferred K0 (HipMeshMixin.hip_defer_k0): the derived attributes are materialised when somebody asks for them
     def _hip_materialize(self):
         pass
 
-    def _hip_frame_value(self, k):
-        """While K0 is deferred and nothing is being differentiated (an evaluation pass between two training steps), the getters
-        serve what the last training frame derived -- if the inputs have not changed since -- instead of launching K0."""
-        fr = self.__dict__.get("_hip_frame")
-        if fr is None or not self.__dict__.get("_hip_pending") or torch.is_grad_enabled():
-            return None
-        vertices, faces, _alpha, _scale = self._hip_inputs()
-        return fr[0][k] if fr[1] == _stamp(vertices, faces, _alpha, _scale, self._opacity) else None
+    def _hip_value(self, k):
+        """Entry k of (xyz, exp(scaling), unit rotation, sigmoid(opacity)) as the kernels derived it; None where the getter has to
+        apply the reference's formula itself.  While K0 is deferred and nothing is being differentiated (an evaluation pass between
+        two training steps), that is what the last training frame derived -- if the inputs have not changed since: no K0 launch."""
+        d = self._hip
+        if d.frame is not None and d.pending and not torch.is_grad_enabled():
+            fr = _current(d.frame, *self._hip_inputs(), self._opacity)
+            if fr is not None:
+                return fr[k]
+        self._hip_materialize()
+        if k == 0:
+            return self._xyz
+        if k == 3:
+            return self.hip_opacity_act()
+        act = _current(d.activated, self._scaling, self._rotation)
+        return None if act is None else act[k - 1]
 
     @property
     def get_xyz(self):
-        v = self._hip_frame_value(0)
-        if v is not None:
-            return v
-        self._hip_materialize()
-        return self._xyz
+        return self._hip_value(0)
 
     @property
     def get_scaling(self):
-        v = self._hip_frame_value(1)
-        if v is not None:
-            return v
-        self._hip_materialize()
-        act = self.__dict__.get("_hip_activated")
-        if act is not None and act[0] is self._scaling:
-            return act[2]
-        return torch.exp(self._scaling)
+        v = self._hip_value(1)
+        return v if v is not None else torch.exp(self._scaling)
 
     @property
     def get_rotation(self):
-        v = self._hip_frame_value(2)
-        if v is not None:
-            return v
-        self._hip_materialize()
-        act = self.__dict__.get("_hip_activated")
-        if act is not None and act[1] is self._rotation:
-            return act[3]
-        return torch.nn.functional.normalize(self._rotation)
+        v = self._hip_value(2)
+        return v if v is not None else torch.nn.functional.normalize(self._rotation)
 
     @property
     def get_opacity(self):
-        v = self._hip_frame_value(3)
-        if v is not None:
-            return v
-        self._hip_materialize()
-        cached = self.__dict__.get("_hip_opacity")
-        if cached is not None and cached[0] is self._opacity and cached[1] == self._opacity._version:
-            return cached[2]
-        return torch.sigmoid(self._opacity)
+        v = self._hip_value(3)
+        return v if v is not None else torch.sigmoid(self._opacity)
 
     @property
     def get_features(self):
@@ -129,34 +153,43 @@ class HipMeshMixin(_HipGetters):
 
     # ---- deferred K0 (opt-in; games_hip/train.py and bench.py switch it on).  train.py:154-157 calls update_alpha() /
     # prepare_scaling_rot() after every optimizer step and the next thing that happens is render() (train.py:100): with
-    # `hip_defer_k0 = True` the two calls only mark the derived attributes stale, and `games_hip.render.render` renders the frame
+    # `hip_defer_k0 = True` the two calls only mark the model (`_Derived.pending`), and `games_hip.render.render` renders the frame
     # STRAIGHT FROM THE MESH -- the face -> Gaussian arithmetic runs inside the rasterizer's preprocess thread, which also stores
     # xyz / activated scale / unit quaternion / sigmoid opacity for the backward (GmsRasterForwardArgs.mesh_out_*, ABI 6): no K0
     # launch, 84 + 44 bytes per Gaussian less HBM traffic, ONE autograd node from the mesh parameters to the image.  Anything
-    # else that asks for the derived values -- the property getters, save_ply, the reference's own render() -- materialises them
-    # first with the K0 launch, so every reader sees current values; only code that reads the RAW attributes (`_xyz`,
-    # `_scaling`, `_rotation`, `alpha`) directly between an optimizer step and the next render would see the previous step's,
-    # which is why the mode is opt-in (the reference's train.py has no such reader: train.py:100-157).
+    # else that asks for the derived values -- the getters, save_ply, the reference's own render() -- gets them from a K0 launch
+    # first; the mark comes off only when that launch carries a graph, so while it is set a reader under no_grad cannot cost the
+    # next frame its gradients.  Opt-in because code that reads the RAW attributes (`_xyz`, `_scaling`, `_rotation`, `alpha`) between an
+    # optimizer step and the next render sees the previous step's (the reference's train.py has no such reader: train.py:100-157).
     hip_defer_k0 = False
 
     def _hip_defer_now(self):
-        return (self.hip_defer_k0 and torch.is_grad_enabled() and self.__dict__.get("_hip_tri_external") is None
+        return (self.hip_defer_k0 and torch.is_grad_enabled() and self._hip.tri_external is None
                 and "_xyz" in self.__dict__ and "_scaling" in self.__dict__)          # (the first K0 of a model's life is always eager)
 
+    def _hip_refresh(self):
+        """update_alpha() + prepare_scaling_rot() as launches, whatever `hip_defer_k0` says: what a model saves is what it serves."""
+        keep, self.hip_defer_k0 = self.hip_defer_k0, False
+        try:
+            self.update_alpha()
+            self.prepare_scaling_rot()
+        finally:
+            self.hip_defer_k0 = keep
+
     def _hip_materialize(self):
-        if self.__dict__.pop("_hip_pending", None):
-            keep, self.hip_defer_k0 = self.hip_defer_k0, False
-            try:
-                self.update_alpha()
-                self.prepare_scaling_rot()
-            finally:
-                self.hip_defer_k0 = keep
+        d = self._hip
+        if not d.pending or d.tri_external is not None:   # (assigned triangles win until the next update_alpha(): no getter undoes them)
+            return
+        if not torch.is_grad_enabled():     # has an earlier no_grad reader derived the attributes from these very parameters?
+            g = _current(d.geometry, *self._hip_inputs())
+            if g is not None and g[0] is self._scaling and g[1] is self._rotation and (d.opacity_act is None or self.hip_opacity_act() is not None):
+                return
+        self._hip_refresh()
 
     def _hip_fused_frame(self, xyz, scaling_act, rotation_unit, opacity_act):
         """What a training frame rendered straight from the mesh derived (games_hip.render): served by the getters while the
         inputs are unchanged, so that e.g. an evaluation pass right after a training step launches no K0 either."""
-        vertices, faces, _alpha, _scale = self._hip_inputs()
-        self.__dict__["_hip_frame"] = ((xyz, scaling_act, rotation_unit, opacity_act), _stamp(vertices, faces, _alpha, _scale, self._opacity))
+        self._hip.frame = _Stamp((xyz, scaling_act, rotation_unit, opacity_act), *self._hip_inputs(), self._opacity)
 
     # ---- inputs of the op (overridden by the FLAME mixin, whose vertices come out of the FLAME layer)
     def _hip_inputs(self):
@@ -166,79 +199,72 @@ class HipMeshMixin(_HipGetters):
         vertices, faces, _alpha, _scale = self._hip_inputs()
         P = int(_alpha.shape[0] * _alpha.shape[1])
         # create_from_pcd calls update_alpha() before `_scale` exists (gaussian_mesh_model.py:78-81,
-        # gaussian_flame_model.py:78-82): alpha / xyz do not depend on it, scaling / rotation are not cached then
+        # gaussian_flame_model.py:78-82): alpha / xyz do not depend on it, scaling / rotation are not kept then
         have_scale = torch.is_tensor(_scale) and _scale.numel() == P
         scale_in = _scale if have_scale else torch.ones((P, 1), dtype=torch.float32, device=_alpha.device)
         opa = getattr(self, "_opacity", None)
         fuse_opacity = have_scale and torch.is_tensor(opa) and opa.is_cuda and opa.numel() == P
         out = mesh_to_gaussians(vertices, faces, _alpha, scale_in, self.alpha_mode, fused_activations=True,
                                 _opacity=opa if fuse_opacity else None)
-        alpha, xyz, scaling, rotation, scaling_act, rotation_unit = out[:6]
-        self.__dict__["_hip_opacity"] = (opa, opa._version, out[6]) if fuse_opacity else None
-        self.__dict__["_hip_cached"] = ((scaling, rotation, scaling_act, rotation_unit),
-                                        _stamp(vertices, faces, _alpha, _scale)) if have_scale else None
-        return alpha, xyz
+        d = self._hip
+        d.opacity_act = _Stamp(out[6], opa) if fuse_opacity else None
+        d.geometry = _Stamp(tuple(out[2:6]), vertices, faces, _alpha, _scale) if have_scale else None
+        return out[0], out[1]
 
     def update_alpha(self):
+        d = self._hip
         if self._hip_defer_now():
-            self.__dict__["_hip_pending"] = True          # render() will derive the Gaussians inside the rasterizer (see hip_defer_k0)
+            d.pending = True          # render() will derive the Gaussians inside the rasterizer (see hip_defer_k0)
             return
-        self.__dict__.pop("_hip_pending", None)
-        alpha, xyz = self._hip_run()
-        self.alpha = alpha
-        self._xyz = xyz
-        # `triangles` is only read by save_ply and the animated renderers: gathered on first access
-        self.__dict__.pop("_hip_tri", None)
-        self.__dict__["_hip_tri_external"] = None
-        if "triangles" in self.__dict__:           # a save_ply put it there (see save_ply below): keep it fresh
-            self.__dict__["triangles"] = self.triangles
+        d.pending = d.pending and not torch.is_grad_enabled()
+        self.alpha, self._xyz = self._hip_run()
+        d.tri_external = None
 
     @property
     def triangles(self):
-        ext = self.__dict__.get("_hip_tri_external")
-        if ext is not None:
-            return ext
-        tri = self.__dict__.get("_hip_tri")
+        d = self._hip
+        if d.tri_external is not None:
+            return d.tri_external
         vertices, faces = getattr(self, "vertices", None), getattr(self, "faces", None)
+        tri = _current(d.tri, vertices, faces)
         if tri is None and torch.is_tensor(vertices) and torch.is_tensor(faces) and faces.numel():
             with torch.no_grad():
                 tri = vertices[faces]
-            self.__dict__["_hip_tri"] = tri
+            d.tri = _Stamp(tri, vertices, faces)
         return tri
 
     @triangles.setter
     def triangles(self, value):
         # a renderer / loader replaced pc.triangles (renderer/gaussian_animated_renderer/__init__.py:72,
         # GaussianMeshModel.load_ply :231)
-        self.__dict__["_hip_tri_external"] = value
+        self._hip.tri_external = value
 
     def prepare_scaling_rot(self, *unused):
-        if self.__dict__.get("_hip_pending") and self._hip_defer_now():
+        d = self._hip
+        if d.pending and self._hip_defer_now():
             return
-        tri = self.__dict__.get("_hip_tri_external")
-        cached = self.__dict__.get("_hip_cached")
         vertices, faces, _alpha, _scale = self._hip_inputs()
-        if tri is not None:
+        if d.tri_external is not None:
             # a renderer replaced pc.triangles (renderer/gaussian_animated_renderer/__init__.py:72-73):
             # derive scale / rotation from those triangles
-            _, _, scaling, rotation, scaling_act, rotation_unit = triangles_to_gaussians(
-                tri, _alpha, _scale, self.alpha_mode, fused_activations=True)
-        elif cached is not None and cached[1] == _stamp(vertices, faces, _alpha, _scale):
-            scaling, rotation, scaling_act, rotation_unit = cached[0]
-        else:   # no update_alpha() since the inputs changed: recompute from the current tensors, as the reference does
-            _, _, scaling, rotation, scaling_act, rotation_unit = mesh_to_gaussians(
-                vertices, faces, _alpha, _scale, self.alpha_mode, fused_activations=True)
-        self._scaling = scaling
-        self._rotation = rotation
-        self.__dict__["_hip_activated"] = (scaling, rotation, scaling_act, rotation_unit)
+            derived = triangles_to_gaussians(d.tri_external, _alpha, _scale, self.alpha_mode, fused_activations=True)[2:6]
+        else:
+            derived = _current(d.geometry, vertices, faces, _alpha, _scale)
+            if derived is None:   # no update_alpha() since the inputs changed: recompute from the current tensors, as the reference does
+                derived = mesh_to_gaussians(vertices, faces, _alpha, _scale, self.alpha_mode, fused_activations=True)[2:6]
+        self.hip_install_derived(*derived)
 
     def save_ply(self, path):
-        """The reference's save_ply (gaussian_mesh_model.py:189-207) reads `triangles` out of the instance
-        `__dict__`; here it is a lazily gathered property, so materialise it there first (update_alpha keeps it
-        fresh from then on)."""
-        self._hip_materialize()
+        """The reference's save_ply (gaussian_mesh_model.py:189-207) calls update_alpha() / prepare_scaling_rot(), which may defer, and
+        reads `triangles` out of the instance `__dict__`, where the lazily gathered property does not live: derive first, and lend it
+        the triangles for the duration of the call."""
+        if self._hip_defer_now():
+            self._hip_refresh()
         self.__dict__["triangles"] = self.triangles
-        return super().save_ply(path)
+        try:
+            return super().save_ply(path)
+        finally:
+            del self.__dict__["triangles"]
 
 
 class HipFlameMixin(HipMeshMixin):
@@ -264,11 +290,7 @@ class HipFlameMixin(HipMeshMixin):
 
     def update_alpha(self):
         self.vertices = self._hip_flame_vertices()
-        alpha, xyz = self._hip_run()
-        self.alpha = alpha
-        self._xyz = xyz
-        self.__dict__.pop("_hip_tri", None)
-        self.__dict__["_hip_tri_external"] = None
+        super().update_alpha()
 
     def _hip_defer_now(self):       # (the FLAME layer runs in update_alpha: K0 stays an eager launch)
         return False
@@ -284,11 +306,10 @@ class HipMultiMeshMixin(_HipGetters):
     Host class provides the reference's list attributes: vertices[i], faces[i], _alpha[i] [F_i,S_i,3], _scale[i] [P_i,1]."""
 
     def _hip_topology(self):
-        key = (_stamp(*self.faces), tuple((int(f.shape[0]), int(a.shape[1]), int(v.shape[0]))
-                                          for f, a, v in zip(self.faces, self._alpha, self.vertices)))
-        cached = self.__dict__.get("_hip_topo")
-        if cached is not None and cached[0] == key:
-            return cached[1:]
+        shapes = tuple((int(f.shape[0]), int(a.shape[1]), int(v.shape[0])) for f, a, v in zip(self.faces, self._alpha, self.vertices))
+        kept = _current(self._hip.topology, *self.faces)
+        if kept is not None and kept[0] == shapes:
+            return kept[1]
         device = self.vertices[0].device
         faces, counts = [], []
         voff = 0
@@ -300,8 +321,11 @@ class HipMultiMeshMixin(_HipGetters):
         fso = torch.cat([torch.zeros(1, dtype=torch.int64), counts.cumsum(0)]).to(torch.int32)
         sf = torch.repeat_interleave(torch.arange(counts.numel(), dtype=torch.int32), counts)
         topo = (torch.cat(faces).contiguous(), fso.to(device), sf.to(device))
-        self.__dict__["_hip_topo"] = (key,) + topo
+        self._hip.topology = _Stamp((shapes, topo), *self.faces)
         return topo
+
+    def _hip_inputs(self):
+        return (*self.vertices, *self.faces, *self._alpha, *self._scale)
 
     def _hip_run(self):
         faces, fso, sf = self._hip_topology()
@@ -312,8 +336,9 @@ class HipMultiMeshMixin(_HipGetters):
         fuse_opacity = torch.is_tensor(opa) and opa.is_cuda and opa.numel() == Sc.numel()
         out = mesh_to_gaussians(V, faces, A, Sc, "relu", face_splat_offset=fso, splat_face=sf, fused_activations=True,
                                 _opacity=opa if fuse_opacity else None)
-        self.__dict__["_hip_opacity"] = (opa, opa._version, out[6]) if fuse_opacity else None
-        self.__dict__["_hip_cached"] = (tuple(out[2:6]), _stamp(*self.vertices, *self.faces, *self._alpha, *self._scale))
+        d = self._hip
+        d.opacity_act = _Stamp(out[6], opa) if fuse_opacity else None
+        d.geometry = _Stamp(tuple(out[2:6]), *self._hip_inputs())
         return out[0], out[1]
 
     def update_alpha(self):
@@ -326,13 +351,11 @@ class HipMultiMeshMixin(_HipGetters):
         self.update_alpha()
 
     def prepare_scaling_rot(self, *unused):
-        cached = self.__dict__.get("_hip_cached")
-        if cached is None or cached[1] != _stamp(*self.vertices, *self.faces, *self._alpha, *self._scale):
+        derived = _current(self._hip.geometry, *self._hip_inputs())
+        if derived is None:
             self._hip_run()
-            cached = self.__dict__["_hip_cached"]
-        scaling, rotation, scaling_act, rotation_unit = cached[0]
-        self._scaling, self._rotation = scaling, rotation
-        self.__dict__["_hip_activated"] = (scaling, rotation, scaling_act, rotation_unit)
+            derived = self._hip.geometry.value
+        self.hip_install_derived(*derived)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -369,24 +392,22 @@ class HipPointsMixin(_HipGetters):
         opa = getattr(self, "_opacity", None)
         fuse_opacity = self._hip_on_gpu(opa) and opa.numel() == triangles.shape[0]
         out = points_to_gaussians(triangles, opa if fuse_opacity else None, eps, float(self.eps_s0))
-        xyz, scaling, rotation, scaling_act, rotation_unit = out[:5]
-        self._scaling = scaling
-        self._rotation = rotation
-        self.__dict__["_hip_activated"] = (scaling, rotation, scaling_act, rotation_unit)
-        self.__dict__["_hip_opacity"] = (opa, opa._version, out[5]) if fuse_opacity else None
-        self.__dict__["_hip_points_xyz"] = (triangles, xyz)
+        self.hip_install_derived(*out[1:5])
+        d = self._hip
+        d.opacity_act = _Stamp(out[5], opa) if fuse_opacity else None
+        d.centre = _Stamp(out[0], triangles)
 
     def _hip_points_centre(self, triangles):
         """triangles[:, 0] as the points op returned it (differentiable through its node) when `triangles` is the tensor the last
         prepare_scaling_rot() ran on, else the slice itself."""
-        cached = self.__dict__.get("_hip_points_xyz")
-        return cached[1] if cached is not None and cached[0] is triangles else triangles[:, 0]
+        centre = _current(self._hip.centre, triangles)
+        return centre if centre is not None else triangles[:, 0]
 
     @property
     def get_scaling(self):
-        act = self.__dict__.get("_hip_activated")
-        if act is not None and act[0] is self._scaling:
-            return act[2]
+        v = self._hip_value(1)
+        if v is not None:
+            return v
         s = self._scaling        # points_gaussian_model.py:107-109
         s0 = torch.full((s.shape[0], 1), float(self.eps_s0), dtype=s.dtype, device=s.device)
         return torch.cat([s0, torch.exp(s[:, [-2, -1]])], dim=1)
@@ -420,6 +441,8 @@ class _StandaloneBase:
         import numpy as np
         from ._plyfile_compat import PlyData, PlyElement
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        if hasattr(self, "_hip_refresh"):
+            self._hip_refresh()                 # what a model saves is what it serves: derived from the current parameters, now
         xyz = self._xyz.detach().cpu().numpy()
         cols = [xyz, np.zeros_like(xyz),
                 self._features_dc.detach().transpose(1, 2).flatten(start_dim=1).contiguous().cpu().numpy(),
@@ -493,8 +516,6 @@ class HipGaussianMeshModel(HipMeshMixin, _StandaloneBase):
     # ---- checkpoints: the reference's on-disk format (scene/gaussian_model.py:177-268 point_cloud.ply +
     # games/mesh_splatting/scene/gaussian_mesh_model.py:189-222 model_params.pt), through the plyfile stand-in
     def save_ply(self, path):
-        self.update_alpha()
-        self.prepare_scaling_rot()
         self._save_point_cloud(path)
         torch.save({"_alpha": self._alpha, "_scale": self._scale, "point_cloud": None, "triangles": self.triangles,
                     "vertices": self.vertices, "faces": self.faces}, path.replace("point_cloud.ply", "model_params.pt"))
@@ -654,8 +675,6 @@ class HipGaussianFlameModel(HipFlameMixin, _StandaloneBase):
         scale multipliers) ride along -- the reference's own `load_ply` ignores unknown keys; without them a loaded model can
         only replay the PLY's scaling / rotation, not re-derive them per animated frame (BASELINE
         config 5)."""
-        self.update_alpha()
-        self.prepare_scaling_rot()
         self._save_point_cloud(path)
         save_dict = {k: getattr(self, k) for k in self.FLAME_ATTRS + self.FLAME_EXTRA_ATTRS}
         torch.save(save_dict, path.replace("point_cloud.ply", "flame_params.pt"))
@@ -679,11 +698,9 @@ class HipGaussianFlameModel(HipFlameMixin, _StandaloneBase):
         params = torch.load(path.replace("point_cloud.ply", "flame_params.pt"), map_location=device, weights_only=False)
         for k in self.FLAME_ATTRS:
             setattr(self, k, params[k])
+        # (the getters serve exp(_scaling) / normalize(_rotation) of these new tensors until something re-derives them)
+        self.__dict__.pop("_hip_derived", None)
         self.vertices = None
-        self.__dict__["_hip_cached"] = None
-        self.__dict__["_hip_opacity"] = None
-        # the getters serve exp(_scaling) / normalize(_rotation) of the PLY columns until something re-derives them
-        self.__dict__["_hip_activated"] = None
         if all(k in params for k in self.FLAME_EXTRA_ATTRS):
             self._alpha = nn.Parameter(params["_alpha"].detach().to(device))
             self._scales = nn.Parameter(params["_scales"].detach().to(device))

@@ -8,11 +8,15 @@ GPU tests run where the reference tree is absent.  Flag semantics (`compute_cov3
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass
 
 import torch
 
+import diff_gaussian_rasterization as dgr
 from diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
+
+from .mesh_op import ALPHA_MODES
 
 
 @dataclass
@@ -63,53 +67,70 @@ def eval_sh(deg, sh, dirs):
 _zero_cache = {}
 
 
-def _zero_points(xyz: torch.Tensor) -> torch.Tensor:
-    key = (xyz.device, tuple(xyz.shape), xyz.dtype)
+def _zero_points(device, shape, dtype=torch.float32) -> torch.Tensor:
+    key = (device, tuple(shape), dtype)
     z = _zero_cache.get(key)
     if z is None:
         if len(_zero_cache) >= 8:
             _zero_cache.clear()
-        z = _zero_cache[key] = torch.zeros(xyz.shape, dtype=xyz.dtype, device=xyz.device)
+        z = _zero_cache[key] = torch.zeros(shape, dtype=dtype, device=device)
     return z.detach().requires_grad_(True)
+
+
+class _View:
+    """The same model with other centres (the reference's animated renderers pass them as means3D); never a deferred training frame."""
+    hip_k0_pending = False
+
+    def __init__(self, pc, xyz):
+        self._pc, self.get_xyz = pc, xyz
+
+    def __getattr__(self, name):
+        return getattr(self._pc, name)
+
+
+def _native_route(entry, knob, pc, pipe, override_color) -> bool:
+    """What the three fused routes share: the extension has `entry`, the environment does not set `knob` to 0, nothing python-side
+    is requested (the rasterizer's native SH / cov3D stages), split degree-3 SH STORAGE, contiguous."""
+    if (dgr._C is None or not hasattr(dgr._C, entry) or os.environ.get(knob, "1") == "0"
+            or override_color is not None or pipe.compute_cov3D_python or pipe.convert_SHs_python):
+        return False
+    fr, dc = getattr(pc, "_features_rest", None), getattr(pc, "_features_dc", None)
+    return torch.is_tensor(fr) and fr.dim() == 3 and fr.shape[1] == 15 and fr.is_contiguous() and torch.is_tensor(dc) and dc.is_contiguous()
+
+
+def _kernel_opacity_current(pc) -> bool:
+    """The unfused frame reads get_opacity: the kernel's sigmoid while the model still holds it for the current `_opacity` (else
+    torch.sigmoid, which the fused forward-only routes do not reproduce bit for bit)."""
+    ask = getattr(pc, "hip_opacity_act", None)
+    return ask is not None and ask() is not None
+
+
+def _mesh_sizes_ok(pc) -> bool:
+    """Uniform splats per face on the GPU, one `_opacity` / scale row per Gaussian."""
+    a, op = getattr(pc, "_alpha", None), getattr(pc, "_opacity", None)
+    if not (torch.is_tensor(a) and a.dim() == 3 and a.is_cuda):
+        return False
+    P, sc = int(a.shape[0] * a.shape[1]), getattr(pc, getattr(pc, "_hip_scale_attr", "_scale"), None)
+    return torch.is_tensor(op) and op.numel() == P and torch.is_tensor(sc) and sc.numel() == P
 
 
 def _fused_training_ok(pc, pipe, override_color) -> bool:
     """Can this DIFFERENTIATED frame be rendered straight from the mesh (games_hip.model.HipMeshMixin.hip_defer_k0)?  The model
-    deferred its K0 (update_alpha() since the last optimizer step, nothing has asked for the derived values), uniform splats per
-    face, split degree-3 SH STORAGE (any active degree), the rasterizer's native SH / cov3D stages."""
-    import os
-    import diff_gaussian_rasterization as dgr
-    if not (hasattr(pc, "__dict__") and pc.__dict__.get("_hip_pending")) or not torch.is_grad_enabled():
-        return False
-    if dgr._C is None or not hasattr(dgr._C, "render_mesh") or os.environ.get("GMS_TRAIN_FUSED", "1") == "0":
-        return False
-    if override_color is not None or pipe.compute_cov3D_python or pipe.convert_SHs_python:
-        return False
-    a, fr, dc, op = getattr(pc, "_alpha", None), getattr(pc, "_features_rest", None), getattr(pc, "_features_dc", None), getattr(pc, "_opacity", None)
-    if not (torch.is_tensor(a) and a.dim() == 3 and a.is_cuda and torch.is_tensor(fr) and fr.dim() == 3 and fr.shape[1] == 15 and torch.is_tensor(dc)):
-        return False
-    P = int(a.shape[0] * a.shape[1])
-    sc = getattr(pc, getattr(pc, "_hip_scale_attr", "_scale"), None)
-    return (0 <= int(pc.active_sh_degree) <= 3 and torch.is_tensor(op) and op.numel() == P and torch.is_tensor(sc) and sc.numel() == P
-            and dc.is_contiguous() and fr.is_contiguous() and dc.shape[0] == P and torch.is_tensor(getattr(pc, "faces", None)))
+    deferred its K0 (update_alpha() since the last optimizer step, nothing has asked for the derived values with a graph), uniform
+    splats per face, split degree-3 SH STORAGE (any active degree), the rasterizer's native SH / cov3D stages."""
+    return (getattr(pc, "hip_k0_pending", False) and torch.is_grad_enabled()
+            and _native_route("render_mesh", "GMS_TRAIN_FUSED", pc, pipe, override_color) and _mesh_sizes_ok(pc)
+            and 0 <= int(pc.active_sh_degree) <= 3 and pc._features_dc.shape[0] == pc._opacity.numel()
+            and torch.is_tensor(getattr(pc, "faces", None)))
 
 
 def _render_training_frame_from_mesh(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
     """train.py:100 on a model whose K0 is deferred: ONE C++ autograd node from (vertices, _alpha, _scale, _opacity, SH) to the image
     (`_C.render_mesh`; GmsRasterForwardArgs.mesh + mesh_out_*).  Same image and gradients as the two-node graph (tests/test_gpu_fused_training.py)."""
-    import diff_gaussian_rasterization as dgr
-    from .mesh_op import ALPHA_MODES
     vertices, faces, _alpha, _scale = pc._hip_inputs()
     if faces.dtype != torch.int64 or not faces.is_contiguous():
         faces = faces.long().contiguous()
-    P = int(_alpha.shape[0] * _alpha.shape[1])
-    key = (_alpha.device, (P, 3), torch.float32)
-    z = _zero_cache.get(key)
-    if z is None:
-        if len(_zero_cache) >= 8:
-            _zero_cache.clear()
-        z = _zero_cache[key] = torch.zeros((P, 3), dtype=torch.float32, device=_alpha.device)
-    screenspace_points = z.detach().requires_grad_(True)
+    screenspace_points = _zero_points(_alpha.device, (int(_alpha.shape[0] * _alpha.shape[1]), 3))
     H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
     image, radii, invdepth, xyz, scaling_act, rotation_unit, opacity_act, visible = dgr._C.render_mesh(
         vertices, faces, _alpha, _scale, pc._opacity, pc._features_dc, pc._features_rest, screenspace_points,
@@ -130,7 +151,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     # 3.6 MB fill + an elementwise kernel per render for a tensor whose VALUES nobody reads (the rasterizer only hands a
     # gradient back through it).  Here: a fresh leaf aliasing a cached all-zero buffer -- same values, its own `.grad`
     # (train.py:129-133 reads it for the densification statistics), no kernel
-    screenspace_points = _zero_points(xyz)
+    screenspace_points = _zero_points(xyz.device, xyz.shape, xyz.dtype)
     tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
     tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
     raster_settings = GaussianRasterizationSettings(
@@ -169,23 +190,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
 def _fused_frame_ok(pc, pipe, override_color) -> bool:
     """Can this forward-only frame take the fused mesh -> image path (GmsRasterForwardArgs.mesh)?  Uniform splats per face, split
     degree-3 SH storage at full degree, the rasterizer's native SH / cov3D stages, nothing to differentiate."""
-    import os
-    import diff_gaussian_rasterization as dgr
-    if dgr._C is None or not hasattr(dgr._C, "render_mesh_forward") or os.environ.get("GMS_ANIMATE_FUSED", "1") == "0":
-        return False
-    if torch.is_grad_enabled() or override_color is not None or pipe.compute_cov3D_python or pipe.convert_SHs_python:
-        return False
-    a, fr, op = getattr(pc, "_alpha", None), getattr(pc, "_features_rest", None), getattr(pc, "_opacity", None)
-    if not (torch.is_tensor(a) and a.dim() == 3 and a.is_cuda and torch.is_tensor(fr) and fr.dim() == 3 and fr.shape[1] == 15):
-        return False
-    P = int(a.shape[0] * a.shape[1])
-    sc = getattr(pc, getattr(pc, "_hip_scale_attr", "_scale"), None)
-    # the unfused frame reads get_opacity: the kernel's sigmoid while the model's cache of it is current (else torch.sigmoid, which
-    # this path does not reproduce bit for bit)
-    cached = pc.__dict__.get("_hip_opacity") if hasattr(pc, "__dict__") else None
-    cache_ok = cached is not None and cached[0] is op and cached[1] == op._version
-    return (int(pc.active_sh_degree) == 3 and torch.is_tensor(op) and op.numel() == P and torch.is_tensor(sc) and sc.numel() == P
-            and cache_ok and pc._features_dc.is_contiguous() and fr.is_contiguous())
+    return (not torch.is_grad_enabled() and _native_route("render_mesh_forward", "GMS_ANIMATE_FUSED", pc, pipe, override_color)
+            and _mesh_sizes_ok(pc) and int(pc.active_sh_degree) == 3 and _kernel_opacity_current(pc))
 
 
 def render_mesh_frame(vertices: torch.Tensor, faces: torch.Tensor, viewpoint_camera, pc, pipe, bg_color: torch.Tensor,
@@ -197,8 +203,6 @@ def render_mesh_frame(vertices: torch.Tensor, faces: torch.Tensor, viewpoint_cam
     / `pc._xyz` keep the values of the last `prepare_scaling_rot()` (the undeformed mesh), and `viewspace_points` is None -- a
     forward-only frame has no screen-space gradient to receive.  Code that saves or inspects the DEFORMED Gaussians after a frame
     calls `render_animated` with `GMS_ANIMATE_FUSED=0` (or assigns `pc.triangles` and calls `prepare_scaling_rot()`)."""
-    import diff_gaussian_rasterization as dgr
-    from .mesh_op import ALPHA_MODES
     H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
     color, radii, invdepth, visible = dgr._C.render_mesh_forward(
         vertices.float(), faces, pc._alpha, getattr(pc, getattr(pc, "_hip_scale_attr", "_scale")), pc._opacity, ALPHA_MODES[getattr(pc, "alpha_mode", "relu")], int(pc._alpha.shape[1]),
@@ -213,30 +217,21 @@ def render_animated(idxs, triangles, viewpoint_camera, pc, pipe, bg_color: torch
     """renderer/gaussian_animated_renderer/__init__.py:21-121: the mesh is deformed per frame, centres follow
     `pc.alpha @ triangles` (:61-67) and scale / rotation are re-derived from the deformed triangles (:72-73).
     With the fused op that is one kernel: assigning `pc.triangles` and calling `prepare_scaling_rot()` runs
-    the op on the explicit triangles; its xyz output is `alpha @ triangles`."""
-    from .mesh_op import triangles_to_gaussians, _identity_faces
+    the op on the explicit triangles; its xyz output is `alpha @ triangles`.  `pc` carries games_hip.model.HipMeshMixin."""
+    from .mesh_op import identity_faces, triangles_to_gaussians
     if _fused_frame_ok(pc, pipe, override_color):
         # forward-only frame (the animated drivers run under no_grad): K0 inside the preprocess thread, explicit triangles as an
         # identity-indexed mesh.  (The cached kernel sigmoid is what the unfused frame would read from get_opacity.)
         F_ = int(triangles.shape[0])
         if F_ != int(pc._alpha.shape[0]):          # (the unfused route fails in `alpha @ triangles`: same error class here)
             raise RuntimeError(f"render_animated: {F_} triangles for a model with {int(pc._alpha.shape[0])} faces")
-        key = (triangles.device, F_)
-        if key not in _identity_faces:
-            _identity_faces[key] = torch.arange(3 * F_, device=triangles.device, dtype=torch.int64).reshape(F_, 3)
         pc.triangles = triangles
-        return render_mesh_frame(triangles.reshape(3 * F_, 3), _identity_faces[key], viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
+        return render_mesh_frame(triangles.reshape(3 * F_, 3), identity_faces(triangles.device, F_), viewpoint_camera, pc, pipe, bg_color,
+                                 scaling_modifier)
     pc.triangles = triangles
-    _, xyz, scaling, rotation, scaling_act, rotation_unit = triangles_to_gaussians(
-        triangles, pc._alpha, pc._scale, getattr(pc, "alpha_mode", "relu"), fused_activations=True)
-    pc._scaling, pc._rotation = scaling, rotation
-    pc._hip_activated = (scaling, rotation, scaling_act, rotation_unit)
-
-    class _View:       # same model, centres from the deformed mesh (the reference passes them as means3D)
-        def __getattr__(self, name):
-            return getattr(pc, name)
-        get_xyz = xyz
-    return render(viewpoint_camera, _View(), pipe, bg_color, scaling_modifier, override_color)
+    out = triangles_to_gaussians(triangles, pc._alpha, pc._scale, getattr(pc, "alpha_mode", "relu"), fused_activations=True)
+    pc.hip_install_derived(*out[2:6])
+    return render(viewpoint_camera, _View(pc, out[1]), pipe, bg_color, scaling_modifier, override_color)
 
 
 def _points_frame_ok(pc, pipe, override_color) -> bool:
@@ -244,18 +239,8 @@ def _points_frame_ok(pc, pipe, override_color) -> bool:
     differentiate, the rasterizer's native SH / cov3D stages, split degree-3 SH storage (any active degree), and the model's cache of
     the kernel sigmoid current (the unfused frame reads get_opacity: the kernel's sigmoid then, else torch.sigmoid, which this path
     does not reproduce bit for bit).  `GMS_ANIMATE_FUSED=0` keeps the two-launch route, as for mesh frames."""
-    import os
-    import diff_gaussian_rasterization as dgr
-    if dgr._C is None or not hasattr(dgr._C, "render_points_forward") or os.environ.get("GMS_ANIMATE_FUSED", "1") == "0":
-        return False
-    if torch.is_grad_enabled() or override_color is not None or pipe.compute_cov3D_python or pipe.convert_SHs_python:
-        return False
-    fr, dc, op = getattr(pc, "_features_rest", None), getattr(pc, "_features_dc", None), getattr(pc, "_opacity", None)
-    if not (torch.is_tensor(fr) and fr.dim() == 3 and fr.shape[1] == 15 and fr.is_cuda and torch.is_tensor(dc) and torch.is_tensor(op)):
-        return False
-    cached = pc.__dict__.get("_hip_opacity") if hasattr(pc, "__dict__") else None
-    cache_ok = cached is not None and cached[0] is op and cached[1] == op._version
-    return 0 <= int(pc.active_sh_degree) <= 3 and cache_ok and dc.is_contiguous() and fr.is_contiguous()
+    return (not torch.is_grad_enabled() and _native_route("render_points_forward", "GMS_ANIMATE_FUSED", pc, pipe, override_color)
+            and pc._features_rest.is_cuda and 0 <= int(pc.active_sh_degree) <= 3 and _kernel_opacity_current(pc))
 
 
 def render_points_frame(triangles: torch.Tensor, viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, eps=1e-8):
@@ -263,7 +248,6 @@ def render_points_frame(triangles: torch.Tensor, viewpoint_camera, pc, pipe, bg_
     preprocess thread (no points launch, no per-Gaussian tensors).  Same image, bit for bit, as the points op followed by the
     rasterizer on its outputs; callers check `_points_frame_ok`.  As with `render_mesh_frame`, `pc._scaling` / `pc._rotation` keep the
     values of the last prepare_scaling_rot() and `viewspace_points` is None."""
-    import diff_gaussian_rasterization as dgr
     H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
     color, radii, invdepth, visible = dgr._C.render_points_forward(
         triangles, pc._opacity, pc._features_dc, pc._features_rest, bg_color, viewpoint_camera.world_view_transform,
@@ -282,9 +266,4 @@ def render_points_animated(triangles, viewpoint_camera, pc, pipe, bg_color: torc
         return render_points_frame(triangles, viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
     pc.prepare_scaling_rot(triangles)
     centre = pc._hip_points_centre(triangles) if hasattr(pc, "_hip_points_centre") else triangles[:, 0]
-
-    class _View:       # same model, centres from the triangles (the reference passes them as means3D)
-        def __getattr__(self, name):
-            return getattr(pc, name)
-        get_xyz = centre
-    return render(viewpoint_camera, _View(), pipe, bg_color, scaling_modifier, override_color)
+    return render(viewpoint_camera, _View(pc, centre), pipe, bg_color, scaling_modifier, override_color)

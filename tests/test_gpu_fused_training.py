@@ -47,7 +47,7 @@ def test_fused_training_frame_equals_the_two_node_graph(det, size):
         img0, radii0, g0 = _step(model, cam, bg, False)
         before = dgr._C.last_stats()["num_rendered"]
         img1, radii1, g1 = _step(model, cam, bg, True)
-        assert model.__dict__.get("_hip_pending") is True               # K0 really was deferred: no eager launch happened
+        assert model.hip_k0_pending is True               # K0 really was deferred: no eager launch happened
         assert dgr._C.last_stats()["num_rendered"] == before
     finally:
         dgr.set_deterministic(was)
@@ -72,16 +72,16 @@ def test_deferred_values_are_materialised_for_every_reader_and_served_from_the_f
     with torch.no_grad():
         model._alpha.add_(0.01 * torch.randn_like(model._alpha))        # "an optimizer step"
     model.update_alpha(); model.prepare_scaling_rot()                    # deferred
-    assert model.__dict__.get("_hip_pending") is True
+    assert model.hip_k0_pending is True
     stale = model._xyz.detach().clone()
     out = render(cam, model, PipelineParams(), bg)                       # the frame derives the Gaussians itself
     assert out["render"].requires_grad and out["viewspace_points"].requires_grad
     with torch.no_grad():
         xyz_frame = model.get_xyz                                        # under no_grad: what the frame derived, no K0 launch
-        assert model.__dict__.get("_hip_pending") is True and not torch.equal(xyz_frame, stale)
+        assert model.hip_k0_pending is True and not torch.equal(xyz_frame, stale)
         sc_frame, rot_frame, op_frame = model.get_scaling, model.get_rotation, model.get_opacity
     xyz = model.get_xyz                                                  # grad mode: the K0 launch (a differentiable tensor)
-    assert model.__dict__.get("_hip_pending") is None and xyz.requires_grad
+    assert model.hip_k0_pending is False and xyz.requires_grad
     assert torch.equal(xyz.detach(), xyz_frame) and torch.equal(model._xyz.detach(), xyz_frame)
     assert torch.equal(model.get_scaling.detach(), sc_frame) and torch.equal(model.get_rotation.detach(), rot_frame)
     assert torch.equal(model.get_opacity.detach(), op_frame)
@@ -89,7 +89,7 @@ def test_deferred_values_are_materialised_for_every_reader_and_served_from_the_f
     model.update_alpha(); model.prepare_scaling_rot()
     pipe = PipelineParams(); pipe.convert_SHs_python = True
     out2 = render(cam, model, pipe, bg)
-    assert model.__dict__.get("_hip_pending") is None and out2["render"].requires_grad
+    assert model.hip_k0_pending is False and out2["render"].requires_grad
     model.hip_defer_k0 = False
 
 
@@ -109,7 +109,7 @@ def test_fused_training_frame_during_the_sh_ramp(degree):
         _step(model, cam, bg, False)
         img0, radii0, g0 = _step(model, cam, bg, False)
         img1, radii1, g1 = _step(model, cam, bg, True)
-        assert model.__dict__.get("_hip_pending") is True               # the frame took the fused route
+        assert model.hip_k0_pending is True               # the frame took the fused route
     finally:
         dgr.set_deterministic(was)
         model.active_sh_degree = 3
@@ -184,3 +184,87 @@ def test_mesh_backward_inside_preprocess_bwd_equals_the_mesh_backward_launch(siz
     for k in g0:
         scale = float(g0[k].abs().max())
         assert scale > 0 and float((g1[k] - g0[k]).abs().max()) <= 2e-5 * scale + 1e-12, (k, float((g1[k] - g0[k]).abs().max()), scale)
+
+
+def _optimizer_like_edit(model, seed):
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    with torch.no_grad():
+        model.vertices.add_(0.01 * torch.randn(model.vertices.shape, device="cuda", generator=g))
+        model._alpha.add_(0.01 * torch.randn(model._alpha.shape, device="cuda", generator=g))
+        model._scale.mul_(1.02)
+
+
+def test_save_after_deferred_steps_writes_what_the_model_serves(tmp_path):
+    """What a model saves is what it serves: after training steps whose K0 ran inside the rasterizer (`_xyz` / `_scaling` / `_rotation`
+    still hold the values from before them), save_ply WITH GRAD ENABLED writes the derivation of the current parameters."""
+    from games_hip.model import HipGaussianMeshModel
+    model = _model()
+    cam = syn.orbit_camera(1, width=96, height=96).to("cuda")
+    bg = torch.ones(3, device="cuda")
+    stale = model._xyz.detach().clone()
+    path = str(tmp_path / "point_cloud.ply")
+    try:
+        for k in range(3):
+            _step(model, cam, bg, True)
+            _optimizer_like_edit(model, k)
+        model.update_alpha(); model.prepare_scaling_rot()               # train.py:154-157 after the last step: deferred
+        assert model.hip_k0_pending is True and torch.equal(model._xyz.detach(), stale)
+        model.save_ply(path)
+    finally:
+        model.hip_defer_k0 = False
+    loaded = HipGaussianMeshModel(3)
+    loaded.load_ply(path)
+    cols = loaded._load_point_cloud(path, "cuda")
+    assert not torch.equal(model.get_xyz.detach(), stale)
+    for got in (loaded.get_xyz, cols["xyz"]):
+        assert torch.equal(got.detach(), model.get_xyz.detach())        # same kernel, float32 columns
+    for got in (loaded._scaling, cols["scaling"]):
+        assert torch.equal(got.detach(), model._scaling.detach())
+    for got in (loaded._rotation, cols["rotation"]):
+        assert torch.equal(got.detach(), model._rotation.detach())
+    assert torch.equal(loaded.triangles, model.vertices.detach()[model.faces])
+
+
+def test_no_grad_reads_do_not_cost_the_next_training_frame_its_gradients():
+    """An evaluation pass between the deferred update_alpha() and the next training frame reads the getters under no_grad: the frame
+    still goes straight from the mesh and every parameter gets the gradient it gets without the reads, bit for bit (deterministic mode)."""
+    import diff_gaussian_rasterization as dgr
+    from games_hip.render import PipelineParams, render
+    cam = syn.orbit_camera(1, width=96, height=96).to("cuda")
+    bg = torch.tensor([0.9, 0.7, 0.3], device="cuda")
+
+    def frame(read, defer=True):
+        model = _model()
+        stale = model._xyz.detach().clone()
+        model.hip_defer_k0 = defer
+        _optimizer_like_edit(model, 7)
+        model.update_alpha(); model.prepare_scaling_rot()
+        if read:
+            with torch.no_grad():
+                served = [model.get_xyz, model.get_scaling, model.get_rotation, model.get_opacity]
+            assert not torch.equal(served[0], stale)                    # current values, not the ones from before the edit
+        else:
+            assert torch.equal(model._xyz.detach(), stale) == defer     # nothing was launched before the frame
+        assert model.hip_k0_pending is defer
+        out = render(cam, model, PipelineParams(), bg)
+        img = out["render"]
+        (img * ((img.detach() - 0.5) / img.numel() * 1000.0)).sum().backward()
+        assert model.hip_k0_pending is defer                            # the frame took the fused route
+        g = {n: getattr(model, n).grad.detach().clone() for n in PARAMS}
+        g["viewspace"] = out["viewspace_points"].grad.detach().clone()
+        model.hip_defer_k0 = False
+        return img.detach().clone(), g, dgr._C.last_stats()["num_rendered"]
+
+    was = dgr.deterministic()
+    dgr.set_deterministic(True)
+    try:
+        img_r, g_r, n_r = frame(False, defer=False)                     # the two-node graph of the same parameters
+        img_b, g_b, n_b = frame(False)
+        img_a, g_a, n_a = frame(True)
+    finally:
+        dgr.set_deterministic(was)
+    assert n_a == n_b == n_r
+    assert torch.equal(img_a, img_b) and torch.equal(img_b, img_r)
+    for k in g_b:
+        assert torch.equal(g_a[k], g_b[k]) and torch.equal(g_b[k], g_r[k]), k
+        assert float(g_a[k].abs().max()) > 0, k

@@ -60,7 +60,7 @@ def ref_frame(tri, pc, view, bg):
                                        bg, 1.0, view.world_view_transform, view.full_proj_transform, pc.active_sh_degree, view.camera_center,
                                        False, False, False)
     xyz = tri[:, 0]
-    return GaussianRasterizer(rs)(means3D=xyz, means2D=_zero_points(xyz), shs=pc.get_features, colors_precomp=None,
+    return GaussianRasterizer(rs)(means3D=xyz, means2D=_zero_points(xyz.device, xyz.shape, xyz.dtype), shs=pc.get_features, colors_precomp=None,
                                   opacities=torch.sigmoid(pc._opacity), scales=scales,
                                   rotations=torch.nn.functional.normalize(_rotation), cov3D_precomp=None)[0]
 
