@@ -1200,6 +1200,95 @@ Tensor flame_forward(const std::vector<Tensor> &tables, const std::vector<int64_
     return flame_run_forward(in, nullptr);
 }
 
+// ---------------------------------------------------------------------------------------------- density control (csrc/densify.hip)
+// float32, contiguous, on `dev`, holding rows * width values: what the kernels index
+const float *densify_f32(const Tensor &t, int64_t numel, c10::Device dev, const char *what)
+{
+    TORCH_CHECK(t.defined() && t.scalar_type() == torch::kFloat && t.is_contiguous() && t.numel() == numel && (numel == 0 || t.device() == dev),
+                "densify: ", what, " must be a contiguous float32 tensor of ", numel, " values on the model's device");
+    return numel ? t.data_ptr<float>() : nullptr;
+}
+
+// train.py:132-133 + add_densification_stats, in place on max_radii2D (None: left alone) / xyz_gradient_accum / denom: one launch, no host wait
+void densify_stats(const Tensor &radii, const Tensor &viewspace_grad, const std::optional<Tensor> &max_radii2D, Tensor xyz_gradient_accum, Tensor denom)
+{
+    require_gpu(radii);
+    const int64_t P = radii.numel();
+    const c10::Device dev = radii.device();
+    TORCH_CHECK(radii.scalar_type() == torch::kInt && radii.is_contiguous(), "densify_stats: radii must be a contiguous int32 tensor");
+    TORCH_CHECK(viewspace_grad.dim() == 2 && viewspace_grad.size(1) == 3, "densify_stats: the screen-space gradient must have dimensions (P, 3)");
+    const float *g = densify_f32(viewspace_grad, 3 * P, dev, "viewspace_grad");
+    float *mr = max_radii2D.has_value() && max_radii2D->defined() ? const_cast<float *>(densify_f32(*max_radii2D, P, dev, "max_radii2D")) : nullptr;
+    float *ac = const_cast<float *>(densify_f32(xyz_gradient_accum, P, dev, "xyz_gradient_accum"));
+    float *dn = const_cast<float *>(densify_f32(denom, P, dev, "denom"));
+    if (P == 0) return;
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+    check_rc(gms_densify_stats(P, radii.data_ptr<int32_t>(), g, mr, ac, dn, stream_of(dev)), "gms_densify_stats");
+}
+
+// -> (src int32 [P'], kind int32 [P'], [P', survivors, clones, first children, second children]); one stream synchronisation
+std::tuple<Tensor, Tensor, std::vector<int64_t>> densify_plan(const Tensor &xyz_gradient_accum, const Tensor &denom, const Tensor &opacity,
+                                                              const Tensor &scaling, double grad_threshold, double dense_threshold,
+                                                              double min_opacity, bool prune_world, double world_threshold, double eps_s0)
+{
+    require_gpu(scaling);
+    TORCH_CHECK(scaling.dim() == 2, "densify_plan: scaling must have dimensions (P, 2) or (P, 3)");
+    const int64_t P = scaling.size(0), S = scaling.size(1);
+    const c10::Device dev = scaling.device();
+    const float *sc = densify_f32(scaling, P * S, dev, "scaling"), *ac = densify_f32(xyz_gradient_accum, P, dev, "xyz_gradient_accum");
+    const float *dn = densify_f32(denom, P, dev, "denom"), *op = densify_f32(opacity, P, dev, "opacity");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+    auto iopt = torch::TensorOptions().dtype(torch::kInt).device(dev);
+    Tensor src = torch::empty({2 * P}, iopt), kind = torch::empty({2 * P}, iopt);
+    const size_t bytes = gms_densify_plan_workspace_bytes(P);
+    Tensor work = torch::empty({(int64_t)bytes}, torch::TensorOptions().dtype(torch::kUInt8).device(dev));
+    std::vector<int64_t> counts(5, 0);
+    check_rc(gms_densify_plan(P, (int32_t)S, ac, dn, op, sc, (float)grad_threshold, (float)dense_threshold, (float)min_opacity, prune_world ? 1 : 0,
+                              (float)world_threshold, (float)eps_s0, P ? src.data_ptr<int32_t>() : nullptr, P ? kind.data_ptr<int32_t>() : nullptr,
+                              counts.data(), work.data_ptr(), bytes, P ? stream_of(dev) : nullptr),
+             "gms_densify_plan");
+    return {src.narrow(0, 0, counts[0]), kind.narrow(0, 0, counts[0]), counts};
+}
+
+// params = [xyz, f_dc, f_rest, opacity, scaling, rotation]; exp_avg / exp_avg_sq: the same six, or empty lists (no optimizer state yet)
+// -> (new params, new exp_avg, new exp_avg_sq), dimension 0 = len(src); one launch
+std::tuple<std::vector<Tensor>, std::vector<Tensor>, std::vector<Tensor>> densify_apply(const Tensor &src, const Tensor &kind, const std::vector<Tensor> &params,
+                                                                                        const std::vector<Tensor> &exp_avg, const std::vector<Tensor> &exp_avg_sq,
+                                                                                        const Tensor &noise, double eps_s0)
+{
+    TORCH_CHECK(params.size() == 6, "densify_apply: six parameter tensors expected (xyz, f_dc, f_rest, opacity, scaling, rotation)");
+    const bool moments = !exp_avg.empty() || !exp_avg_sq.empty();
+    TORCH_CHECK(!moments || (exp_avg.size() == 6 && exp_avg_sq.size() == 6), "densify_apply: six tensors of each Adam moment, or none");
+    require_gpu(params[0]); require_gpu(src);
+    const int64_t P = params[0].size(0), P_new = src.numel();
+    const c10::Device dev = params[0].device();
+    TORCH_CHECK(src.scalar_type() == torch::kInt && kind.scalar_type() == torch::kInt && src.is_contiguous() && kind.is_contiguous() && kind.numel() == P_new &&
+                (P_new == 0 || (src.device() == dev && kind.device() == dev)), "densify_apply: src and kind must be contiguous int32 [P'] on the model's device");
+    const float *z = densify_f32(noise, 6 * P, dev, "noise [2,P,3]");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+    GmsDensifyTensor t[6];
+    std::vector<Tensor> po(6), mo, vo;
+    for (int g = 0; g < 6; g++) {
+        const Tensor &p = params[g];
+        TORCH_CHECK(p.defined() && p.dim() >= 1 && p.size(0) == P, "densify_apply: parameter ", g, " does not have P rows");
+        const int64_t width = P ? p.numel() / P : 0;
+        std::vector<int64_t> shape = p.sizes().vec();
+        shape[0] = P_new;
+        po[g] = torch::empty(shape, p.options());
+        t[g] = GmsDensifyTensor{densify_f32(p, P * width, dev, "a parameter"), nullptr, nullptr, P_new * width ? po[g].data_ptr<float>() : nullptr,
+                                nullptr, nullptr, (int32_t)width};
+        if (moments) {
+            mo.push_back(torch::empty(shape, p.options())); vo.push_back(torch::empty(shape, p.options()));
+            t[g].exp_avg = densify_f32(exp_avg[g], P * width, dev, "exp_avg");
+            t[g].exp_avg_sq = densify_f32(exp_avg_sq[g], P * width, dev, "exp_avg_sq");
+            if (P_new * width) { t[g].exp_avg_out = mo[g].data_ptr<float>(); t[g].exp_avg_sq_out = vo[g].data_ptr<float>(); }
+        }
+    }
+    if (P_new == 0 || P == 0) return {po, mo, vo};
+    check_rc(gms_densify_apply(P, P_new, src.data_ptr<int32_t>(), kind.data_ptr<int32_t>(), t, z, (float)eps_s0, stream_of(dev)), "gms_densify_apply");
+    return {po, mo, vo};
+}
+
 // ---------------------------------------------------------------------------------------------- multi-tensor Adam
 void adam_step(const std::vector<Tensor> &params, const std::vector<Tensor> &grads, const std::vector<Tensor> &exp_avg,
                const std::vector<Tensor> &exp_avg_sq, const std::vector<double> &lrs, const std::vector<int64_t> &steps, double beta1,
@@ -1245,6 +1334,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("bind_pseudomesh", &bind_pseudomesh, "bind pseudo-triangles [P,3,3] to the nearest faces of a guide mesh: (face_idx int32 [P], alpha [P,3,3], n_degenerate)", nogil());
     m.def("bind_apply", &bind_apply, "pseudo-triangles [P,3,3] of a binding on (edited) guide vertices; launches only", py::arg("face_idx"), py::arg("alpha"),
           py::arg("guide_vertices"), py::arg("guide_faces"), py::arg("out") = py::none(), nogil());
+    m.def("densify_stats", &densify_stats, "per-iteration densification statistics, in place on (max_radii2D, xyz_gradient_accum, denom); one launch", nogil());
+    m.def("densify_plan", &densify_plan, "clone / split / prune decisions as a source map: (src int32 [P'], kind int32 [P'], counts)", nogil());
+    m.def("densify_apply", &densify_apply, "gather the six parameters and their Adam moments through a plan: (params, exp_avg, exp_avg_sq)", nogil());
     m.def("flame_vertices", &flame_vertices, "differentiable FLAME layer (+ axis swap and enlargement): vertices [V,3], one autograd node", py::arg("tables"),
           py::arg("parents"), py::arg("rots"), py::arg("rot_joints"), py::arg("shape"), py::arg("expression"), py::arg("transl") = py::none(),
           py::arg("enlargement") = py::none(), py::arg("enlargement_scalar") = 1.0, py::arg("swap") = false, nogil());

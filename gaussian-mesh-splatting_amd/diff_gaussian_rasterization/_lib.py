@@ -133,6 +133,14 @@ class FlameGrads(C.Structure):
     ]
 
 
+class DensifyTensor(C.Structure):
+    """GmsDensifyTensor: one parameter with its Adam moments, before and after a densification."""
+    _fields_ = [
+        ("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+        ("param_out", C.c_void_p), ("exp_avg_out", C.c_void_p), ("exp_avg_sq_out", C.c_void_p), ("width", C.c_int32),
+    ]
+
+
 def flame_saved_floats(V: int) -> int:
     """GMS_FLAME_SAVED_FLOATS."""
     return 3 * int(V) + 24 * FLAME_MAX_JOINTS
@@ -151,6 +159,7 @@ EXPORTS = (
     "gms_points_prepare_vertices", "gms_points_to_gaussians_forward", "gms_points_to_gaussians_backward",
     "gms_bind_workspace_bytes", "gms_bind_pseudomesh", "gms_bind_apply",
     "gms_flame_workspace_bytes", "gms_flame_forward", "gms_flame_backward",
+    "gms_densify_stats", "gms_densify_plan_workspace_bytes", "gms_densify_plan", "gms_densify_apply",
 )
 K_COUNT = 23
 
@@ -218,6 +227,16 @@ def load():
         lib.gms_flame_backward.restype = C.c_int32
         lib.gms_flame_backward.argtypes = [C.POINTER(FlameModel), C.POINTER(FlameParams), C.c_void_p, C.c_void_p, C.POINTER(FlameGrads), C.c_void_p,
                                            C.c_size_t, C.c_void_p]
+        lib.gms_densify_stats.restype = C.c_int32
+        lib.gms_densify_stats.argtypes = [C.c_int64] + [C.c_void_p] * 6
+        lib.gms_densify_plan_workspace_bytes.restype = C.c_size_t
+        lib.gms_densify_plan_workspace_bytes.argtypes = [C.c_int64]
+        lib.gms_densify_plan.restype = C.c_int32
+        lib.gms_densify_plan.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                         C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.c_size_t,
+                                         C.c_void_p]
+        lib.gms_densify_apply.restype = C.c_int32
+        lib.gms_densify_apply.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(DensifyTensor), C.c_void_p, C.c_float, C.c_void_p]
         lib.gms_l1_ssim_partials.restype = C.c_size_t
         lib.gms_l1_ssim_partials.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         lib.gms_l1_ssim_forward.restype = C.c_int32

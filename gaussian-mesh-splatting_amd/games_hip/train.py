@@ -1,4 +1,4 @@
-"""The training loop of train.py:39-157, for the mesh-bound models, on the HIP stack.
+"""The training loop of train.py:39-157, for the mesh-bound models and the free-Gaussian ones (gs / gs_flat), on the HIP stack.
 
 Host-side mirror of the reference's `training()` (BASELINE config 3: "gs_mesh hotdog full train loop 7k iters").  On a machine
 that holds the reference, its own `train.py` runs unchanged on the drop-in packages (tests/test_reference_train_cpu.py drives
@@ -12,12 +12,19 @@ GPU box has no reference tree.  Per iteration, in the reference's order:
     render_pkg = render(viewpoint_cam, gaussians, pipe, bg)       train.py:100
     loss = (1 - l) * l1_loss + l * (1 - ssim)                     train.py:105-107
     loss.backward()                                               train.py:108
-    [densification: gs / gs_flat only]                            train.py:129-145  (not executed for mesh models)
+    [gs / gs_flat only] while iteration < densify_until_iter:     train.py:129-143  (a model without `densify_and_prune`, or an
+        max_radii2D / add_densification_stats                     `opt` without `densify_until_iter`, skips the block: the mesh
+        densify_and_prune(...) every densification_interval       path runs the statements it always ran)
+        reset_opacity() every opacity_reset_interval
     optimizer.step(); optimizer.zero_grad(set_to_none=True)       train.py:147-150  (skipped on the last iteration, as there)
     gaussians.update_alpha(); gaussians.prepare_scaling_rot()     train.py:154-157
 
 What is left out, and why: the network GUI (train.py:64-80), tensorboard / checkpoint files and `scene.save` (I/O; the `report`
-callback receives what `training_report` receives), `os.makedirs(.../xyz)` every iteration."""
+callback receives what `training_report` receives), `os.makedirs(.../xyz)` every iteration.
+
+Density control runs on the kernels of csrc/densify.hip (games_hip.densify): the per-iteration statistics are one launch without a
+host wait (the reference's boolean-mask statements wait for the device at every `x[mask]`), a densification is a plan, one read-back
+of its counts and one gather.  `games_hip.free_model` has the stand-alone gs / gs_flat models this loop trains."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -42,16 +49,59 @@ class OptimizationParamsMesh:
     lambda_dssim: float = 0.2
 
 
+@dataclass
+class OptimizationParams:
+    """arguments/__init__.py:72-90 (gs / gs_flat)."""
+    iterations: int = 30_000
+    position_lr_init: float = 0.00016
+    position_lr_final: float = 0.0000016
+    position_lr_delay_mult: float = 0.01
+    position_lr_max_steps: int = 30_000
+    feature_lr: float = 0.0025
+    opacity_lr: float = 0.05
+    scaling_lr: float = 0.005
+    rotation_lr: float = 0.001
+    percent_dense: float = 0.01
+    lambda_dssim: float = 0.2
+    densification_interval: int = 100
+    opacity_reset_interval: int = 3000
+    densify_from_iter: int = 500
+    densify_until_iter: int = 15_000
+    densify_grad_threshold: float = 0.0002
+    random_background: bool = False
+
+
+def _density_control(gaussians, opt, iteration, render_pkg, cameras_extent, white_background):
+    """train.py:129-143, for a model that has `densify_and_prune` under an `opt` that has `densify_until_iter`."""
+    if iteration >= opt.densify_until_iter:
+        return
+    viewspace_point_tensor, visibility_filter, radii = render_pkg["viewspace_points"], render_pkg["visibility_filter"], render_pkg["radii"]
+    if hasattr(gaussians, "hip_densification_stats"):        # train.py:132-134 in one launch, no host wait (csrc/densify.hip)
+        gaussians.hip_densification_stats(viewspace_point_tensor, radii)
+    else:
+        # Keep track of max radii in image-space for pruning
+        gaussians.max_radii2D[visibility_filter] = torch.max(gaussians.max_radii2D[visibility_filter], radii[visibility_filter])
+        gaussians.add_densification_stats(viewspace_point_tensor, visibility_filter)
+    if iteration > opt.densify_from_iter and iteration % opt.densification_interval == 0:
+        size_threshold = 20 if iteration > opt.opacity_reset_interval else None
+        gaussians.densify_and_prune(opt.densify_grad_threshold, 0.005, cameras_extent, size_threshold)
+    if iteration % opt.opacity_reset_interval == 0 or (white_background and iteration == opt.densify_from_iter):
+        gaussians.reset_opacity()
+
+
 def training(gaussians, train_cameras: Sequence, opt: OptimizationParamsMesh, pipe, background: torch.Tensor, *,
              render: Optional[Callable] = None, loss_fn: Optional[Callable] = None, first_iter: int = 0,
-             report: Optional[Callable] = None, report_iterations: Sequence[int] = ()) -> List[float]:
+             report: Optional[Callable] = None, report_iterations: Sequence[int] = (), cameras_extent: float = 1.0,
+             white_background: bool = False) -> List[float]:
     """Runs iterations first_iter+1 .. opt.iterations.  `train_cameras`: objects with the camera attributes `render()` reads and
     `original_image` [3,H,W] (scene/cameras.py:17-58).  `gaussians`: a model with `training_setup()` already called (train.py:46).
     `render` / `loss_fn(image, gt, lambda_dssim) -> scalar` default to the HIP path (games_hip.render.render, the fused L1+SSIM of
     csrc/loss.hip).  `report(iteration, loss)` is called inside `torch.no_grad()` at `report_iterations` (the place of
     `training_report`, train.py:120-122).  Returns the loss values it synchronised on (one per report).  Uses `random.randint` and
     `torch.rand` exactly where the reference does: seed them as `safe_state` does (utils/general_utils.py:203-213) to reproduce its
-    camera order."""
+    camera order.  `cameras_extent` (scene.cameras_extent) and `white_background` (dataset.white_background) are read by the density
+    control of gs / gs_flat models only (train.py:138, 142)."""
+    densify = hasattr(gaussians, "densify_and_prune") and hasattr(opt, "densify_until_iter")
     if render is None:
         from .render import render as render_fn
     else:
@@ -111,6 +161,10 @@ def training(gaussians, train_cameras: Sequence, opt: OptimizationParamsMesh, pi
                 reported.append(float(loss.detach()))
                 if report is not None:
                     report(iteration, reported[-1])
+            # Densification (`render_pkg` is the frame the gradients came from: the redone one after a deferred overflow, whose
+            # tensors have the model's current size)
+            if densify:
+                _density_control(gaussians, opt, iteration, render_pkg, cameras_extent, white_background)
             # Optimizer step
             if iteration < opt.iterations:
                 gaussians.optimizer.step()

@@ -461,6 +461,55 @@ int32_t gms_flame_forward(const GmsFlameModel *model, const GmsFlameParams *para
 int32_t gms_flame_backward(const GmsFlameModel *model, const GmsFlameParams *params, const float *saved, const float *dL_dvertices,
                            const GmsFlameGrads *grads, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- adaptive density control of the free-Gaussian models, gs / gs_flat (csrc/densify.hip) ----------
+ * Additive to ABI 10: no existing layout changes; these kernels have no gms_profile_* slot.  All three reject null or
+ * inconsistent arguments before touching a device; P = 0 succeeds and launches nothing.
+ *
+ * gms_densify_stats, every iteration, one launch and no host wait: replaces train.py:132-133 and `add_densification_stats`
+ * (scene/gaussian_model.py:416-418).  For every row with radii[i] > 0: max_radii2D[i] = max(max_radii2D[i], (float)radii[i]);
+ * xyz_gradient_accum[i] += sqrt(gx*gx + gy*gy) with (gx, gy) the first two columns of viewspace_grad [P,3]; denom[i] += 1.
+ * The other rows are not written.  max_radii2D may be NULL (a caller that has run train.py:132 itself): it is then left alone.
+ *
+ * gms_densify_plan: the decisions of `densify_and_prune` -> `densify_and_clone` -> `densify_and_split` (N = 2) -> the final
+ * prune (scene/gaussian_model.py:360-412; games/flat_splatting/scene/flat_gaussian_model.py:62-88 for S = 2 stored scales, whose
+ * first axis is the constant eps_s0), as one map.  g = accum / denom with NaN -> 0; clone: g >= grad_threshold and
+ * max(get_scaling) <= dense_threshold (= percent_dense * extent); split: g >= grad_threshold and max(get_scaling) > dense_threshold.
+ * Final prune of the unsplit originals, the clones and the children: sigmoid(opacity) < min_opacity, or -- with prune_world, the
+ * reference's `max_screen_size` given -- max(get_scaling) > world_threshold (= 0.1 * extent), a child being tested with its new
+ * scale.  (The reference's max_radii2D term is always false: densification_postfix has zeroed max_radii2D by then.)
+ * grad_threshold must be positive.  Row j of the result comes from row src_out[j] of the input as kind_out[j]: 0 survivor,
+ * 1 clone, 2 / 3 split child of repeat block 0 / 1; in the reference's order: survivors by index, clones by index, all first
+ * children, all second children.  src_out / kind_out: device int32 with room for 2 P rows (the most a plan can produce).
+ * counts_out: HOST int64[5] = {P', survivors, clones, first children, second children}; reading it back is the call's one stream
+ * synchronisation.  `workspace`: caller-owned device scratch of at least gms_densify_plan_workspace_bytes(P) bytes.  No atomics:
+ * bit-identical from call to call.
+ *
+ * gms_densify_apply, one gather launch: builds the P_new rows of the six parameter tensors and of their Adam moments.
+ * `tensors`: HOST array of six, in the order xyz (width 3), f_dc (3), f_rest (any width, 0 included), opacity (1), scaling
+ * (2 or 3), rotation (4).  Survivors copy parameter and moments bit for bit; clones and children copy the source's parameter row
+ * and get zero moments; a child's xyz' = R(q / |q|) . (get_scaling * z) + xyz and scaling' = log(get_scaling / 1.6) (the stored
+ * columns), in the reference's order of operations.  z = noise [2,P,3]: standard normals indexed by repeat block and source row.
+ * src / kind as written by the plan (an index outside [0, P) is the caller's error: not checked). */
+typedef struct GmsDensifyTensor {
+    const float *param;           /* device [P, width] */
+    const float *exp_avg;         /* device [P, width], or NULL with the other three moment pointers: no optimizer state yet */
+    const float *exp_avg_sq;
+    float *param_out;             /* device [P_new, width] */
+    float *exp_avg_out;
+    float *exp_avg_sq_out;
+    int32_t width;
+} GmsDensifyTensor;
+int32_t gms_densify_stats(int64_t P, const int32_t *radii /* [P] */, const float *viewspace_grad /* [P,3] */, float *max_radii2D /* [P] or NULL */,
+                          float *xyz_gradient_accum /* [P] */, float *denom /* [P] */, void *stream);
+size_t gms_densify_plan_workspace_bytes(int64_t P);
+int32_t gms_densify_plan(int64_t P, int32_t S, const float *xyz_gradient_accum /* [P] */, const float *denom /* [P] */,
+                         const float *opacity /* [P] raw */, const float *scaling /* [P,S] raw */, float grad_threshold, float dense_threshold,
+                         float min_opacity, int32_t prune_world, float world_threshold, float eps_s0, int32_t *src_out /* [2P] */,
+                         int32_t *kind_out /* [2P] */, int64_t *counts_out /* HOST [5] */, void *workspace, size_t workspace_bytes,
+                         void *stream);
+int32_t gms_densify_apply(int64_t P, int64_t P_new, const int32_t *src /* [P_new] */, const int32_t *kind /* [P_new] */,
+                          const GmsDensifyTensor *tensors /* HOST [6] */, const float *noise /* [2,P,3] */, float eps_s0, void *stream);
+
 /* ---- per-kernel timing (HIP events on the launch stream; off by default) ------------------
  * When enabled every kernel launch made by this library is bracketed by two hipEvents on the
  * caller's stream.  gms_profile_read() synchronises the recorded events and returns the summed
