@@ -33,10 +33,14 @@ struct AdamTable {
 __device__ __forceinline__ void adam_update(float &p, float g, float &m, float &v, float w1, float beta2, float w2, float step_size,
                                             float bc2_sqrt, float eps)
 {
-    m = m + (g - m) * w1;
+    // The kernel holds two copies of this body (float4 rows; the scalar tail and unaligned tensors).  Left to the compiler, the copies were
+    // contracted differently -- the scalar one kept `m + (g - m) * w1` as a multiply and an add -- so a tensor's bits depended on its
+    // alignment.  The rounding is therefore spelled out: two fused steps (the ones the float4 copy has always had), nothing else fused.
+#pragma clang fp contract(off)
+    m = __builtin_fmaf(g - m, w1, m);
     v = v * beta2 + w2 * g * g;
     const float denom = sqrtf(v) / bc2_sqrt + eps;
-    p = p - step_size * (m / denom);
+    p = __builtin_fmaf(-step_size, m / denom, p);
 }
 
 __global__ void __launch_bounds__(BLOCK) adam_kernel(AdamTable t, float w1, float beta2, float w2, float eps)

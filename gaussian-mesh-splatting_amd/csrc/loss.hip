@@ -99,9 +99,14 @@ __global__ void __launch_bounds__(BLOCK) l1_ssim_fwd_kernel(int H, int W, const 
             float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
 #pragma unroll
             for (int k = 0; k < NW; k++) {
+                // Every accumulation of the two passes (here and in the backward) is an explicit fused multiply-add.  Left to contraction,
+                // the five moments were not rounded alike -- the vectoriser packs the products of one chain into v_pk_mul, and a packed
+                // product is not fused with the scalar add that follows -- so on EQUAL images E[x^2], E[y^2] and E[xy] differed in the last
+                // bit at half the pixels, and SSIM(x, x) was not exactly 1 as it is in the reference's float32 evaluation.
                 const float x = xin[i + k], y = yin[i + k], w = win.w[k];
                 const float wx = w * x, wy = w * y;
-                a += wx; b += wy; aa += wx * x; bb += wy * y; ab += wx * y;
+                a = __builtin_fmaf(w, x, a); b = __builtin_fmaf(w, y, b);
+                aa = __builtin_fmaf(wx, x, aa); bb = __builtin_fmaf(wy, y, bb); ab = __builtin_fmaf(wx, y, ab);
             }
             hz[0][r][c0 + i] = a; hz[1][r][c0 + i] = b; hz[2][r][c0 + i] = aa; hz[3][r][c0 + i] = bb; hz[4][r][c0 + i] = ab;
         }
@@ -121,12 +126,17 @@ __global__ void __launch_bounds__(BLOCK) l1_ssim_fwd_kernel(int H, int W, const 
             for (int i = 0; i < LQ; i++) {
                 float acc = 0.f;
 #pragma unroll
-                for (int k = 0; k < NW; k++) acc += win.w[k] * col[i + k];
+                for (int k = 0; k < NW; k++) acc = __builtin_fmaf(win.w[k], col[i + k], acc);
                 mom[m][i] = acc;
             }
         }
 #pragma unroll
         for (int i = 0; i < LQ; i++) {
+            // Nothing in this body is contracted: fused, `e11 - m1 * m1` took the exact square and `e12 - m1m2` the rounded product, so on
+            // equal images s1 + s2 and 2 s12 differed by a rounding of mu^2 -- against C2 = 9e-4 that put SSIM(x, x) of a flat region 1e-5
+            // below 1, where the reference's float32 evaluation gives exactly 1 (numerator and denominator are the same numbers).  For the
+            // same reason S is a true quotient, not a product with the reciprocal the derivatives share.
+#pragma clang fp contract(off)
             const int r = r0 + i;
             const int gy = y0 + r, gx = x0 + c;
             if (gy >= H || gx >= W) continue;
@@ -136,7 +146,7 @@ __global__ void __launch_bounds__(BLOCK) l1_ssim_fwd_kernel(int H, int W, const 
             const float An = 2.f * m1m2 + SSIM_C1, Bn = 2.f * s12 + SSIM_C2;
             const float Ad = m1sq + m2sq + SSIM_C1, Bd = s1 + s2 + SSIM_C2;
             const float inv = 1.f / (Ad * Bd);
-            const float S = An * Bn * inv;
+            const float S = (An * Bn) / (Ad * Bd);
             ssim_sum += S;
             l1_sum += fabsf(sx[r + LR][c + LR] - sy[r + LR][c + LR]);
             if (dmaps) {
@@ -158,7 +168,7 @@ __global__ void __launch_bounds__(BLOCK) l1_ssim_fwd_kernel(int H, int W, const 
 }
 
 // value = w_l1 * mean|x-y| + w_ssim * mean(ssim) + bias; fixed summation order, double accumulators
-__global__ void __launch_bounds__(BLOCK) l1_ssim_reduce_kernel(int nblocks, const float *partials, double inv_count, float w_l1,
+__global__ void __launch_bounds__(BLOCK) l1_ssim_reduce_kernel(int nblocks, const float *partials, double count, float w_l1,
                                                                float w_ssim, float bias, float *out)
 {
     __shared__ double red[2][4];
@@ -168,8 +178,9 @@ __global__ void __launch_bounds__(BLOCK) l1_ssim_reduce_kernel(int nblocks, cons
     if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double l1 = (red[0][0] + red[0][1] + red[0][2] + red[0][3]) * inv_count;
-        const double ss = (red[1][0] + red[1][1] + red[1][2] + red[1][3]) * inv_count;
+        // (a quotient: count * (1 / count) is not always 1, and the mean SSIM of equal images is exactly 1)
+        const double l1 = (red[0][0] + red[0][1] + red[0][2] + red[0][3]) / count;
+        const double ss = (red[1][0] + red[1][1] + red[1][2] + red[1][3]) / count;
         out[0] = (float)((double)w_l1 * l1 + (double)w_ssim * ss + (double)bias);
         out[1] = (float)l1;
         out[2] = (float)ss;
@@ -219,7 +230,7 @@ __global__ void __launch_bounds__(BLOCK) l1_ssim_bwd_kernel(int H, int W, const 
             for (int i = 0; i < LQ; i++) {
                 float acc = 0.f;
 #pragma unroll
-                for (int k = 0; k < NW; k++) acc += win.w[k] * in[i + k];
+                for (int k = 0; k < NW; k++) acc = __builtin_fmaf(win.w[k], in[i + k], acc);
                 hz[m][r][c0 + i] = acc;
             }
         }
@@ -239,7 +250,7 @@ __global__ void __launch_bounds__(BLOCK) l1_ssim_bwd_kernel(int H, int W, const 
             for (int i = 0; i < LQ; i++) {
                 float acc = 0.f;
 #pragma unroll
-                for (int k = 0; k < NW; k++) acc += win.w[k] * col[i + k];
+                for (int k = 0; k < NW; k++) acc = __builtin_fmaf(win.w[k], col[i + k], acc);
                 v[m][i] = acc;
             }
         }
@@ -291,7 +302,7 @@ extern "C" int32_t gms_l1_ssim_forward(const GmsLossArgs *a, float *dmaps, float
     const int nblocks = (int)(grid.x * grid.y * grid.z);
     GMS_LAUNCH(GMS_K_LOSS_FWD, stream,
                (l1_ssim_fwd_kernel<<<grid, BLOCK, 0, stream>>>(a->height, a->width, a->img, a->gt, win, dmaps, (size_t)count, partials),
-                l1_ssim_reduce_kernel<<<1, BLOCK, 0, stream>>>(nblocks, partials, 1.0 / (double)count, a->w_l1, a->w_ssim, a->bias, out)));
+                l1_ssim_reduce_kernel<<<1, BLOCK, 0, stream>>>(nblocks, partials, (double)count, a->w_l1, a->w_ssim, a->bias, out)));
     GMS_KERNEL_CHECK(0, stream, "l1_ssim_fwd");
     return GMS_OK;
 }

@@ -44,8 +44,7 @@ def test_deferred_and_blocking_forms_give_the_same_frame_and_gradients(dgr_state
     model = _model()
     cam = syn.orbit_camera(2, width=160, height=144).to("cuda")
     bg = torch.tensor([0.9, 0.7, 0.3], device="cuda")
-    dgr.set_deterministic(True)                              # fixed summation order: the two forms must agree bit for bit
-    dgr.set_deterministic(False); dgr.set_deferred_counts(False)
+    dgr.set_deterministic(False); dgr.set_deferred_counts(False)      # float atomics: the image agrees bit for bit, the gradients to summation order
     _step(model, cam, bg); _step(model, cam, bg)            # (the first frames of a shape size their buffers with a blocking read-back)
     ref_img, ref = _step(model, cam, bg, defer_k0)
     dgr.set_deferred_counts(True)
@@ -66,6 +65,29 @@ def test_deferred_and_blocking_forms_give_the_same_frame_and_gradients(dgr_state
     with pytest.raises(RuntimeError, match="ticket expired"):
         outs[0].sum().backward()
     outs[-1].sum().backward()                                # the newest ticket is fine
+
+
+@pytest.mark.parametrize("defer_k0", [False, True])
+def test_in_deterministic_mode_the_switch_changes_no_bit(dgr_state, defer_k0):
+    """Deterministic mode: fixed-point sums, no float atomic, so the image and every gradient must be bit-equal with the switch off and
+    on.  The binding passes no capacity hint in this mode (the frame's layout may depend on the frame alone), and without a hint
+    there is nothing to defer against: the frame is read back inside the forward whatever the switch says.  What this pins is that
+    set_deferred_counts(True) neither breaks nor perturbs a deterministic run; the deferred form itself exists in default mode only."""
+    dgr = dgr_state
+    model = _model()
+    cam = syn.orbit_camera(2, width=160, height=144).to("cuda")
+    bg = torch.tensor([0.9, 0.7, 0.3], device="cuda")
+    dgr.set_deterministic(True); dgr.set_deferred_counts(False)
+    _step(model, cam, bg); _step(model, cam, bg)
+    ref_img, ref = _step(model, cam, bg, defer_k0)
+    n_blocking = dgr.last_stats()["num_rendered"]
+    dgr.set_deferred_counts(True)
+    img, got = _step(model, cam, bg, defer_k0)
+    model.hip_defer_k0 = False
+    assert dgr.last_stats()["num_rendered"] == n_blocking > 0
+    assert torch.equal(img, ref_img)
+    for k in ref:
+        assert torch.equal(got[k], ref[k]), k
 
 
 def test_an_overflowed_deferred_frame_is_reported_by_the_backward_and_the_redone_step_is_right(dgr_state):
