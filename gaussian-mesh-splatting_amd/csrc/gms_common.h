@@ -45,9 +45,14 @@ struct GeomState {
     ushort4 *rect;      // [P] tile rectangle [minx, maxx) x [miny, maxy) as (minx, miny, maxx, maxy); all zero for a culled Gaussian.
                         //     What emit_instances reads (with `depth`: 12 bytes per Gaussian) instead of the pixel centre out of the
                         //     48-byte record, whose every cache line it had to fetch for 8 bytes (round 6: 25 -> 13 MB of HBM traffic)
+    float *sh_ddir;     // [P][9] d colour / d view direction of the SH colour (gms_project.h::sh_eval_with_dir_jacobian), row a*3+c.  Written by
+                        //     preprocess_fwd for visible Gaussians of SH frames only (culled Gaussians and colors_precomp frames leave it
+                        //     untouched); preprocess_bwd contracts it with dL/dcolour instead of reading the coefficient rows again
+    static constexpr size_t SH_DDIR = 9;
     static __host__ __device__ size_t bytes(size_t P)
     {
-        return align_up(P * sizeof(SplatRec), 256) + align_up(P * 4, 256) + align_up(P, 256) + align_up(P * sizeof(ushort4), 256);
+        return align_up(P * sizeof(SplatRec), 256) + align_up(P * 4, 256) + align_up(P, 256) + align_up(P * sizeof(ushort4), 256) +
+               align_up(P * SH_DDIR * 4, 256);
     }
     static __host__ __device__ GeomState carve(void *base, size_t P)
     {
@@ -56,7 +61,8 @@ struct GeomState {
         g.rec = (SplatRec *)p; p += align_up(P * sizeof(SplatRec), 256);
         g.depth = (float *)p;  p += align_up(P * 4, 256);
         g.clamped = (uint8_t *)p; p += align_up(P, 256);
-        g.rect = (ushort4 *)p;
+        g.rect = (ushort4 *)p; p += align_up(P * sizeof(ushort4), 256);
+        g.sh_ddir = (float *)p;
         return g;
     }
 };

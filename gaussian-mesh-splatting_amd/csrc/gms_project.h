@@ -77,4 +77,97 @@ __device__ __forceinline__ void ewa_project(const float *V, float vx, float vy, 
     e.c0 = e.T1[0] * e.ST1[0] + e.T1[1] * e.ST1[1] + e.T1[2] * e.ST1[2];
 }
 
+// SH colour and its direction derivative in one pass over the coefficient row.
+//   res[c]       = sum_k basis_k(x, y, z) * sh(k, c): SH -> RGB before +0.5 / clamp, the operation order of utils/sh_utils.py:57-112
+//                  evaluated per channel (k ascending, each product rounded, then added);
+//   D[a * 3 + c] = sum_k (d basis_k / d dir_a) * sh(k, c): the 3x3 per Gaussian that the backward contracts with dL/dcolour
+//                  (gdir[a] = sum_c D[a*3+c] * dRGB[c]).  It is linear in the coefficients, so the forward, which holds them, evaluates it
+//                  once and stores nine floats (GeomState::sh_ddir), and the backward never reads a coefficient.  The basis is
+//                  differentiated as a polynomial in (x, y, z) (no unit-norm substitution: the caller projects onto the tangent plane).
+// One function for every route (all preprocess_fwd instantiations, the test hook), so that all of them give the same bits; the order is
+// part of the contract: contraction off for the polynomials and the colour, k ascending, the three channels inner, each derivative term
+// added by ONE explicit fused multiply-add (D = fma(derivative, coefficient, D): half the instructions of multiply-then-add), entries
+// whose derivative is identically zero skipped.  Degree 0 gives D = 0 exactly.  `sh(k, c)` is any accessor (registers, LDS, global),
+// called once per (k, c).  Fused because the colour is a chain of sixteen dependent additions per channel: the derivative's independent
+// multiply-adds fill its gaps, the row is read once, and a coefficient's register dies as the accumulators it feeds come alive.
+// Longest chain of a D entry (the test's operation count, 20): an x or y entry at degree 3 is 12 fused multiply-adds whose derivative
+// takes at most 8 operations (k = 11, y: zz, 4zz, xx, -, yy, 3yy, -, * C); a z entry is 9 of at most 9 (k = 12).
+template <int DEG, typename SH>
+__device__ __forceinline__ void sh_eval_with_dir_jacobian(SH sh, float x, float y, float z, float res[3], float D[9])
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int j = 0; j < 9; j++) D[j] = 0.f;
+    // GMS_SH_K(k, basis value, X(..) Y(..) Z(..)): fetch the row's three coefficients, add them into the colour and into the axes whose
+    // derivative is not identically zero
+#define GMS_SH_K(K, BV, AXES)                                                      \
+    {                                                                              \
+        const float s[3] = {sh((K), 0), sh((K), 1), sh((K), 2)};                   \
+        const float bv = (BV);                                                     \
+        _Pragma("unroll") for (int c = 0; c < 3; c++) res[c] = res[c] + bv * s[c]; \
+        AXES                                                                       \
+    }
+#define GMS_DDIR_AXIS(A, BD)                                                       \
+    {                                                                              \
+        const float bd = (BD);                                                     \
+        _Pragma("unroll") for (int c = 0; c < 3; c++) D[(A) * 3 + c] = __fmaf_rn(bd, s[c], D[(A) * 3 + c]); \
+    }
+    // GMS_SH_FENCE(): an empty asm that every live value passes through, between groups of rows.  It orders nothing in memory; it keeps the
+    // compiler from evaluating all ~50 polynomials up front, which under preprocess_fwd's cap of 96 registers spilled 20-30 of them
+    // (tests/test_preprocess_fwd_resources_cpu.py holds the headline instantiation to no spill).
+#define GMS_SH_FENCE()                                                             \
+    __asm__ volatile("" : "+v"(x), "+v"(y), "+v"(z), "+v"(xx), "+v"(yy), "+v"(zz), "+v"(xy), "+v"(yz), "+v"(xz),       \
+                          "+v"(res[0]), "+v"(res[1]), "+v"(res[2]), "+v"(D[0]), "+v"(D[1]), "+v"(D[2]), "+v"(D[3]), "+v"(D[4]), \
+                          "+v"(D[5]), "+v"(D[6]), "+v"(D[7]), "+v"(D[8]));
+#define GMS_DDIR_X(BD) GMS_DDIR_AXIS(0, BD)
+#define GMS_DDIR_Y(BD) GMS_DDIR_AXIS(1, BD)
+#define GMS_DDIR_Z(BD) GMS_DDIR_AXIS(2, BD)
+#pragma unroll
+    for (int c = 0; c < 3; c++) res[c] = SH_C0 * sh(0, c);
+    if (DEG > 0) {
+        GMS_SH_K(1, -(SH_C1 * y), GMS_DDIR_Y(-SH_C1))
+        GMS_SH_K(2, SH_C1 * z, GMS_DDIR_Z(SH_C1))
+        GMS_SH_K(3, -(SH_C1 * x), GMS_DDIR_X(-SH_C1))
+    }
+    if (DEG > 1) {
+        float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
+        GMS_SH_FENCE()
+        GMS_SH_K(4, SH_C2[0] * xy, GMS_DDIR_X(SH_C2[0] * y) GMS_DDIR_Y(SH_C2[0] * x))
+        GMS_SH_K(5, SH_C2[1] * yz, GMS_DDIR_Y(SH_C2[1] * z) GMS_DDIR_Z(SH_C2[1] * y))
+        GMS_SH_K(6, SH_C2[2] * (2.f * zz - xx - yy), GMS_DDIR_X(-2.f * SH_C2[2] * x) GMS_DDIR_Y(-2.f * SH_C2[2] * y) GMS_DDIR_Z(4.f * SH_C2[2] * z))
+        GMS_SH_FENCE()
+        GMS_SH_K(7, SH_C2[3] * xz, GMS_DDIR_X(SH_C2[3] * z) GMS_DDIR_Z(SH_C2[3] * x))
+        GMS_SH_K(8, SH_C2[4] * (xx - yy), GMS_DDIR_X(2.f * SH_C2[4] * x) GMS_DDIR_Y(-2.f * SH_C2[4] * y))
+        if (DEG > 2) {
+            GMS_SH_FENCE()
+            GMS_SH_K(9, SH_C3[0] * y * (3.f * xx - yy), GMS_DDIR_X(SH_C3[0] * 6.f * xy) GMS_DDIR_Y(SH_C3[0] * (3.f * xx - 3.f * yy)))
+            GMS_SH_K(10, SH_C3[1] * xy * z, GMS_DDIR_X(SH_C3[1] * yz) GMS_DDIR_Y(SH_C3[1] * xz) GMS_DDIR_Z(SH_C3[1] * xy))
+            GMS_SH_K(11, SH_C3[2] * y * (4.f * zz - xx - yy),
+                     GMS_DDIR_X(SH_C3[2] * (-2.f * xy)) GMS_DDIR_Y(SH_C3[2] * (4.f * zz - xx - 3.f * yy)) GMS_DDIR_Z(SH_C3[2] * 8.f * yz))
+            GMS_SH_FENCE()
+            GMS_SH_K(12, SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy),
+                     GMS_DDIR_X(SH_C3[3] * (-6.f * xz)) GMS_DDIR_Y(SH_C3[3] * (-6.f * yz)) GMS_DDIR_Z(SH_C3[3] * (6.f * zz - 3.f * xx - 3.f * yy)))
+            GMS_SH_K(13, SH_C3[4] * x * (4.f * zz - xx - yy),
+                     GMS_DDIR_X(SH_C3[4] * (4.f * zz - 3.f * xx - yy)) GMS_DDIR_Y(SH_C3[4] * (-2.f * xy)) GMS_DDIR_Z(SH_C3[4] * 8.f * xz))
+            GMS_SH_FENCE()
+            GMS_SH_K(14, SH_C3[5] * z * (xx - yy), GMS_DDIR_X(SH_C3[5] * 2.f * xz) GMS_DDIR_Y(SH_C3[5] * (-2.f * yz)) GMS_DDIR_Z(SH_C3[5] * (xx - yy)))
+            GMS_SH_K(15, SH_C3[6] * x * (xx - 3.f * yy), GMS_DDIR_X(SH_C3[6] * (3.f * xx - 3.f * yy)) GMS_DDIR_Y(SH_C3[6] * (-6.f * xy)))
+        }
+    }
+#undef GMS_SH_K
+#undef GMS_SH_FENCE
+#undef GMS_DDIR_X
+#undef GMS_DDIR_Y
+#undef GMS_DDIR_Z
+#undef GMS_DDIR_AXIS
+}
+
+// dL/ddir from the stored 3x3 and the clamp-masked dL/dcolour (fixed order, no contraction: the same bits on every route)
+__device__ __forceinline__ void sh_dir_grad(const float D[9], const float dRGB[3], float gdir[3])
+{
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int a = 0; a < 3; a++) gdir[a] = D[a * 3] * dRGB[0] + D[a * 3 + 1] * dRGB[1] + D[a * 3 + 2] * dRGB[2];
+}
+
 }  // namespace gms

@@ -7,9 +7,9 @@
 //   K8+K9 preprocess_bwd 1 thread / Gaussian: reads the 64-byte record (and clears it), maps the moments to the gradients
 //                        of (pixel mean, conic, opacity) with per-Gaussian constants, then conic -> cov2D -> (cov3D, mean)
 //                        through the EWA Jacobian, pixel mean -> world mean through the projection, inverse depth, SH
-//                        backward (coefficients staged in, gradients staged out through the same LDS rows, so both the
-//                        192-B read and the 192-B write per Gaussian are coalesced float4 streams), cov3D -> scale /
-//                        quaternion.
+//                        backward (no coefficient is read: the direction term is the forward's stored 3x3 times dL/dcolour,
+//                        the gradient rows are basis x dL/dcolour, staged through LDS rows so the 192-B write per Gaussian
+//                        is a coalesced float4 stream), cov3D -> scale / quaternion.
 //
 // Gradient conventions: SURVEY.md appendix A.4/A.5 (straight-through alpha clamp, constant
 // skip tests, clamp masks, 1/(det^2+1e-7), NDC-scaled mean2D gradient).  Two forms are restated from the published
@@ -34,6 +34,7 @@ struct PreBwdArgs {
     int aa;
     const int *radii;
     const uint8_t *clamped;
+    const float *sh_ddir;   // [P][9] d colour / d direction, stored by preprocess_fwd for visible Gaussians (GeomState::sh_ddir)
     float *accum;           // [P,16] gradient records filled by blend_bwd
     int rezero;             // clear each record after reading it
     float *dL_dmean2D, *dL_dopacity, *dL_dcolors;
@@ -44,165 +45,72 @@ struct PreBwdArgs {
     float *mesh_dvertices, *mesh_dalpha, *mesh_dscale, *mesh_dopacity;
 };
 
-// SH backward for one Gaussian.  The coefficient row is read from the lane's LDS row as float4
-// (ds_read_b128, conflict-free at the 52-dword pitch), d loss / d sh is written back in place, the
-// direction gradient is accumulated.  r[k*3+c] lives in registers (all indices are constants).
-// (the arithmetic, on a coefficient row held in registers: r[k*3+c] in, d loss / d sh [k*3+c] out)
+// SH basis values at the unit direction (x, y, z), the `basis_k` of the colour sum (gms_project.h::sh_eval_with_dir_jacobian)
 template <int DEG>
-__device__ __forceinline__ void sh_backward_regs(float *r, float x, float y, float z, const float dRGB[3], float gdir[3])
+__device__ __forceinline__ void sh_basis(float x, float y, float z, float *Y)
 {
-#define GMS_SH_TERM(K, BV, BDX, BDY, BDZ)                                          \
-    {                                                                              \
-        const float bv = (BV), bx = (BDX), by = (BDY), bz = (BDZ);                 \
-        _Pragma("unroll") for (int c = 0; c < 3; c++) {                            \
-            const float w = r[(K) * 3 + c] * dRGB[c];                              \
-            gdir[0] += bx * w; gdir[1] += by * w; gdir[2] += bz * w;               \
-            r[(K) * 3 + c] = bv * dRGB[c];                                         \
-        }                                                                          \
-    }
-    GMS_SH_TERM(0, SH_C0, 0.f, 0.f, 0.f)
-    if (DEG > 0) {
-        GMS_SH_TERM(1, -SH_C1 * y, 0.f, -SH_C1, 0.f)
-        GMS_SH_TERM(2, SH_C1 * z, 0.f, 0.f, SH_C1)
-        GMS_SH_TERM(3, -SH_C1 * x, -SH_C1, 0.f, 0.f)
-    }
+#pragma clang fp contract(on)      // (within an expression only: the same bits in every kernel that inlines this)
+    Y[0] = SH_C0;
+    if (DEG > 0) { Y[1] = -SH_C1 * y; Y[2] = SH_C1 * z; Y[3] = -SH_C1 * x; }
     if (DEG > 1) {
         const float xx = x * x, yy = y * y, zz = z * z;
-        GMS_SH_TERM(4, SH_C2[0] * x * y, SH_C2[0] * y, SH_C2[0] * x, 0.f)
-        GMS_SH_TERM(5, SH_C2[1] * y * z, 0.f, SH_C2[1] * z, SH_C2[1] * y)
-        GMS_SH_TERM(6, SH_C2[2] * (2.f * zz - xx - yy), -2.f * SH_C2[2] * x, -2.f * SH_C2[2] * y, 4.f * SH_C2[2] * z)
-        GMS_SH_TERM(7, SH_C2[3] * x * z, SH_C2[3] * z, 0.f, SH_C2[3] * x)
-        GMS_SH_TERM(8, SH_C2[4] * (xx - yy), 2.f * SH_C2[4] * x, -2.f * SH_C2[4] * y, 0.f)
+        Y[4] = SH_C2[0] * x * y; Y[5] = SH_C2[1] * y * z; Y[6] = SH_C2[2] * (2.f * zz - xx - yy);
+        Y[7] = SH_C2[3] * x * z; Y[8] = SH_C2[4] * (xx - yy);
     }
     if (DEG > 2) {
         const float xx = x * x, yy = y * y, zz = z * z;
-        GMS_SH_TERM(9, SH_C3[0] * y * (3.f * xx - yy), SH_C3[0] * 6.f * x * y, SH_C3[0] * (3.f * xx - 3.f * yy), 0.f)
-        GMS_SH_TERM(10, SH_C3[1] * x * y * z, SH_C3[1] * y * z, SH_C3[1] * x * z, SH_C3[1] * x * y)
-        GMS_SH_TERM(11, SH_C3[2] * y * (4.f * zz - xx - yy), SH_C3[2] * (-2.f * x * y), SH_C3[2] * (4.f * zz - xx - 3.f * yy), SH_C3[2] * 8.f * y * z)
-        GMS_SH_TERM(12, SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy), SH_C3[3] * (-6.f * x * z), SH_C3[3] * (-6.f * y * z), SH_C3[3] * (6.f * zz - 3.f * xx - 3.f * yy))
-        GMS_SH_TERM(13, SH_C3[4] * x * (4.f * zz - xx - yy), SH_C3[4] * (4.f * zz - 3.f * xx - yy), SH_C3[4] * (-2.f * x * y), SH_C3[4] * 8.f * x * z)
-        GMS_SH_TERM(14, SH_C3[5] * z * (xx - yy), SH_C3[5] * 2.f * x * z, SH_C3[5] * (-2.f * y * z), SH_C3[5] * (xx - yy))
-        GMS_SH_TERM(15, SH_C3[6] * x * (xx - 3.f * yy), SH_C3[6] * (3.f * xx - 3.f * yy), SH_C3[6] * (-6.f * x * y), 0.f)
+        Y[9] = SH_C3[0] * y * (3.f * xx - yy); Y[10] = SH_C3[1] * x * y * z; Y[11] = SH_C3[2] * y * (4.f * zz - xx - yy);
+        Y[12] = SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy); Y[13] = SH_C3[4] * x * (4.f * zz - xx - yy);
+        Y[14] = SH_C3[5] * z * (xx - yy); Y[15] = SH_C3[6] * x * (xx - 3.f * yy);
     }
-#undef GMS_SH_TERM
 }
 
-template <int DEG>
-__device__ __forceinline__ void sh_backward(float *row_lds, float x, float y, float z, const float dRGB[3], float gdir[3])
+// One Gaussian's SH gradient row, d loss / d sh[k][c] = basis_k(dir) * dRGB[c], handed to put(k*3+c, value) for all 48 slots of a
+// degree-3 row: zero above the active degree and for a culled Gaussian.  No coefficient enters (the direction term, which does need
+// them, comes from the forward: gms_project.h::sh_eval_with_dir_jacobian).
+template <int DEG, typename PUT>
+__device__ __forceinline__ void sh_grad_row(bool vis, float x, float y, float z, const float dRGB[3], PUT put)
 {
-    constexpr int NQ = ((DEG + 1) * (DEG + 1) * 3 + 3) / 4;
-    float r[NQ * 4];
+    constexpr int NB = (DEG + 1) * (DEG + 1);
+    float Y[16];
+    sh_basis<DEG>(x, y, z, Y);
+    // (a culled Gaussian: dRGB is +0 and so is its basis here, so its products are +0 too -- NB selects instead of one per product)
 #pragma unroll
-    for (int q = 0; q < NQ; q++) {
-        const float4 v = *reinterpret_cast<const float4 *>(row_lds + q * 4);
-        r[4 * q] = v.x; r[4 * q + 1] = v.y; r[4 * q + 2] = v.z; r[4 * q + 3] = v.w;
-    }
-    sh_backward_regs<DEG>(r, x, y, z, dRGB, gdir);
-    // coefficients beyond the active degree inside the last chunk get zero gradient
+    for (int k = 0; k < NB; k++) Y[k] = vis ? Y[k] : 0.f;
 #pragma unroll
-    for (int k = (DEG + 1) * (DEG + 1) * 3; k < NQ * 4; k++) r[k] = 0.f;
+    for (int k = 0; k < 16; k++)
 #pragma unroll
-    for (int q = 0; q < NQ; q++)
-        *reinterpret_cast<float4 *>(row_lds + q * 4) = make_float4(r[4 * q], r[4 * q + 1], r[4 * q + 2], r[4 * q + 3]);
+        for (int c = 0; c < 3; c++) put(k * 3 + c, k < NB ? Y[k < NB ? k : 0] * dRGB[c] : 0.f);
 }
 
-template <int NQ>
-__device__ __forceinline__ void stage_sh_rows_b(const float *shs, int g0, int rows, int rowq, float *wl, int lane)
-{
-    const float4 *src = reinterpret_cast<const float4 *>(shs) + (size_t)g0 * rowq;
-    for (int idx = lane; idx < rows * NQ; idx += WAVE) {
-        const int r = idx / NQ, c = idx - r * NQ;
-        *reinterpret_cast<float4 *>(wl + r * 52 + c * 4) = src[(size_t)r * rowq + c];
-    }
-}
+// The SH gradient rows leave through one LDS image per wave (64 rows).  Split storage keeps the rows as they lie in memory -- 64 x 45
+// floats of dL/d`_features_rest`, contiguous, then the 64 x 3 of dL/d`_features_dc` -- so the wave's rows are one contiguous float4 stream;
+// concatenated storage keeps them at a 52-dword pitch.  (Two halves of 32 rows through 26 KB, which admit five blocks per CU under a cap
+// of 96 registers, were measured as well -- DESIGN.md 7.3; the block keeps the 52 KB and three blocks per CU that
+// tests/test_kernel_resources_cpu.py pins.)
+constexpr int BWD_RESTF = 45;                                        // floats per row of shs_rest (M = 16)
+constexpr int BWD_WAVE_FLOATS = WAVE * SH_PITCH_B;                   // 3 328 >= 64 x 45 + 64 x 3
+static_assert(BWD_WAVE_FLOATS >= WAVE * BWD_RESTF + WAVE * 3, "the split image fits the wave's LDS");
 
 template <bool MESH>
-__global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int pre_bwd_linear)
+__global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int dst_vec)
 {
-    __shared__ __attribute__((aligned(16))) float sh_lds[4 * WAVE * SH_PITCH_B];
+    // Contraction is held to what ONE source expression allows (the front end's choice, the same in both instantiations).  Under the file's
+    // default the optimiser fuses across statements as the surrounding code lets it, and the two instantiations then disagree where
+    // the conic's gradient cancels (det - a c): by 2e-5 of dL/d_scale on a small scene, a hundred times the float atomics' noise
+    // (tests/test_gpu_fused_training.py::test_mesh_backward_inside_preprocess_bwd_equals_the_mesh_backward_launch[203-2] fails under `fast`).
+#pragma clang fp contract(on)
+    __shared__ __attribute__((aligned(16))) float sh_lds[4 * BWD_WAVE_FLOATS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x * BLOCK + tid;
     const bool valid = i < a.P;
     const bool vis = valid && a.radii[i] > 0;
-    float *wl = sh_lds + wave * (WAVE * SH_PITCH_B);
+    float *wl = sh_lds + wave * BWD_WAVE_FLOATS;
     const int rowf = a.M * 3;
-    const bool use_sh = a.shs != nullptr;
-    const bool vec_ok = use_sh && (rowf % 4 == 0) && (rowf <= 48);
-    const int nb = (a.D + 1) * (a.D + 1);
+    const bool use_sh = a.shs != nullptr;             // (`shs` / `shs_rest` select the path and the gradient layout; neither is dereferenced)
     const int g0 = blockIdx.x * BLOCK + wave * WAVE;
     const int rows = min(WAVE, a.P - g0);
-
-    // stage the SH rows of this wave's 64 Gaussians into LDS (coalesced)
     const bool split = a.shs_rest != nullptr;         // DC [P,3] + REST [P,45] stored separately (M = 16)
-    constexpr int RESTF = 45;
-    // Round 5, split degree-3 storage (the training layout): the wave's coefficient block goes global -> LDS by LDS-DMA as it lies (64 rows
-    // of `_features_rest` = 11 520 contiguous bytes, row pitch 45 dwords, then the 768 bytes of `_features_dc`), the gradients go back
-    // into the same linear image and leave as one contiguous float4 stream: no scatter with a division by 45 on either side.
-    const bool linear = use_sh && split && a.D == 3 && pre_bwd_linear;
-    float *const lin_dc = wl + WAVE * RESTF;
-    if (linear) {
-        if (__any(vis)) {
-            const int rr = max(rows, 0);
-            const float *sp = a.shs_rest + (size_t)g0 * RESTF;       // g0 % 64 == 0: 16-byte aligned
-            const int nfl = rr * RESTF, nd = rr * 3;
-#pragma unroll
-            for (int j = 0; j < 12; j++) {
-                const int e4 = (lane + WAVE * j) * 4;
-                if (e4 + 3 < nfl)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(sp + e4),
-                                                     (__attribute__((address_space(3))) void *)(wl + WAVE * 4 * j), 16, 0, 0);
-            }
-            if (lane * 4 + 3 < nd)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.shs + (size_t)g0 * 3 + lane * 4),
-                                                 (__attribute__((address_space(3))) void *)lin_dc, 16, 0, 0);
-            if (rr < WAVE) {          // last wave of the array: the (at most one) 16-byte chunk of each block that straddles its end
-                for (int e = (nfl & ~3) + lane; e < nfl; e += WAVE) wl[e] = sp[e];
-                for (int e = (nd & ~3) + lane; e < nd; e += WAVE) lin_dc[e] = a.shs[(size_t)g0 * 3 + e];
-            }
-            __builtin_amdgcn_s_waitcnt(0x0f70);        // vmcnt(0): the LDS-DMA copies have landed
-        }
-        wave_sync();      // the rows are this wave's own
-    } else if (use_sh && split) {
-        if (__any(vis)) {
-            for (int e = lane; e < rows * 3; e += WAVE) wl[(e / 3) * SH_PITCH_B + (e % 3)] = a.shs[(size_t)g0 * 3 + e];
-            const int need = nb * 3 - 3;              // floats of each REST row the active degree uses
-            if (need == RESTF) {                      // full rows: flat float4 copy of the wave's contiguous block
-                const float *sp = a.shs_rest + (size_t)g0 * RESTF;
-                const int nfl = rows * RESTF;
-                for (int e4 = lane * 4; e4 < nfl; e4 += WAVE * 4) {
-                    float v4[4];
-                    if (e4 + 3 < nfl) { const float4 v = *reinterpret_cast<const float4 *>(sp + e4); v4[0] = v.x; v4[1] = v.y; v4[2] = v.z; v4[3] = v.w; }
-                    else { for (int t = 0; t < 4; t++) v4[t] = e4 + t < nfl ? sp[e4 + t] : 0.f; }
-#pragma unroll
-                    for (int t = 0; t < 4; t++) {
-                        const int e = e4 + t;
-                        if (e < nfl) wl[(e / RESTF) * SH_PITCH_B + 3 + (e % RESTF)] = v4[t];
-                    }
-                }
-            } else {
-                for (int e = lane; e < rows * need; e += WAVE) {
-                    const int r = e / need, c = e - r * need;
-                    wl[r * SH_PITCH_B + 3 + c] = a.shs_rest[((size_t)g0 + r) * RESTF + c];
-                }
-            }
-        }
-        wave_sync();      // the rows are this wave's own
-    } else if (use_sh) {
-        if (vec_ok) {
-            if (__any(vis)) {
-                const int rowq = rowf / 4;
-                switch (a.D) {
-                case 0: stage_sh_rows_b<1>(a.shs, g0, rows, rowq, wl, lane); break;
-                case 1: stage_sh_rows_b<3>(a.shs, g0, rows, rowq, wl, lane); break;
-                case 2: stage_sh_rows_b<7>(a.shs, g0, rows, rowq, wl, lane); break;
-                default: stage_sh_rows_b<12>(a.shs, g0, rows, rowq, wl, lane); break;
-                }
-            }
-        } else if (vis) {
-            for (int k = 0; k < nb * 3; k++) wl[lane * SH_PITCH_B + k] = a.shs[(size_t)i * rowf + k];
-        }
-        wave_sync();      // the rows are this wave's own
-    }
 
     float dmean[3] = {0.f, 0.f, 0.f};
     float dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -227,10 +135,18 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
     const float acc_col[3] = {gb.z, gb.w, gc4.x};
     const float acc_id = gc4.y;
     float dop = 0.f;
-    float *row = wl + lane * SH_PITCH_B;
-
+    float px = 0.f, py = 0.f, pz = 0.f;
+    float dirx = 0.f, diry = 0.f, dirz = 0.f, dir_inv = 0.f;          // unit view direction and 1 / distance
     if (vis) {
-        const float px = a.means3D[3 * (size_t)i], py = a.means3D[3 * (size_t)i + 1], pz = a.means3D[3 * (size_t)i + 2];
+        px = a.means3D[3 * (size_t)i]; py = a.means3D[3 * (size_t)i + 1]; pz = a.means3D[3 * (size_t)i + 2];
+        if (use_sh) {
+            const float ddx = px - a.campos[0], ddy = py - a.campos[1], ddz = pz - a.campos[2];
+            dir_inv = 1.f / sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
+            dirx = ddx * dir_inv; diry = ddy * dir_inv; dirz = ddz * dir_inv;
+            const unsigned cl = a.clamped[i];
+#pragma unroll
+            for (int c = 0; c < 3; c++) dcol_sh[c] = ((cl >> c) & 1u) ? 0.f : acc_col[c];
+        }
         const float *V = a.view, *Mx = a.proj;
         float vx, vy, vz;
         view_transform(V, px, py, pz, vx, vy, vz);
@@ -311,36 +227,13 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
         for (int r = 0; r < 3; r++)
             dmean[r] += (Mx[4 * r + 0] * mw - Mx[4 * r + 3] * mul1) * gmx + (Mx[4 * r + 1] * mw - Mx[4 * r + 3] * mul2) * gmy;
 
-        // colour
+        // colour: the direction term is the forward's d colour / d direction times dL/dcolour
         if (use_sh) {
-            const float ddx = px - a.campos[0], ddy = py - a.campos[1], ddz = pz - a.campos[2];
-            const float inv = 1.f / sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
-            const float x = ddx * inv, y = ddy * inv, z = ddz * inv;
-            const unsigned cl = a.clamped[i];
-            float dRGB[3];
+            const float x = dirx, y = diry, z = dirz, inv = dir_inv;
+            float D[9], gdir[3];
 #pragma unroll
-            for (int c = 0; c < 3; c++) { dRGB[c] = ((cl >> c) & 1u) ? 0.f : acc_col[c]; dcol_sh[c] = dRGB[c]; }
-            float gdir[3] = {0.f, 0.f, 0.f};
-            if (linear) {
-                float r[48];
-#pragma unroll
-                for (int c = 0; c < 3; c++) r[c] = lin_dc[lane * 3 + c];
-#pragma unroll
-                for (int m = 0; m < RESTF; m++) r[3 + m] = wl[lane * RESTF + m];
-                sh_backward_regs<3>(r, x, y, z, dRGB, gdir);
-                if (!a.dL_dcolor_sh) {          // (factorised mode writes no SH gradient rows)
-#pragma unroll
-                    for (int c = 0; c < 3; c++) lin_dc[lane * 3 + c] = r[c];
-#pragma unroll
-                    for (int m = 0; m < RESTF; m++) wl[lane * RESTF + m] = r[3 + m];
-                }
-            } else
-            switch (a.D) {
-            case 0: sh_backward<0>(row, x, y, z, dRGB, gdir); break;
-            case 1: sh_backward<1>(row, x, y, z, dRGB, gdir); break;
-            case 2: sh_backward<2>(row, x, y, z, dRGB, gdir); break;
-            default: sh_backward<3>(row, x, y, z, dRGB, gdir); break;
-            }
+            for (int j = 0; j < 9; j++) D[j] = a.sh_ddir[(size_t)i * GeomState::SH_DDIR + j];
+            sh_dir_grad(D, dcol_sh, gdir);
             const float dd = x * gdir[0] + y * gdir[1] + z * gdir[2];
             dmean[0] += (gdir[0] - x * dd) * inv;
             dmean[1] += (gdir[1] - y * dd) * inv;
@@ -381,74 +274,7 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
         }
     }
 
-    // ---- SH gradient rows: zero what was not written, then stream the wave's rows out coalesced
-    // (factorised mode: dL/dsh = Y(dir) x dL/dcolour is formed later, by sh_grad_expand, from the [P,3] factor written below)
-    if (use_sh && a.dL_dcolor_sh) {
-    } else if (linear) {
-        if (!vis) {          // culled Gaussian: a zero gradient row
-#pragma unroll
-            for (int c = 0; c < 3; c++) lin_dc[lane * 3 + c] = 0.f;
-#pragma unroll
-            for (int m = 0; m < RESTF; m++) wl[lane * RESTF + m] = 0.f;
-        }
-        wave_sync();      // the rows are this wave's own
-        if (rows > 0) {
-            const int nfl = rows * RESTF, nd = rows * 3;
-            float *dp = a.dL_dsh_rest + (size_t)g0 * RESTF, *dd = a.dL_dsh + (size_t)g0 * 3;
-#pragma unroll
-            for (int j = 0; j < 12; j++) {
-                const int e4 = (lane + WAVE * j) * 4;
-                // Non-temporal: the 54 MB of dL/dSH are written once and read by nobody in this call.  As plain stores the launch had two
-                // speeds, 45 us in most processes and 53 in about one of four (same binary, same inputs: it goes with where the allocator
-                // put the buffers); streamed past the caches it takes 44 us in every one of ten runs (profiles/r06x4_*, r06x5_*).
-                if (e4 + 3 < nfl) {
-                    typedef float v4f __attribute__((ext_vector_type(4)));
-                    __builtin_nontemporal_store(*reinterpret_cast<const v4f *>(wl + e4), reinterpret_cast<v4f *>(dp + e4));
-                }
-                else for (int t = 0; t < 4; t++) if (e4 + t < nfl) dp[e4 + t] = wl[e4 + t];
-            }
-            if (lane * 4 + 3 < nd) *reinterpret_cast<float4 *>(dd + lane * 4) = *reinterpret_cast<const float4 *>(lin_dc + lane * 4);
-            else for (int t = 0; t < 4; t++) if (lane * 4 + t < nd) dd[lane * 4 + t] = lin_dc[lane * 4 + t];
-        }
-    } else if (use_sh && split) {
-        for (int q = vis ? (nb * 3 + 3) / 4 : 0; q < 12; q++)
-            *reinterpret_cast<float4 *>(row + q * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-        wave_sync();      // the rows are this wave's own
-        if (rows > 0) {
-            for (int e = lane; e < rows * 3; e += WAVE) a.dL_dsh[(size_t)g0 * 3 + e] = wl[(e / 3) * SH_PITCH_B + (e % 3)];
-            float *dp = a.dL_dsh_rest + (size_t)g0 * RESTF;
-            const int nfl = rows * RESTF;
-            for (int e4 = lane * 4; e4 < nfl; e4 += WAVE * 4) {
-                float v4[4];
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    const int e = e4 + t;
-                    v4[t] = e < nfl ? wl[(e / RESTF) * SH_PITCH_B + 3 + (e % RESTF)] : 0.f;
-                }
-                if (e4 + 3 < nfl) *reinterpret_cast<float4 *>(dp + e4) = make_float4(v4[0], v4[1], v4[2], v4[3]);
-                else for (int t = 0; t < 4; t++) if (e4 + t < nfl) dp[e4 + t] = v4[t];
-            }
-        }
-    } else if (use_sh) {
-        const int used = vis ? nb * 3 : 0;
-        if (vec_ok) {
-            // chunks the SH backward did not write (culled Gaussian, or coefficients above the active degree)
-            const int rowq = rowf / 4;
-            for (int q = vis ? (nb * 3 + 3) / 4 : 0; q < rowq; q++)
-                *reinterpret_cast<float4 *>(row + q * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-            wave_sync();      // the rows are this wave's own
-            if (rows > 0) {
-                float4 *dst = reinterpret_cast<float4 *>(a.dL_dsh + (size_t)g0 * rowf);
-                for (int idx = lane; idx < rows * rowq; idx += WAVE) {
-                    int r = idx / rowq, c = idx - r * rowq;
-                    dst[(size_t)r * rowq + c] = *reinterpret_cast<const float4 *>(wl + r * SH_PITCH_B + c * 4);
-                }
-            }
-        } else if (valid) {
-            for (int k = 0; k < rowf; k++) a.dL_dsh[(size_t)i * rowf + k] = k < used ? row[k] : 0.f;
-        }
-    }
-    if (!valid) return;
+    if (valid) {
     if (MESH) {
         // the frame came straight from the mesh (gmsplat.h, ABI 8): on through the face -> Gaussian parameterization from registers
         const float gs[3] = {dscale[0], dscale[1], dscale[2]}, gq[4] = {drot[0], drot[1], drot[2], drot[3]};
@@ -462,7 +288,7 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
         a.dL_dcolor_sh[3 * (size_t)a.P] = a.campos[0]; a.dL_dcolor_sh[3 * (size_t)a.P + 1] = a.campos[1]; a.dL_dcolor_sh[3 * (size_t)a.P + 2] = a.campos[2];
     }
     if (a.dL_dcolor_sh) { a.dL_dcolor_sh[3 * (size_t)i] = dcol_sh[0]; a.dL_dcolor_sh[3 * (size_t)i + 1] = dcol_sh[1]; a.dL_dcolor_sh[3 * (size_t)i + 2] = dcol_sh[2]; }
-    if (MESH) return;
+    if (!MESH) {
     a.dL_dmeans3D[3 * (size_t)i] = dmean[0]; a.dL_dmeans3D[3 * (size_t)i + 1] = dmean[1]; a.dL_dmeans3D[3 * (size_t)i + 2] = dmean[2];
     if (a.cov3Dp) {
         if (a.dL_dcov3D)
@@ -471,6 +297,70 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
     } else {
         a.dL_dscales[3 * (size_t)i] = dscale[0]; a.dL_dscales[3 * (size_t)i + 1] = dscale[1]; a.dL_dscales[3 * (size_t)i + 2] = dscale[2];
         *reinterpret_cast<float4 *>(a.dL_drots + 4 * (size_t)i) = make_float4(drot[0], drot[1], drot[2], drot[3]);
+    }
+    }
+    }
+    // ---- SH gradient rows, last (they need the direction and dL/dcolour only; behind everything else no other pointer or matrix is
+    // held in scalar registers across them): every lane writes its row (zeros for a culled Gaussian) into LDS, the wave streams them out coalesced
+    // (factorised mode: dL/dsh = Y(dir) x dL/dcolour is formed later, by sh_grad_expand, from the [P,3] factor written above)
+    if (use_sh && !a.dL_dcolor_sh && rows > 0) {
+        // (the view direction is formed again from the mean, the same statements as above: three registers fewer across the tail)
+        float rdx = 0.f, rdy = 0.f, rdz = 0.f;
+        if (vis) {
+            const float ddx = a.means3D[3 * (size_t)i] - a.campos[0], ddy = a.means3D[3 * (size_t)i + 1] - a.campos[1], ddz = a.means3D[3 * (size_t)i + 2] - a.campos[2];
+            const float dinv = 1.f / sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
+            rdx = ddx * dinv; rdy = ddy * dinv; rdz = ddz * dinv;
+        }
+        float *const dcw = wl + WAVE * BWD_RESTF;          // split storage: the wave's 64 x 3 DC gradients
+        auto write_row = [&](auto put) {
+            switch (a.D) {
+            case 0: sh_grad_row<0>(vis, rdx, rdy, rdz, dcol_sh, put); break;
+            case 1: sh_grad_row<1>(vis, rdx, rdy, rdz, dcol_sh, put); break;
+            case 2: sh_grad_row<2>(vis, rdx, rdy, rdz, dcol_sh, put); break;
+            default: sh_grad_row<3>(vis, rdx, rdy, rdz, dcol_sh, put); break;
+            }
+        };
+        if (split) {
+            float *const d0 = dcw + lane * 3, *const d1 = wl + lane * BWD_RESTF - 3;      // slots 0..2 and 3..47
+            write_row([&](int e, float v) { (e < 3 ? d0 : d1)[e] = v; });
+        } else {
+            float *const d0 = wl + lane * SH_PITCH_B;
+            const int lim = min(rowf, 48);
+            write_row([&](int e, float v) { if (e < lim) d0[e] = v; });
+        }
+        wave_sync();      // the rows are this wave's own
+        if (split) {
+            const int nfl = rows * BWD_RESTF, nd = rows * 3;
+            float *dp = a.dL_dsh_rest + (size_t)g0 * BWD_RESTF, *dd = a.dL_dsh + (size_t)g0 * 3;      // g0 % 64 == 0: 16-byte aligned when the bases are
+            if (dst_vec) {
+                // Non-temporal: the 54 MB of dL/dSH are written once and read by nobody in this call.  As plain stores the launch had two
+                // speeds, 45 us in most processes and 53 in about one of four (same binary, same inputs: it goes with where the allocator
+                // put the buffers); streamed past the caches it has one (profiles/r06x4_*, r06x5_*).
+                typedef float v4f __attribute__((ext_vector_type(4)));
+#pragma unroll
+                for (int j = 0; j < 12; j++) {
+                    const int e4 = (lane + WAVE * j) * 4;
+                    if (e4 + 3 < nfl) __builtin_nontemporal_store(*reinterpret_cast<const v4f *>(wl + e4), reinterpret_cast<v4f *>(dp + e4));
+                }
+                const int e = (nfl & ~3) + lane;          // (the last wave of the array: up to three floats behind the last whole chunk)
+                if (e < nfl) dp[e] = wl[e];
+                if (lane * 4 + 3 < nd) *reinterpret_cast<float4 *>(dd + lane * 4) = *reinterpret_cast<const float4 *>(dcw + lane * 4);
+                const int ed = (nd & ~3) + lane;
+                if (ed < nd) dd[ed] = dcw[ed];
+            } else {
+                for (int e = lane; e < nfl; e += WAVE) dp[e] = wl[e];
+                for (int e = lane; e < nd; e += WAVE) dd[e] = dcw[e];
+            }
+        } else if (rowf == 48) {      // concatenated storage, M = 16: twelve float4 per row
+            float4 *dst = reinterpret_cast<float4 *>(a.dL_dsh + (size_t)g0 * 48);
+            for (int idx = lane; idx < rows * 12; idx += WAVE) {
+                const int r = idx / 12, c = idx - r * 12;
+                dst[idx] = *reinterpret_cast<const float4 *>(wl + r * SH_PITCH_B + c * 4);
+            }
+        } else if (valid) {      // any other storage width: the lane copies its own row
+            const float *row = wl + lane * SH_PITCH_B;
+            for (int k = 0; k < rowf; k++) a.dL_dsh[(size_t)i * rowf + k] = k < 48 ? row[k] : 0.f;
+        }
     }
 }
 
@@ -524,8 +414,8 @@ __global__ void __launch_bounds__(BLOCK) det_reduce_kernel(int P, int gx, int gy
 // dL/dsh[k][c] of one view is the outer product Y_k(dir) * dL/dcolour_c (clamp mask folded into dL/dcolour), and dir depends
 // only on the Gaussian's position and that view's camera centre.  A multi-view step therefore exchanges the [P,3] factors of
 // its views (3 floats per Gaussian per view instead of 48) and forms  sum_v Y(dir_v) (x) g_v  here, views in index order.
-// The basis values are the `bv` terms of sh_backward above, same expressions: with one view this reproduces the dense
-// gradient bit for bit.
+// The basis values are sh_basis, which the dense rows of preprocess_bwd are formed from as well: with one view this reproduces
+// the dense gradient bit for bit.
 struct ShExpandArgs {
     int P, D, M, V;
     const float *means3D;      // [P,3]
@@ -536,24 +426,6 @@ struct ShExpandArgs {
     float *dL_dsh_rest;
     int accumulate;            // add to the destination instead of overwriting it
 };
-
-template <int DEG>
-__device__ __forceinline__ void sh_basis(float x, float y, float z, float *Y)
-{
-    Y[0] = SH_C0;
-    if (DEG > 0) { Y[1] = -SH_C1 * y; Y[2] = SH_C1 * z; Y[3] = -SH_C1 * x; }
-    if (DEG > 1) {
-        const float xx = x * x, yy = y * y, zz = z * z;
-        Y[4] = SH_C2[0] * x * y; Y[5] = SH_C2[1] * y * z; Y[6] = SH_C2[2] * (2.f * zz - xx - yy);
-        Y[7] = SH_C2[3] * x * z; Y[8] = SH_C2[4] * (xx - yy);
-    }
-    if (DEG > 2) {
-        const float xx = x * x, yy = y * y, zz = z * z;
-        Y[9] = SH_C3[0] * y * (3.f * xx - yy); Y[10] = SH_C3[1] * x * y * z; Y[11] = SH_C3[2] * y * (4.f * zz - xx - yy);
-        Y[12] = SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy); Y[13] = SH_C3[4] * x * (4.f * zz - xx - yy);
-        Y[14] = SH_C3[5] * z * (xx - yy); Y[15] = SH_C3[6] * x * (xx - 3.f * yy);
-    }
-}
 
 template <int DEG>
 __global__ void __launch_bounds__(BLOCK) sh_grad_expand_kernel(ShExpandArgs a)
@@ -681,16 +553,16 @@ extern "C" int32_t gms_rasterize_backward(const GmsRasterBackwardArgs *A, void *
     p.means3D = A->means3D; p.shs = A->shs; p.shs_rest = A->shs_rest; p.colors = A->colors_precomp; p.opac = A->opacities; p.scales = A->scales;
     p.rots = A->rotations; p.cov3Dp = A->cov3D_precomp; p.view = A->viewmatrix; p.proj = A->projmatrix; p.campos = A->campos;
     p.mod = A->scale_modifier; p.scale_grad_mod = upstream_scale_mod_grad() ? 1.f : A->scale_modifier; p.tanx = A->tan_fovx; p.tany = A->tan_fovy; p.aa = A->antialiasing; p.radii = A->radii;
-    p.clamped = geom.clamped; p.accum = A->grad_accum; p.rezero = fault_mode() == 3 ? 0 : A->grad_accum_rezero; p.dL_dmean2D = A->dL_dmeans2D;
+    p.clamped = geom.clamped; p.sh_ddir = geom.sh_ddir; p.accum = A->grad_accum; p.rezero = fault_mode() == 3 ? 0 : A->grad_accum_rezero; p.dL_dmean2D = A->dL_dmeans2D;
     p.dL_dcolors = A->colors_precomp ? A->dL_dcolors : nullptr; p.dL_dcolor_sh = (A->shs && A->sh_factor_mode) ? A->dL_dcolors : nullptr; p.campos_row = A->factor_campos_row; p.dL_dopacity = A->dL_dopacity; p.dL_dmeans3D = A->dL_dmeans3D;
     p.dL_dcov3D = A->dL_dcov3D; p.dL_dsh = A->dL_dsh; p.dL_dsh_rest = A->dL_dsh_rest; p.dL_dscales = A->dL_dscales; p.dL_drots = A->dL_drotations;
-    const int lin_ok = A->shs && A->shs_rest && A->D == 3 && (((uintptr_t)A->shs) & 15u) == 0 && (((uintptr_t)A->shs_rest) & 15u) == 0 &&
-                       (A->sh_factor_mode || ((((uintptr_t)A->dL_dsh) & 15u) == 0 && (((uintptr_t)A->dL_dsh_rest) & 15u) == 0));
+    // split storage: the gradient rows leave as float4 where both destinations are 16-byte aligned
+    const int dst_vec = A->shs_rest && !A->sh_factor_mode && (((uintptr_t)A->dL_dsh) & 15u) == 0 && (((uintptr_t)A->dL_dsh_rest) & 15u) == 0;
     if (mesh) {
         p.mesh = *mesh; p.mesh_dvertices = A->mesh_dL_dvertices; p.mesh_dalpha = A->mesh_dL_dalpha; p.mesh_dscale = A->mesh_dL_dscale; p.mesh_dopacity = A->mesh_dL_d_opacity;
-        GMS_LAUNCH(GMS_K_PREPROCESS_BWD, stream, preprocess_bwd_kernel<true><<<(unsigned)((P + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(p, lin_ok));
+        GMS_LAUNCH(GMS_K_PREPROCESS_BWD, stream, preprocess_bwd_kernel<true><<<(unsigned)((P + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(p, dst_vec));
     } else {
-        GMS_LAUNCH(GMS_K_PREPROCESS_BWD, stream, preprocess_bwd_kernel<false><<<(unsigned)((P + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(p, lin_ok));
+        GMS_LAUNCH(GMS_K_PREPROCESS_BWD, stream, preprocess_bwd_kernel<false><<<(unsigned)((P + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(p, dst_vec));
     }
     GMS_KERNEL_CHECK(A->debug, stream, "preprocess_bwd");
     if (fault_mode() == 4 && A->dL_dscales)      // negative control: dL/dscale.x of every 1000th Gaussian off by 2e-3

@@ -69,32 +69,6 @@ struct PreArgs {
     float *k0_xyz, *k0_scale, *k0_rot, *k0_opac;   // ... and stored here for the backward (training frames; NULL: forward-only frame)
 };
 
-// SH -> RGB (before +0.5/clamp) for one channel from the coefficient row r[k*3+c] held in registers;
-// same operation order as utils/sh_utils.py:57-112 evaluated per channel.
-template <int DEG>
-__device__ __forceinline__ float sh_eval_channel(const float *row, int c, float x, float y, float z)
-{
-#pragma clang fp contract(off)
-    float res = SH_C0 * row[0 * 3 + c];
-    if (DEG > 0) {
-        res = res - SH_C1 * y * row[1 * 3 + c] + SH_C1 * z * row[2 * 3 + c] - SH_C1 * x * row[3 * 3 + c];
-        if (DEG > 1) {
-            float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-            res = res + SH_C2[0] * xy * row[4 * 3 + c] + SH_C2[1] * yz * row[5 * 3 + c] +
-                  SH_C2[2] * (2.f * zz - xx - yy) * row[6 * 3 + c] + SH_C2[3] * xz * row[7 * 3 + c] +
-                  SH_C2[4] * (xx - yy) * row[8 * 3 + c];
-            if (DEG > 2) {
-                res = res + SH_C3[0] * y * (3.f * xx - yy) * row[9 * 3 + c] + SH_C3[1] * xy * z * row[10 * 3 + c] +
-                      SH_C3[2] * y * (4.f * zz - xx - yy) * row[11 * 3 + c] +
-                      SH_C3[3] * z * (2.f * zz - 3.f * xx - 3.f * yy) * row[12 * 3 + c] +
-                      SH_C3[4] * x * (4.f * zz - xx - yy) * row[13 * 3 + c] + SH_C3[5] * z * (xx - yy) * row[14 * 3 + c] +
-                      SH_C3[6] * x * (xx - 3.f * yy) * row[15 * 3 + c];
-            }
-        }
-    }
-    return res;
-}
-
 // Stage the first NQ float4 chunks of `rows` consecutive SH rows into the wave's LDS region with
 // coalesced loads (each wave instruction moves 1 KiB), pitch SH_PITCH dwords per row.
 template <int NQ>
@@ -107,9 +81,10 @@ __device__ __forceinline__ void stage_sh_rows(const float *shs, int g0, int rows
     }
 }
 
-// Read the lane's row back as float4 (ds_read_b128, conflict-free at a 52-dword pitch) and evaluate.
+// Read the lane's row back as float4 (ds_read_b128, conflict-free at a 52-dword pitch) and evaluate the colour and its
+// direction derivative `ddir` (gms_project.h::sh_eval_with_dir_jacobian, what preprocess_bwd needs of the coefficients).
 template <int DEG>
-__device__ __forceinline__ void sh_colour(const float *row_lds, float x, float y, float z, float rgb[3], unsigned &clampbits)
+__device__ __forceinline__ void sh_colour(const float *row_lds, float x, float y, float z, float rgb[3], unsigned &clampbits, float ddir[9])
 {
     constexpr int NQ = ((DEG + 1) * (DEG + 1) * 3 + 3) / 4;
     float r[NQ * 4];
@@ -118,12 +93,22 @@ __device__ __forceinline__ void sh_colour(const float *row_lds, float x, float y
         const float4 v = *reinterpret_cast<const float4 *>(row_lds + q * 4);
         r[4 * q] = v.x; r[4 * q + 1] = v.y; r[4 * q + 2] = v.z; r[4 * q + 3] = v.w;
     }
+    float res[3];
+    sh_eval_with_dir_jacobian<DEG>([&](int k, int c) { return r[k * 3 + c]; }, x, y, z, res, ddir);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-        float v = sh_eval_channel<DEG>(r, c, x, y, z) + 0.5f;
+        float v = res[c] + 0.5f;
         if (v < 0.f) { clampbits |= 1u << c; v = 0.f; }
         rgb[c] = v;
     }
+}
+
+// the nine floats of a visible Gaussian's direction derivative (GeomState::sh_ddir)
+__device__ __forceinline__ void store_sh_ddir(float *sh_ddir, int i, const float ddir[9])
+{
+    float *d = sh_ddir + (size_t)i * GeomState::SH_DDIR;
+#pragma unroll
+    for (int j = 0; j < 9; j++) d[j] = ddir[j];
 }
 
 // (a two-stream forward -- this kernel cut into a geometry launch and an SH -> RGB launch on a second stream beside scan / emit /
@@ -318,7 +303,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsP
             const int r0 = half * DMA_HALF_ROWS;                             // first row of this half
             const int hrows = max(0, min(rows - r0, DMA_HALF_ROWS));
             if (half == 1) {
-                wave_sync();                           // every lane of the first half has its coefficients in registers
+                wave_sync();                           // (fence: the first half's reads of the LDS rows, inside sh_eval_with_dir_jacobian, are done before the DMA below overwrites them)
                 const int nfl = hrows * RESTF;
 #pragma unroll
                 for (int j = 0; j < DMA_HALF_Q; j++) {
@@ -339,17 +324,19 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsP
             __builtin_amdgcn_s_waitcnt(0x0f70);        // vmcnt(0): the LDS-DMA copies have landed
             wave_sync();                               // the rows are this wave's own
             if (vis && (lane >> 5) == half) {
-                float r[48];
-#pragma unroll
-                for (int c = 0; c < 3; c++) r[c] = wl[DMA_REST_FLOATS + lane * 3 + c];
-#pragma unroll
-                for (int m = 0; m < RESTF; m++) r[3 + m] = wl[(lane - r0) * RESTF + m];
+                // colour at the ACTIVE degree and its direction derivative, straight from the LDS rows (one read per coefficient); the
+                // derivative is stored at once: nine accumulators that do not outlive the half
+                const float *dcrow = wl + DMA_REST_FLOATS + lane * 3;
+                const float *rrow = wl + (lane - r0) * RESTF - 3;
+                float res[3], ddir[9];
+                sh_eval_with_dir_jacobian<SHDEG>([&](int k, int c) { return k == 0 ? dcrow[c] : rrow[k * 3 + c]; }, dxc, dyc, dzc, res, ddir);
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
-                    float v = sh_eval_channel<SHDEG>(r, c, dxc, dyc, dzc) + 0.5f;          // (the ACTIVE degree: what sh_colour<SHDEG> evaluates)
+                    float v = res[c] + 0.5f;
                     if (v < 0.f) { clampbits |= 1u << c; v = 0.f; }
                     rgb[c] = v;
                 }
+                store_sh_ddir(a.geom.sh_ddir, i, ddir);
             }
         }
     } else if (SHDEG >= 0) {
@@ -382,7 +369,9 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsP
         if (vis) {
             float dx = px - a.campos[0], dy = py - a.campos[1], dz = pz - a.campos[2];
             float inv = 1.f / sqrtf(dx * dx + dy * dy + dz * dz);
-            sh_colour<(SHDEG >= 0 ? SHDEG : 0)>(wl + lane * SH_PITCH, dx * inv, dy * inv, dz * inv, rgb, clampbits);
+            float ddir[9];
+            sh_colour<(SHDEG >= 0 ? SHDEG : 0)>(wl + lane * SH_PITCH, dx * inv, dy * inv, dz * inv, rgb, clampbits, ddir);
+            store_sh_ddir(a.geom.sh_ddir, i, ddir);
         }
     } else if (a.shs) {
         const int nb = (a.D + 1) * (a.D + 1);
@@ -409,12 +398,14 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsP
             float inv = 1.f / sqrtf(dx * dx + dy * dy + dz * dz);
             float x = dx * inv, y = dy * inv, z = dz * inv;
             const float *row = wl + lane * SH_PITCH;
+            float ddir[9];
             switch (a.D) {
-            case 0: sh_colour<0>(row, x, y, z, rgb, clampbits); break;
-            case 1: sh_colour<1>(row, x, y, z, rgb, clampbits); break;
-            case 2: sh_colour<2>(row, x, y, z, rgb, clampbits); break;
-            default: sh_colour<3>(row, x, y, z, rgb, clampbits); break;
+            case 0: sh_colour<0>(row, x, y, z, rgb, clampbits, ddir); break;
+            case 1: sh_colour<1>(row, x, y, z, rgb, clampbits, ddir); break;
+            case 2: sh_colour<2>(row, x, y, z, rgb, clampbits, ddir); break;
+            default: sh_colour<3>(row, x, y, z, rgb, clampbits, ddir); break;
             }
+            store_sh_ddir(a.geom.sh_ddir, i, ddir);
         }
     } else if (vis) {
         rgb[0] = a.colors[3 * (size_t)i]; rgb[1] = a.colors[3 * (size_t)i + 1]; rgb[2] = a.colors[3 * (size_t)i + 2];

@@ -10,6 +10,7 @@
 
 #include "gms_common.h"
 #include "gms_blend.h"
+#include "gms_project.h"
 
 namespace gms {
 
@@ -61,7 +62,46 @@ __global__ void __launch_bounds__(256) test_fx_kernel(int n, const float *y, con
     back[i] = fx_to_float(v0, k[i]);
 }
 
+// rows [n][16][3], dirs [n][3] (taken as given: not normalised here) -> out [n][9] (row a*3+c), at active degree `deg`
+__global__ void __launch_bounds__(256) test_sh_dir_jacobian_kernel(int n, int deg, const float *rows, const float *dirs, float *out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float *r = rows + (size_t)i * 48;
+    const float x = dirs[3 * (size_t)i], y = dirs[3 * (size_t)i + 1], z = dirs[3 * (size_t)i + 2];
+    auto sh = [&](int k, int c) { return r[k * 3 + c]; };
+    float D[9], colour[3];
+    switch (deg) {
+    case 0: sh_eval_with_dir_jacobian<0>(sh, x, y, z, colour, D); break;
+    case 1: sh_eval_with_dir_jacobian<1>(sh, x, y, z, colour, D); break;
+    case 2: sh_eval_with_dir_jacobian<2>(sh, x, y, z, colour, D); break;
+    default: sh_eval_with_dir_jacobian<3>(sh, x, y, z, colour, D); break;
+    }
+    for (int j = 0; j < 9; j++) out[9 * (size_t)i + j] = D[j];
+}
+
 }  // namespace gms
+
+// host buffers in, host buffers out; returns 0 or a negative hipError (-1: deg outside 0..3)
+extern "C" int32_t gms_test_sh_dir_jacobian(int32_t n, int32_t deg, const float *rows_host, const float *dirs_host, float *out_host)
+{
+    if (deg < 0 || deg > 3) return -1;
+    if (n <= 0) return 0;
+    float *dr = nullptr, *dd = nullptr, *dout = nullptr;
+    hipError_t e = hipMalloc(&dr, (size_t)n * 48 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&dd, (size_t)n * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc(&dout, (size_t)n * 9 * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(dr, rows_host, (size_t)n * 48 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dd, dirs_host, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        gms::test_sh_dir_jacobian_kernel<<<(unsigned)((n + 255) / 256), 256>>>(n, deg, dr, dd, dout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out_host, dout, (size_t)n * 9 * sizeof(float), hipMemcpyDeviceToHost);
+    (void)hipFree(dr); (void)hipFree(dd); (void)hipFree(dout);
+    return e == hipSuccess ? 0 : -(int32_t)e;
+}
 
 extern "C" int32_t gms_test_fixed_point(int32_t n, const float *y_host, const int32_t *k_host, long long *fixed_host, float *back_host)
 {

@@ -59,11 +59,17 @@ inline void check_rc(int64_t rc, const char *what)
 
 // resize callbacks of the C ABI: the caller's (torch's caching) allocator owns all scratch
 struct Slot { Tensor t; c10::Device dev; bool failed; };
+// Diagnostics (tests): >= 0 fills every scratch buffer with that byte, on the frame's stream, before the library writes into it -- 0xFF
+// makes every float of it a NaN, so that a read of something the forward never wrote shows.  -1 (default): the buffers come as they are.
+std::atomic<int> g_scratch_fill{-1};
+void set_scratch_fill(int64_t byte) { g_scratch_fill = (byte >= 0 && byte <= 255) ? (int)byte : -1; }
 void *alloc_cb(void *ctx, size_t bytes)
 {
     Slot *s = static_cast<Slot *>(ctx);
     try {
         s->t = torch::empty({(int64_t)(bytes > 0 ? bytes : 1)}, torch::TensorOptions().dtype(torch::kUInt8).device(s->dev));
+        const int fill = g_scratch_fill.load();
+        if (fill >= 0) s->t.fill_(fill);
         return s->t.data_ptr();
     } catch (...) {
         s->failed = true;
@@ -1346,6 +1352,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("render_mesh", &render_mesh, "differentiable frame straight from a mesh: [image, radii, invdepth, xyz, scaling_act, rotation_unit, opacity_act]", nogil());
     m.def("l1_ssim", &l1_ssim, "differentiable w_l1 * L1 + w_ssim * SSIM + bias; returns (value [0-dim], [l1, ssim])", nogil());
     m.def("adam_step", &adam_step, nogil());
+    m.def("set_scratch_fill", &set_scratch_fill, "fill every scratch buffer with this byte before the library writes into it; -1: off (diagnostics only)");
     m.def("set_keep_buffers", &set_keep_buffers, "keep references to the last forward's scratch tensors (diagnostics only)");
     m.def("clear_accum", &clear_accum);
     m.def("set_sh_factor_mode", &set_sh_factor_mode, "factorised SH gradient: backward calls queue [P+1,3] factors instead of writing dL/dsh");

@@ -213,6 +213,18 @@ def keep_buffers(on: bool = True) -> None:
             _last_stats.pop(k, None)
 
 
+_scratch_fill = None
+
+
+def set_scratch_fill(byte: Optional[int]) -> None:
+    """Diagnostics (tests): fill every scratch buffer (geom / binning / image) with `byte` before the library writes into it -- 0xFF
+    makes every float of it a NaN, so that a read of something the forward never wrote shows.  None (default): off."""
+    global _scratch_fill
+    _scratch_fill = None if byte is None else int(byte) & 0xFF
+    if _C is not None:
+        _C.set_scratch_fill(-1 if _scratch_fill is None else _scratch_fill)
+
+
 def raw_buffers() -> dict:
     """The scratch tensors of the most recent forward (geom / binning / image byte buffers): diagnostics only; needs
     `keep_buffers(True)` before that forward."""
@@ -264,6 +276,8 @@ class _Scratch:
             def cb(_ctx, nbytes):
                 try:
                     t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.device)
+                    if _scratch_fill is not None:
+                        t.fill_(_scratch_fill)
                     self.tensors[name] = t
                     return t.data_ptr()
                 except Exception as e:  # noqa: BLE001 - reported through the error code path

@@ -190,6 +190,10 @@ typedef struct GmsRasterBackwardArgs {
                                          max(num_rendered, 1) */
     const float *background;
     const float *means3D, *shs, *shs_rest, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp;
+                                      /* `shs` / `shs_rest` are validated as in the forward and select the SH path and the layout of
+                                         dL_dsh / dL_dsh_rest, but preprocess_bwd no longer dereferences them: the only term of the SH
+                                         backward that needs coefficients, dL/d(view direction), is formed from the 3x3
+                                         d colour / d direction that the forward stored in geom_buffer */
     const float *viewmatrix, *projmatrix, *campos;
     float scale_modifier, tan_fovx, tan_fovy;
     int32_t antialiasing, debug;
@@ -558,7 +562,9 @@ int64_t gms_last_deepest_tile(void);
 int32_t gms_abi_version(void);
 /* Text of the last error on the calling thread ("" if none). */
 const char *gms_last_error(void);
-/* Byte sizes of the scratch buffers for given problem sizes (what the callbacks will be asked for). */
+/* Byte sizes of the scratch buffers for given problem sizes (what the callbacks will be asked for).  The geometry buffer holds,
+ * besides the splat records, 36 bytes per Gaussian of d colour / d direction (nine floats, written by the forward for visible
+ * Gaussians of SH frames, read by the backward): gms_geom_bytes includes them. */
 size_t gms_geom_bytes(int32_t P);
 size_t gms_image_bytes(int32_t width, int32_t height);
 /* Byte offset, inside the image scratch buffer, of n_contrib [H*W] uint32 (1-based list position of the last splat each
