@@ -950,6 +950,31 @@ std::vector<Tensor> l1_ssim(const Tensor &img, const Tensor &gt, double w_l1, do
     return L1SsimFn::apply(img, gt, w_l1, w_ssim, bias, at::GradMode::is_enabled() && img.requires_grad());
 }
 
+// ---------------------------------------------------------------------------------------------- evaluation sums (csrc/metrics.hip)
+// img / gt [C,H,W] or [B,C,H,W]; rows: the caller's float64 [n,8] table on the images' device, rows first_row .. first_row + B - 1
+// are written.  Launches only.  -> (img_u8, gt_u8) uint8 of the images' shape, or two empty tensors.
+std::tuple<Tensor, Tensor> image_metrics(const Tensor &img, const Tensor &gt, int64_t mode, Tensor rows, int64_t first_row, bool want_u8)
+{
+    require_gpu(img); require_gpu(gt); require_gpu(rows);
+    TORCH_CHECK(img.sizes() == gt.sizes(), "image shapes differ");
+    TORCH_CHECK(img.dim() == 3 || img.dim() == 4, "image_metrics: images must be [C,H,W] or [B,C,H,W]");
+    TORCH_CHECK(rows.scalar_type() == torch::kDouble && rows.is_contiguous() && rows.dim() == 2 && rows.size(1) == GMS_METRIC_ROW &&
+                rows.device() == img.device(), "image_metrics: rows must be a contiguous float64 [n,8] tensor on the images' device");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(img.device());
+    Tensor x = f32c(img.detach()), y = f32c(gt.detach());
+    const int64_t d = x.dim(), B = d == 4 ? x.size(0) : 1, Cn = x.size(d - 3), h = x.size(d - 2), w = x.size(d - 1);
+    TORCH_CHECK(B <= INT32_MAX && Cn <= INT32_MAX && h <= INT32_MAX && w <= INT32_MAX, "image_metrics: sizes exceed int32");
+    auto bopt = torch::TensorOptions().dtype(torch::kUInt8).device(x.device());
+    Tensor xu = want_u8 ? torch::empty(x.sizes(), bopt) : torch::empty({0}, bopt), yu = want_u8 ? torch::empty(x.sizes(), bopt) : torch::empty({0}, bopt);
+    const size_t bytes = gms_image_metrics_workspace_bytes((int32_t)B, (int32_t)Cn, (int32_t)h, (int32_t)w);
+    Tensor work = torch::empty({(int64_t)bytes}, bopt);
+    GmsMetricsArgs a{(int32_t)B, (int32_t)Cn, (int32_t)h, (int32_t)w, cf(x), cf(y), (int32_t)mode,
+                     xu.numel() ? xu.data_ptr<uint8_t>() : nullptr, yu.numel() ? yu.data_ptr<uint8_t>() : nullptr,
+                     rows.numel() ? rows.data_ptr<double>() : nullptr, rows.size(0), first_row};
+    check_rc(gms_image_metrics(&a, work.data_ptr(), bytes, stream_of(x)), "gms_image_metrics");
+    return {xu, yu};
+}
+
 // ---------------------------------------------------------------------------------------------- pseudo-mesh bound to a guide mesh
 // (scripts/edit_pseudomesh_based_on_estimated_mesh.py; csrc/bind.hip)
 struct Guide { Tensor vertices, faces; int32_t V, F; };
@@ -1351,6 +1376,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("enlargement_scalar") = 1.0, py::arg("swap") = false, nogil());
     m.def("render_mesh", &render_mesh, "differentiable frame straight from a mesh: [image, radii, invdepth, xyz, scaling_act, rotation_unit, opacity_act]", nogil());
     m.def("l1_ssim", &l1_ssim, "differentiable w_l1 * L1 + w_ssim * SSIM + bias; returns (value [0-dim], [l1, ssim])", nogil());
+    m.def("image_metrics", &image_metrics, "evaluation sums of image pairs into rows of a device table: (img_u8, gt_u8) or two empty tensors; launches only", nogil());
     m.def("adam_step", &adam_step, nogil());
     m.def("set_scratch_fill", &set_scratch_fill, "fill every scratch buffer with this byte before the library writes into it; -1: off (diagnostics only)");
     m.def("set_keep_buffers", &set_keep_buffers, "keep references to the last forward's scratch tensors (diagnostics only)");

@@ -88,6 +88,18 @@ class LossArgs(C.Structure):
     ]
 
 
+GMS_METRIC_RAW, GMS_METRIC_CLAMP, GMS_METRIC_QUANT8, GMS_METRIC_ROW = 0, 1, 2, 8
+
+
+class MetricsArgs(C.Structure):
+    """GmsMetricsArgs (include/gmsplat.h)."""
+    _fields_ = [
+        ("images", C.c_int32), ("channels", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("img", C.c_void_p), ("gt", C.c_void_p),
+        ("mode", C.c_int32), ("img_u8", C.c_void_p), ("gt_u8", C.c_void_p), ("rows", C.c_void_p), ("table_rows", C.c_int64),
+        ("first_row", C.c_int64),
+    ]
+
+
 class ShGradExpandArgs(C.Structure):
     """GmsShGradExpandArgs (include/gmsplat.h)."""
     _fields_ = [
@@ -160,6 +172,7 @@ EXPORTS = (
     "gms_bind_workspace_bytes", "gms_bind_pseudomesh", "gms_bind_apply",
     "gms_flame_workspace_bytes", "gms_flame_forward", "gms_flame_backward",
     "gms_densify_stats", "gms_densify_plan_workspace_bytes", "gms_densify_plan", "gms_densify_apply",
+    "gms_image_metrics_workspace_bytes", "gms_image_metrics",
 )
 K_COUNT = 23
 
@@ -237,6 +250,10 @@ def load():
                                          C.c_void_p]
         lib.gms_densify_apply.restype = C.c_int32
         lib.gms_densify_apply.argtypes = [C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(DensifyTensor), C.c_void_p, C.c_float, C.c_void_p]
+        lib.gms_image_metrics_workspace_bytes.restype = C.c_size_t
+        lib.gms_image_metrics_workspace_bytes.argtypes = [C.c_int32] * 4
+        lib.gms_image_metrics.restype = C.c_int32
+        lib.gms_image_metrics.argtypes = [C.POINTER(MetricsArgs), C.c_void_p, C.c_size_t, C.c_void_p]
         lib.gms_l1_ssim_partials.restype = C.c_size_t
         lib.gms_l1_ssim_partials.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         lib.gms_l1_ssim_forward.restype = C.c_int32

@@ -92,7 +92,8 @@ def _density_control(gaussians, opt, iteration, render_pkg, cameras_extent, whit
 def training(gaussians, train_cameras: Sequence, opt: OptimizationParamsMesh, pipe, background: torch.Tensor, *,
              render: Optional[Callable] = None, loss_fn: Optional[Callable] = None, first_iter: int = 0,
              report: Optional[Callable] = None, report_iterations: Sequence[int] = (), cameras_extent: float = 1.0,
-             white_background: bool = False) -> List[float]:
+             white_background: bool = False, test_cameras: Sequence = (), testing_iterations: Sequence[int] = (),
+             on_evaluation: Optional[Callable] = None) -> List[float]:
     """Runs iterations first_iter+1 .. opt.iterations.  `train_cameras`: objects with the camera attributes `render()` reads and
     `original_image` [3,H,W] (scene/cameras.py:17-58).  `gaussians`: a model with `training_setup()` already called (train.py:46).
     `render` / `loss_fn(image, gt, lambda_dssim) -> scalar` default to the HIP path (games_hip.render.render, the fused L1+SSIM of
@@ -100,7 +101,11 @@ def training(gaussians, train_cameras: Sequence, opt: OptimizationParamsMesh, pi
     `training_report`, train.py:120-122).  Returns the loss values it synchronised on (one per report).  Uses `random.randint` and
     `torch.rand` exactly where the reference does: seed them as `safe_state` does (utils/general_utils.py:203-213) to reproduce its
     camera order.  `cameras_extent` (scene.cameras_extent) and `white_background` (dataset.white_background) are read by the density
-    control of gs / gs_flat models only (train.py:138, 142)."""
+    control of gs / gs_flat models only (train.py:138, 142).  At `testing_iterations`, `games_hip.evaluate.training_report` runs
+    where the reference calls its own (train.py:122: after the backward, before the optimizer step, inside no_grad) over
+    `test_cameras` and the reference's five train cameras, with this loop's `render` and `background`; its dict goes to
+    `on_evaluation(iteration, result)`.  It draws no random number, and a model with deferred K0 serves it what the training
+    frame derived, so the steps that follow are the ones a run without it takes."""
     densify = hasattr(gaussians, "densify_and_prune") and hasattr(opt, "densify_until_iter")
     if render is None:
         from .render import render as render_fn
@@ -117,6 +122,7 @@ def training(gaussians, train_cameras: Sequence, opt: OptimizationParamsMesh, pi
     viewpoint_stack = None
     reported: List[float] = []
     report_at = set(int(i) for i in report_iterations)
+    test_at = set(int(i) for i in testing_iterations)
     first_iter += 1
     for iteration in range(first_iter, opt.iterations + 1):
         if hasattr(gaussians, "update_learning_rate"):
@@ -161,6 +167,11 @@ def training(gaussians, train_cameras: Sequence, opt: OptimizationParamsMesh, pi
                 reported.append(float(loss.detach()))
                 if report is not None:
                     report(iteration, reported[-1])
+            if iteration in test_at:
+                from .evaluate import training_report
+                result = training_report(iteration, gaussians, test_cameras, train_cameras, pipe, background, render=render_fn)
+                if on_evaluation is not None:
+                    on_evaluation(iteration, result)
             # Densification (`render_pkg` is the frame the gradients came from: the redone one after a deferred overflow, whose
             # tensors have the model's current size)
             if densify:

@@ -514,6 +514,36 @@ int32_t gms_densify_plan(int64_t P, int32_t S, const float *xyz_gradient_accum /
 int32_t gms_densify_apply(int64_t P, int64_t P_new, const int32_t *src /* [P_new] */, const int32_t *kind /* [P_new] */,
                           const GmsDensifyTensor *tensors /* HOST [6] */, const float *noise /* [2,P,3] */, float eps_s0, void *stream);
 
+/* ---- evaluation sums of image pairs (csrc/metrics.hip) ----------------------------------------
+ * What the reference's two quality reports are made of, from one read of each pair and without a host wait:
+ * `training_report` (train.py:183-223: torch.clamp, l1_loss, psnr of a [3,H,W] image = the mean of three per-channel PSNRs) and
+ * scripts/render.py + metrics.py (8-bit PNGs read back as [1,3,H,W]: ssim, psnr of the whole image's MSE).
+ * The value mode is applied to BOTH images before anything else, with the reference's float32 operations:
+ *   GMS_METRIC_RAW     x
+ *   GMS_METRIC_CLAMP   min(max(x, 0), 1), NaN kept                                                   (train.py:203-204)
+ *   GMS_METRIC_QUANT8  q = (uint8) min(max(x * 255.0f + 0.5f, 0), 255) truncating, x' = (float) q / 255.0f: the round trip of
+ *                      torchvision.utils.save_image + to_tensor.  Finite input only.  img_u8 / gt_u8 (both or neither) receive q.
+ * Image i of the call fills row first_row + i of `rows`, GMS_METRIC_ROW doubles:
+ *   { sum |x'-y'|, sum ssim_map, sum (x'-y')^2 of channel 0, 1, 2, 3 (0 for absent channels), H*W, channels }
+ * with the ssim_map of gms_l1_ssim_forward.  Block partials are float32, added in a fixed order in double: the same bits run to run
+ * and stream to stream.  A NaN pixel makes the row's sums NaN in modes RAW and CLAMP.  Two launches, no allocation, no host wait, no
+ * profile id.  `workspace`: caller-owned device scratch of at least gms_image_metrics_workspace_bytes(...) bytes.
+ * GMS_ERR_INVALID_ARGUMENT: first_row + images > table_rows, channels outside 1..4, byte outputs in another mode, null pointers,
+ * negative sizes; GMS_ERR_CAPACITY: workspace too small.  images == 0 or H*W == 0: nothing to do, GMS_OK. */
+#define GMS_METRIC_RAW 0
+#define GMS_METRIC_CLAMP 1
+#define GMS_METRIC_QUANT8 2
+#define GMS_METRIC_ROW 8
+typedef struct GmsMetricsArgs {
+    int32_t images, channels, height, width;
+    const float *img, *gt;          /* [images,channels,H,W] */
+    int32_t mode;                   /* GMS_METRIC_* */
+    uint8_t *img_u8, *gt_u8;        /* optional, mode QUANT8 only */
+    double *rows; int64_t table_rows, first_row;   /* rows [table_rows][8] on the device */
+} GmsMetricsArgs;
+size_t gms_image_metrics_workspace_bytes(int32_t images, int32_t channels, int32_t height, int32_t width);
+int32_t gms_image_metrics(const GmsMetricsArgs *args, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- per-kernel timing (HIP events on the launch stream; off by default) ------------------
  * When enabled every kernel launch made by this library is bracketed by two hipEvents on the
  * caller's stream.  gms_profile_read() synchronises the recorded events and returns the summed
