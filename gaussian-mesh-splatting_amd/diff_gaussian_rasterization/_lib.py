@@ -100,6 +100,16 @@ class MetricsArgs(C.Structure):
     ]
 
 
+class GroundTruthArgs(C.Structure):
+    """GmsGroundTruthArgs (include/gmsplat.h)."""
+    _fields_ = [
+        ("images", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("src", C.c_void_p),
+        ("white_background", C.c_int32), ("out_height", C.c_int32), ("out_width", C.c_int32),
+        ("h_bounds", C.c_void_p), ("h_coeffs", C.c_void_p), ("h_kmax", C.c_int32),
+        ("v_bounds", C.c_void_p), ("v_coeffs", C.c_void_p), ("v_kmax", C.c_int32), ("out", C.c_void_p),
+    ]
+
+
 class ShGradExpandArgs(C.Structure):
     """GmsShGradExpandArgs (include/gmsplat.h)."""
     _fields_ = [
@@ -173,6 +183,7 @@ EXPORTS = (
     "gms_flame_workspace_bytes", "gms_flame_forward", "gms_flame_backward",
     "gms_densify_stats", "gms_densify_plan_workspace_bytes", "gms_densify_plan", "gms_densify_apply",
     "gms_image_metrics_workspace_bytes", "gms_image_metrics",
+    "gms_ground_truth_workspace_bytes", "gms_ground_truth_u8",
 )
 K_COUNT = 23
 
@@ -254,6 +265,10 @@ def load():
         lib.gms_image_metrics_workspace_bytes.argtypes = [C.c_int32] * 4
         lib.gms_image_metrics.restype = C.c_int32
         lib.gms_image_metrics.argtypes = [C.POINTER(MetricsArgs), C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.gms_ground_truth_workspace_bytes.restype = C.c_size_t
+        lib.gms_ground_truth_workspace_bytes.argtypes = [C.c_int32] * 5
+        lib.gms_ground_truth_u8.restype = C.c_int32
+        lib.gms_ground_truth_u8.argtypes = [C.POINTER(GroundTruthArgs), C.c_void_p, C.c_size_t, C.c_void_p]
         lib.gms_l1_ssim_partials.restype = C.c_size_t
         lib.gms_l1_ssim_partials.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         lib.gms_l1_ssim_forward.restype = C.c_int32

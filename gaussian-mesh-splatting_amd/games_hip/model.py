@@ -498,6 +498,29 @@ class HipGaussianMeshModel(HipMeshMixin, _StandaloneBase):
         m.prepare_scaling_rot()
         return m
 
+    def create_from_pcd(self, pcd, spatial_lr_scale: float = 1.0, device="cuda"):
+        """gaussian_mesh_model.py:49-84 from a MeshPointCloud (games_hip.io_mesh, games_hip.dataset.load_scene): _scale 1,
+        opacity 0.1, the colours in the SH constant term, zero higher SH."""
+        import math
+        import numpy as np
+        self.point_cloud = pcd
+        self.spatial_lr_scale = spatial_lr_scale
+        P = pcd.points.shape[0]
+        par = lambda a: nn.Parameter(a.contiguous().requires_grad_(True))
+        fused_color = (torch.tensor(np.asarray(pcd.colors)).float().to(device) - 0.5) / 0.28209479177387814      # RGB2SH
+        features = torch.zeros((P, 3, (self.max_sh_degree + 1) ** 2), device=device)
+        features[:, :3, 0] = fused_color
+        self.vertices = par(pcd.vertices.clone().detach().float().to(device))
+        self.faces = torch.as_tensor(np.asarray(pcd.faces)).to(device)
+        self._alpha = par(pcd.alpha.float().to(device))
+        self._scale = par(torch.ones((P, 1), device=device))
+        self._opacity = par(torch.full((P, 1), math.log(0.1 / 0.9), device=device))
+        self._features_dc = par(features[:, :, 0:1].transpose(1, 2))
+        self._features_rest = par(features[:, :, 1:].transpose(1, 2))
+        self.update_alpha()
+        self.prepare_scaling_rot()
+        self.max_radii2D = torch.zeros((P,), device=device)
+
     def parameters(self):
         return [self.vertices, self._alpha, self._features_dc, self._features_rest, self._opacity, self._scale]
 

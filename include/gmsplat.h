@@ -544,6 +544,37 @@ typedef struct GmsMetricsArgs {
 size_t gms_image_metrics_workspace_bytes(int32_t images, int32_t channels, int32_t height, int32_t width);
 int32_t gms_image_metrics(const GmsMetricsArgs *args, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- ground-truth images from decoded bytes (csrc/images.hip) -------------------------------------
+ * What the reference does to a view's image on the CPU before training sees it, on the device and with its exact results:
+ *   composite  scene/dataset_readers.py:204-210: RGBA bytes over a black or white background,
+ *              byte = trunc((c/255.0 * (a/255.0) + bg * (1 - a/255.0)) * 255.0) in float64, in that operation order (the integer
+ *              formula (c*a + 255*bg*(255-a)) / 255 differs from it at 154 / 152 of the 65 536 (c, a) pairs).  channels == 3: the
+ *              bytes pass through.
+ *   resize     utils/camera_utils.py:41 -> PIL.Image.resize: Pillow's 8-bit bicubic, a horizontal then a vertical integer pass with
+ *              the intermediate rounded to bytes; a pass is skipped when its axis keeps its size.  The caller builds the tables
+ *              (games_hip.dataset.resample_tables restates Pillow's precompute_coeffs): bounds [n_out][2] = (first tap, tap count),
+ *              coeffs [n_out][kmax] int32 with 22 fractional bits, both on the device;
+ *              out = clip8(((1 << 21) + sum_i coeffs[i] * pixel[first + i]) >> 22).  Taps that would leave the axis are cut.
+ *   to float   scene/cameras.py:39 / utils/general_utils.py:103: (float) byte / 255.0f, the IEEE quotient.
+ * src: uint8 [images,height,width,channels] interleaved; out: float32 [images,3,out_height,out_width] planar.  Every result is exact
+ * (bytes equal, floats bit-equal to the reference's).  One launch at native size, one more per resized axis; no allocation, no host
+ * wait, no atomics, no profile id.  `workspace`: caller-owned device scratch of at least gms_ground_truth_workspace_bytes(...) bytes,
+ * read only when a size changes (NULL allowed otherwise).
+ * Returns the number of kernel launches made (1..3), or GMS_ERR_INVALID_ARGUMENT: null pointers (args, src, out, the tables of an axis
+ * that changes, the workspace of a resize), sizes <= 0, more than 65 535 images, channels outside {3, 4}, white_background outside
+ * {0, 1}; GMS_ERR_CAPACITY: workspace too small. */
+typedef struct GmsGroundTruthArgs {
+    int32_t images, height, width, channels;
+    const uint8_t *src;                             /* [images,height,width,channels] */
+    int32_t white_background;                       /* 0: black, 1: white (read for channels == 4) */
+    int32_t out_height, out_width;
+    const int32_t *h_bounds, *h_coeffs; int32_t h_kmax;     /* [out_width][2], [out_width][h_kmax]; read when out_width != width */
+    const int32_t *v_bounds, *v_coeffs; int32_t v_kmax;     /* [out_height][2], [out_height][v_kmax]; read when out_height != height */
+    float *out;                                     /* [images,3,out_height,out_width] */
+} GmsGroundTruthArgs;
+size_t gms_ground_truth_workspace_bytes(int32_t images, int32_t height, int32_t width, int32_t out_height, int32_t out_width);
+int32_t gms_ground_truth_u8(const GmsGroundTruthArgs *args, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- per-kernel timing (HIP events on the launch stream; off by default) ------------------
  * When enabled every kernel launch made by this library is bracketed by two hipEvents on the
  * caller's stream.  gms_profile_read() synchronises the recorded events and returns the summed
