@@ -1,0 +1,860 @@
+// binning.hip -- K2-K4 of the forward pass (raster_forward.hip has the map): tile scan, instance emit, per-tile sort.
+//
+//   K2  tile_scan        ONE block of 1024: eleven exclusive scans over the tiles in one pass (instances, work units,
+//                        multi-segment slots, six heaviest-first unit classes, sort runs, multi-run tiles); publishes
+//                        N / deepest tile / unit count to the host through the pinned slot, clears the tile counters.
+//   K3  emit_instances   one 64-bit key (depth bits << 32 | id) per (Gaussian, tile): per-block LDS tile table, ONE
+//                        cursor atomic per distinct tile per block; spare blocks write the (tile, segment) unit records
+//                        (heaviest first) and the sort's run tables.
+//   K4  tile_sort        presort of 1024-key runs (one block per run, wave-local bitonic sub-stages), then merge-path
+//                        levels in LDS per multi-run tile (<= 8192 keys) or multi-block merge-path passes for deeper
+//                        tiles.  Total order on (depth, id): independent of the emission order == the reference's
+//                        stable radix sort.
+#include "gms_blend.h"
+#include "gms_common.h"
+#include "gms_forward.h"
+
+namespace gms {
+
+// ------------------------------------------------------------------------------------ K2
+// One block: exclusive scans over the tiles of (a) instance counts -> tile_offset (offset[T] = N),
+// (b) segments per tile -> unit_first, (c) segments of multi-segment tiles -> mseg_first (slots of
+// the per-unit pixel state).  Also resets the emit cursors.
+// tile sort (K4) sizes, needed by the scan below
+constexpr int SORT_RUN = 1024;
+constexpr int SORT_RUNS_PER_TILE = 8;
+constexpr int SORT_BIG_CHUNK = SORT_RUN * SORT_RUNS_PER_TILE;    // 8192 keys = 64 KiB LDS
+constexpr int MP_CHUNK = 1024;                                   // output keys per merge-path block
+
+constexpr int NSCAN = 11;
+constexpr int NCLASS = 6;     // dispatch classes: full | partial >=3/4 L | >=1/2 L | >=1/4 L | < 1/4 L | empty
+constexpr int SCAN_THREADS = 1024;
+
+// per-tile quantities scanned: instances, segments, segments of multi-segment tiles, then the dispatch classes
+__device__ __forceinline__ void tile_terms(uint32_t c, uint32_t L, uint32_t t[NSCAN], int sort_np = 0)
+{
+    const uint32_t ns = max(1u, (c + L - 1) / L);   // empty tiles still get a unit (background)
+    t[0] = c; t[1] = ns; t[2] = ns > 1 ? ns : 0;
+    const uint32_t r = c % L;
+    t[3] = c / L;
+    t[4] = r * 4 >= 3 * L ? 1u : 0u;
+    t[5] = (r * 4 < 3 * L && r * 2 >= L) ? 1u : 0u;
+    t[6] = (r * 2 < L && r * 4 >= L) ? 1u : 0u;
+    t[7] = (r * 4 < L && r != 0) ? 1u : 0u;
+    t[8] = c == 0 ? 1u : 0u;
+    t[9] = c > 1 ? (c + MP_CHUNK - 1) / MP_CHUNK : 0u;      // 1024-key sort runs (= merge-path chunks) of the tile
+    t[10] = c > (uint32_t)SORT_RUN ? 1u : 0u;               // tile needs merging
+    (void)sort_np;
+}
+
+// The instance count N goes straight to the host: system-scope stores into pinned memory that the waiting host thread
+// polls -- no copy-engine hop, no event wake-up latency.  Three self-tagged 64-bit words {call sequence number : value}:
+// each is ONE relaxed system-scope store, so no release fence (= write-back of the XCD's dirty L2 lines) is needed to order
+// a value before its flag.
+__device__ __forceinline__ void publish_counts(int32_t *host_slot, int32_t seq, uint32_t n, uint32_t deepest, uint32_t units)
+{
+    unsigned long long *hs = reinterpret_cast<unsigned long long *>(host_slot);
+    const unsigned long long tag = (unsigned long long)(uint32_t)seq << 32;
+    __hip_atomic_store(&hs[2], tag | units, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&hs[1], tag | deepest, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&hs[0], tag | n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// One block of 1024 threads: NSCAN exclusive scans over the tiles at once.  Each wave scans its 64 per-thread
+// sums with DPP-free shuffles, the 16 wave totals are scanned by the first wave: two block barriers in all.
+__global__ void __launch_bounds__(SCAN_THREADS) tile_scan_kernel(uint32_t *count, uint32_t *offset, uint32_t *cursor,
+                                                                 uint32_t *unit_first, uint32_t *mseg_first,
+                                                                 uint32_t *class_first, int T, uint32_t L_forced, int32_t *host_slot,
+                                                                 int32_t seq, int sort_np, uint32_t *scan_out)
+{
+    __shared__ uint32_t wave_tot[NSCAN][SCAN_THREADS / WAVE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int per = (T + SCAN_THREADS - 1) / SCAN_THREADS;
+    const int b = tid * per, e = min(T, b + per);
+    // segment length of this frame: forced, or chosen from the average list length per tile (gms_blend.h)
+    uint32_t L = L_forced;
+    if (L == 0) {
+        __shared__ uint32_t wave_n[SCAN_THREADS / WAVE];
+        uint32_t n = 0;
+        for (int t = b; t < e; t++) n += count[t];
+        for (int d = 32; d >= 1; d >>= 1) n += (uint32_t)__shfl_xor((int)n, d);
+        if (lane == 0) wave_n[wave] = n;
+        __syncthreads();
+        uint64_t total = 0;
+        for (int w = 0; w < SCAN_THREADS / WAVE; w++) total += wave_n[w];
+        L = total > (uint64_t)SEG_VERY_DEEP_PER_TILE * (uint64_t)T ? SEG_LEN_VERY_DEEP
+          : total > (uint64_t)SEG_DEEP_PER_TILE * (uint64_t)T ? SEG_LEN_DEEP : SEG_LEN_SHALLOW;
+    }
+    uint32_t run[NSCAN], own[NSCAN];
+    uint32_t deepest = 0;
+#pragma unroll
+    for (int k = 0; k < NSCAN; k++) run[k] = 0;
+    for (int t = b; t < e; t++) {
+        uint32_t q[NSCAN];
+        tile_terms(count[t], L, q, sort_np);
+        deepest = max(deepest, q[0]);
+#pragma unroll
+        for (int k = 0; k < NSCAN; k++) run[k] += q[k];
+    }
+    for (int d = 32; d >= 1; d >>= 1) deepest = max(deepest, (uint32_t)__shfl_xor((int)deepest, d));
+    __shared__ uint32_t wave_deep[SCAN_THREADS / WAVE];
+    if (lane == 0) wave_deep[wave] = deepest;
+    // inclusive scan inside the wave
+#pragma unroll
+    for (int k = 0; k < NSCAN; k++) {
+        own[k] = run[k];
+        for (int d = 1; d < WAVE; d <<= 1) {
+            const uint32_t x = (uint32_t)__shfl_up((int)run[k], d);
+            if (lane >= d) run[k] += x;
+        }
+        if (lane == WAVE - 1) wave_tot[k][wave] = run[k];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int k = 0; k < NSCAN; k++) {
+            uint32_t v = lane < SCAN_THREADS / WAVE ? wave_tot[k][lane] : 0u;
+            for (int d = 1; d < SCAN_THREADS / WAVE; d <<= 1) {
+                const uint32_t x = (uint32_t)__shfl_up((int)v, d);
+                if (lane >= d) v += x;
+            }
+            if (lane < SCAN_THREADS / WAVE) wave_tot[k][lane] = v;      // inclusive over waves
+        }
+    }
+    __syncthreads();
+    uint32_t tot[NSCAN];
+#pragma unroll
+    for (int k = 0; k < NSCAN; k++) {
+        tot[k] = wave_tot[k][SCAN_THREADS / WAVE - 1];
+        run[k] = run[k] - own[k] + (wave > 0 ? wave_tot[k][wave - 1] : 0u);   // exclusive prefix of this thread's chunk
+    }
+    // The instance count N goes straight to the host: two system-scope stores into pinned memory (value, then the
+    // call's sequence number) that the waiting host thread polls -- no copy-engine hop, no event wake-up latency.
+    if (tid == 0) {
+        uint32_t dm = 0;
+        for (int w = 0; w < SCAN_THREADS / WAVE; w++) dm = max(dm, wave_deep[w]);
+        // {N, deepest tile, work units} go to the host right here, as early as they exist: the host thread that waits for N
+        // then has the rest of the forward (emit, sort, compositing: ~220 us on the headline scene) to get the backward
+        // enqueued before the GPU runs dry.  (Publishing from the emit launch instead was measured: the scan is not
+        // shortened by it -- 15.7 -> 15.4 us -- and the host loses 24 us of that slack.)  The device copy serves that variant.
+        scan_out[0] = tot[0]; scan_out[1] = dm; scan_out[2] = tot[1]; scan_out[3] = L;
+        if (host_slot) publish_counts(host_slot, seq, tot[0], dm, tot[1]);
+    }
+    for (int t = b; t < e; t++) {
+        uint32_t q[NSCAN];
+        tile_terms(count[t], L, q, sort_np);
+        offset[t] = run[0]; unit_first[t] = run[1]; mseg_first[t] = run[2];
+#pragma unroll
+        for (int k = 0; k < NCLASS; k++) class_first[k * (T + 1) + t] = run[3 + k];
+        class_first[NCLASS * (T + 1) + t] = run[9];
+        class_first[(NCLASS + 1) * (T + 1) + t] = run[10];
+        cursor[t] = 0;
+        count[t] = 0;          // the counter array is library-owned and stays all zero between frames (no memset per frame)
+#pragma unroll
+        for (int k = 0; k < NSCAN; k++) run[k] += q[k];
+    }
+    if (tid == 0) {
+        offset[T] = tot[0]; unit_first[T] = tot[1]; mseg_first[T] = tot[2];
+#pragma unroll
+        for (int k = 0; k < NCLASS; k++) class_first[k * (T + 1) + T] = tot[3 + k];
+        class_first[NCLASS * (T + 1) + T] = tot[9];
+        class_first[(NCLASS + 1) * (T + 1) + T] = tot[10];
+    }
+}
+
+// unit table, heaviest first: [all full segments | partial last segments | units of empty tiles]
+struct FillUnitsArgs {
+    const uint32_t *class_first, *offset, *mseg_first;
+    uint4 *unit_tile;
+    uint2 *deep_tab;
+    uint32_t *multi_tab;
+    int T, sort_np;
+    const uint32_t *scan_out;      // [3] = this frame's segment length
+    uint32_t max_units, max_deep, max_multi;
+};
+
+// what fill_units needs to know about one tile: its count, its exclusive prefixes `pre` of the NSCAN scanned quantities and
+// the totals `tot` (tile_scan_kernel's arrays, or the inline scan of the emit launch)
+__device__ __forceinline__ void fill_units_tile(const FillUnitsArgs &f, int t, uint32_t c, uint32_t L, const uint32_t pre[NSCAN], const uint32_t tot[NSCAN])
+{
+    const uint32_t nfull = c / L;
+    uint32_t q[NSCAN];
+    tile_terms(c, L, q, f.sort_np);
+    const uint32_t nseg = q[1];                          // units of this tile (>= 1)
+    const uint4 tail = make_uint4(pre[0], pre[0] + c, 0u, 0u);
+    const uint32_t slot0 = pre[2];
+    auto put = [&](uint32_t u, uint32_t seg) {
+        if (u < f.max_units) {
+            f.unit_tile[2 * (size_t)u] = make_uint4((uint32_t)t, seg, nseg, slot0);
+            f.unit_tile[2 * (size_t)u + 1] = tail;
+        }
+    };
+    for (uint32_t j = 0, d = pre[9]; j < q[9]; j++, d++)
+        if (d < f.max_deep) f.deep_tab[d] = make_uint2((uint32_t)t, j);
+    if (q[10]) { const uint32_t d = pre[10]; if (d < f.max_multi) f.multi_tab[d] = (uint32_t)t; }
+    uint32_t u = pre[3];
+    for (uint32_t s = 0; s < nfull; s++, u++) put(u, s);
+    uint32_t base = tot[3];                             // all full units come first
+    for (int k = 1; k < NCLASS; k++) {
+        if (q[3 + k]) put(base + pre[3 + k], k == NCLASS - 1 ? 0u : nfull);
+        base += tot[3 + k];
+    }
+}
+
+__device__ __forceinline__ void fill_units(const FillUnitsArgs &f, int block)
+{
+    const int T = f.T;
+    const int t = block * BLOCK + threadIdx.x;
+    if (t >= T) return;
+    const uint32_t c = f.offset[t + 1] - f.offset[t];      // (the counters were cleared by the scan)
+    uint32_t pre[NSCAN], tot[NSCAN];
+    pre[0] = f.offset[t]; pre[1] = 0u; pre[2] = f.mseg_first[t]; tot[0] = tot[1] = tot[2] = 0u;
+#pragma unroll
+    for (int k = 0; k < NCLASS + 2; k++) { pre[3 + k] = f.class_first[k * (T + 1) + t]; tot[3 + k] = f.class_first[k * (T + 1) + T]; }
+    fill_units_tile(f, t, c, f.scan_out[3], pre, tot);
+}
+
+// ---- the tile scan INSIDE the emit launch (round 4).  tile_scan_kernel is one block whose 13 us sit between preprocess and emit
+// with the rest of the chip idle.  On the capacity-hint path (every frame but the first of a shape) its work is done redundantly
+// instead: every emit block scans the T <= 4096 counters itself (10-16 KB out of L2, ~1.5 us) and keeps the tile offsets in LDS;
+// the launch's spare blocks -- one per 256 tiles, as before -- run the full NSCAN-quantity scan, write the tables later launches
+// read (tile_offset, unit_first, mseg_first, the totals of class_first, scan_out) and their slice of the unit table, and the first
+// of them publishes N to the host.  The counters are cleared by the presort launch, the cursors by preprocess_fwd.
+constexpr int INLINE_SCAN_MAX_T = 4096;
+
+__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane)
+{
+    for (int d = 1; d < WAVE; d <<= 1) {
+        const uint32_t x = (uint32_t)__shfl_up((int)v, d);
+        if (lane >= d) v += x;
+    }
+    return v;
+}
+
+// exclusive scan of count[0..T) into s_off[0..T]; all BLOCK threads
+__device__ __forceinline__ void inline_offsets(const uint32_t *count, int T, uint32_t *s_off, uint32_t *s_wave /* [4] */)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int per = (T + BLOCK - 1) / BLOCK;
+    const int b = min(T, tid * per), e = min(T, b + per);
+    uint32_t c[16];
+    uint32_t sum = 0;
+#pragma unroll
+    for (int k = 0; k < 16; k++) { c[k] = (k < per && b + k < e) ? count[b + k] : 0u; sum += c[k]; }
+    const uint32_t incl = wave_incl_scan_u32(sum, lane);
+    if (lane == WAVE - 1) s_wave[wave] = incl;
+    __syncthreads();
+    uint32_t pre = incl - sum;
+    for (int w = 0; w < wave; w++) pre += s_wave[w];
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+        if (k < per && b + k < e) { s_off[b + k] = pre; pre += c[k]; }
+    if (tid == BLOCK - 1) s_off[T] = pre;
+    __syncthreads();
+}
+
+struct InlineScanLds {
+    uint32_t chunk[NSCAN][BLOCK];      // exclusive prefix of every thread's chunk of tiles
+    uint32_t wave_tot[NSCAN][BLOCK / WAVE];
+    uint32_t total[NSCAN];
+    uint32_t wave_deep[BLOCK / WAVE];
+    uint32_t deepest;
+};
+
+// the spare blocks' scan of all NSCAN quantities, then tile `t`'s prefixes / totals
+__device__ __forceinline__ void inline_scan_build(const uint32_t *count, int T, uint32_t L, int sort_np, InlineScanLds &S)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int per = (T + BLOCK - 1) / BLOCK;
+    const int b = min(T, tid * per), e = min(T, b + per);
+    uint32_t run[NSCAN];
+    uint32_t deepest = 0;
+#pragma unroll
+    for (int k = 0; k < NSCAN; k++) run[k] = 0;
+    for (int t = b; t < e; t++) {
+        uint32_t q[NSCAN];
+        tile_terms(count[t], L, q, sort_np);
+        deepest = max(deepest, q[0]);
+#pragma unroll
+        for (int k = 0; k < NSCAN; k++) run[k] += q[k];
+    }
+    for (int d = 32; d >= 1; d >>= 1) deepest = max(deepest, (uint32_t)__shfl_xor((int)deepest, d));
+    if (lane == 0) S.wave_deep[wave] = deepest;
+    uint32_t incl[NSCAN];
+#pragma unroll
+    for (int k = 0; k < NSCAN; k++) {
+        incl[k] = wave_incl_scan_u32(run[k], lane);
+        if (lane == WAVE - 1) S.wave_tot[k][wave] = incl[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NSCAN; k++) {
+        uint32_t pre = incl[k] - run[k];
+        for (int w = 0; w < wave; w++) pre += S.wave_tot[k][w];
+        S.chunk[k][tid] = pre;
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < NSCAN; k++) S.total[k] = S.wave_tot[k][0] + S.wave_tot[k][1] + S.wave_tot[k][2] + S.wave_tot[k][3];
+        S.deepest = max(max(S.wave_deep[0], S.wave_deep[1]), max(S.wave_deep[2], S.wave_deep[3]));
+    }
+    __syncthreads();
+}
+
+// ------------------------------------------------------------------------------------ K3
+// The grid's extra blocks (beyond the Gaussians') write the unit table: it only depends on the tile scan, like this
+// kernel, so it rides along instead of costing a launch of its own.
+struct InlineScanArgs {
+    const uint32_t *count;         // [T] per-tile instance counters (preprocess_fwd)
+    uint32_t *offset, *unit_first, *mseg_first, *class_first, *scan_out;
+    uint32_t L;                    // this frame's segment length (forced: the inline path is not taken when the scan has to choose it)
+};
+
+template <bool INLINE>
+__global__ void __launch_bounds__(BLOCK) emit_instances_kernel(int P, int gx, int gy, const int *radii, GeomState geom,
+                                                               const uint32_t *tile_offset, uint32_t *tile_cursor,
+                                                               uint64_t *keys, uint64_t capacity, unsigned emit_blocks, FillUnitsArgs fu,
+                                                               int32_t *host_slot, int32_t seq, const uint32_t *scan_out, InlineScanArgs is)
+{
+    // one LDS buffer: emit blocks = [tile offsets (inline scan) | tile table keys, counts, bases | wave sums]; spare blocks = InlineScanLds
+    constexpr int OFFW = INLINE ? INLINE_SCAN_MAX_T + 4 : 0;
+    __shared__ uint32_t smem[OFFW + 3 * TT_SLOTS + BLOCK / WAVE];
+    static_assert(sizeof(InlineScanLds) <= sizeof(uint32_t) * (INLINE_SCAN_MAX_T + 4 + 3 * TT_SLOTS), "spare blocks alias the emit blocks' LDS");
+    uint32_t *s_off = smem, *s_wave = smem + OFFW + 3 * TT_SLOTS;
+    // INLINE: the spare blocks come FIRST in the grid (the first of them publishes N: the host should not wait for it behind
+    // thousands of emit blocks); otherwise they follow the emit blocks as before
+    const unsigned nspare = gridDim.x - emit_blocks;
+    const bool spare = INLINE ? blockIdx.x < nspare : blockIdx.x >= emit_blocks;
+    const unsigned spare_idx = INLINE ? blockIdx.x : blockIdx.x - emit_blocks;
+    const unsigned emit_idx = INLINE ? blockIdx.x - nspare : blockIdx.x;
+    if (spare) {
+        if (INLINE) {
+            InlineScanLds &S = *reinterpret_cast<InlineScanLds *>(smem);
+            const int T = fu.T;
+            inline_scan_build(is.count, T, is.L, fu.sort_np, S);
+            const int t = (int)spare_idx * BLOCK + (int)threadIdx.x;
+            if (spare_idx == 0 && threadIdx.x == 0) {
+                is.scan_out[0] = S.total[0]; is.scan_out[1] = S.deepest; is.scan_out[2] = S.total[1]; is.scan_out[3] = is.L;
+                if (host_slot) publish_counts(host_slot, seq, S.total[0], S.deepest, S.total[1]);
+                is.offset[T] = S.total[0]; is.unit_first[T] = S.total[1]; is.mseg_first[T] = S.total[2];
+#pragma unroll
+                for (int k = 0; k < NCLASS + 2; k++) is.class_first[k * (T + 1) + T] = S.total[3 + k];
+            }
+            if (t < T) {
+                const int per = (T + BLOCK - 1) / BLOCK;
+                const int c0 = t / per;
+                uint32_t pre[NSCAN], tot[NSCAN];
+#pragma unroll
+                for (int k = 0; k < NSCAN; k++) { pre[k] = S.chunk[k][c0]; tot[k] = S.total[k]; }
+                for (int u = c0 * per; u < t; u++) {
+                    uint32_t q[NSCAN];
+                    tile_terms(is.count[u], is.L, q, fu.sort_np);
+#pragma unroll
+                    for (int k = 0; k < NSCAN; k++) pre[k] += q[k];
+                }
+                is.offset[t] = pre[0]; is.unit_first[t] = pre[1]; is.mseg_first[t] = pre[2];
+#pragma unroll
+                for (int k = 0; k < NCLASS + 2; k++) is.class_first[k * (T + 1) + t] = pre[3 + k];      // (a re-run of the tail reads them)
+                fill_units_tile(fu, t, is.count[t], is.L, pre, tot);
+            }
+            return;
+        }
+        // (first spare block: this frame's counts go to the host from here when the scan left that to us)
+        if (spare_idx == 0 && threadIdx.x == 0 && host_slot) publish_counts(host_slot, seq, scan_out[0], scan_out[1], scan_out[2]);
+        fill_units(fu, (int)spare_idx);
+        return;
+    }
+    if (INLINE) { inline_offsets(is.count, fu.T, s_off, s_wave); tile_offset = s_off; }
+    const int i = (int)emit_idx * BLOCK + threadIdx.x;
+    // (the three loads are independent: the pixel centre and the depth of a culled Gaussian are stale words that nothing reads --
+    // loading them only after `r > 0` was known put a second memory round trip into a kernel that waits 85 % of its cycles)
+    // (two independent loads, 12 bytes per Gaussian: the tile rectangle preprocess_fwd counted over -- all zero for a culled Gaussian --
+    //  and the depth; rounds 1-5 read the radius and the pixel centre, i.e. every cache line of the 48-byte records for 8 bytes each)
+    const ushort4 rc = i < P ? geom.rect[i] : make_ushort4(0, 0, 0, 0);
+    const uint32_t dbits = i < P ? __float_as_uint(geom.depth[i]) : 0u;
+    const int minx = rc.x, miny = rc.y, maxx = rc.z, maxy = rc.w;
+    const int rw = maxx - minx;
+    const int area = rw * (maxy - miny);
+    const uint64_t key = area > 0 ? (((uint64_t)dbits << 32) | (uint32_t)i) : 0ull;
+    (void)radii; (void)gy;
+    const bool small = area <= SMALL_AREA;
+    const int lane = threadIdx.x & 63;
+    int cx = minx, cy = miny;
+    // footprints up to SMALL_AREA tiles: count per tile in the block's LDS table, fetch one cursor range per
+    // distinct tile (one global atomic each, all in flight together), then hand out ranks from LDS
+    int *tt_key = reinterpret_cast<int *>(smem + OFFW);
+    uint32_t *tt_cnt = smem + OFFW + TT_SLOTS, *tt_base = smem + OFFW + 2 * TT_SLOTS;
+    for (int q = threadIdx.x; q < TT_SLOTS; q += BLOCK) { tt_key[q] = -1; tt_cnt[q] = 0; }
+    __syncthreads();
+    if (small) {
+        for (int k = 0; k < area; k++) {
+            const int sl = tt_insert(tt_key, cy * gx + cx);
+            if (sl >= 0) atomicAdd(&tt_cnt[sl], 1u);
+            if (++cx == maxx) { cx = minx; cy++; }
+        }
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < TT_SLOTS; q += BLOCK)
+        if (tt_key[q] >= 0) {
+            tt_base[q] = tile_offset[tt_key[q]] + atomicAdd(&tile_cursor[tt_key[q]], tt_cnt[q]);
+            tt_cnt[q] = 0;
+        }
+    __syncthreads();
+    if (small) {
+        cx = minx; cy = miny;
+        for (int k = 0; k < area; k++) {
+            const int t = cy * gx + cx;
+            const int sl = tt_find(tt_key, t);
+            const uint64_t slot = sl >= 0 ? (uint64_t)tt_base[sl] + atomicAdd(&tt_cnt[sl], 1u)
+                                          : (uint64_t)tile_offset[t] + atomicAdd(&tile_cursor[t], 1u);
+            if (slot < capacity) keys[slot] = key;
+            if (++cx == maxx) { cx = minx; cy++; }
+        }
+    }
+    // large footprints: the wave expands one splat at a time, a tile per lane
+    uint64_t big = __ballot(!small);
+    while (big) {
+        const int src = __builtin_ctzll(big);
+        big &= big - 1;
+        const int bminx = __builtin_amdgcn_readlane(minx, src), bminy = __builtin_amdgcn_readlane(miny, src);
+        const int brw = __builtin_amdgcn_readlane(rw, src), barea = __builtin_amdgcn_readlane(area, src);
+        const uint32_t klo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)key, src);
+        const uint32_t khi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(key >> 32), src);
+        const uint64_t bkey = ((uint64_t)khi << 32) | klo;
+        for (int k = lane; k < barea; k += WAVE) {
+            const int ty = k / brw, tx = k - ty * brw;
+            const int t = (bminy + ty) * gx + bminx + tx;
+            const uint64_t slot = (uint64_t)tile_offset[t] + atomicAdd(&tile_cursor[t], 1u);
+            if (slot < capacity) keys[slot] = bkey;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------ K4
+// Per-tile sort of (depth bits << 32 | id) keys: an all-ascending bitonic network (mirror step +
+// half-cleaners), so virtual +inf padding works for any length.  Compare-exchange index i always
+// touches the 128-key block i/64, and thread t owns indices t, t+THREADS, ...: every sub-stage
+// whose span is <= 128 keys stays inside one wave's blocks and needs only wave-level ordering
+// (LDS operations of a wave execute in order) -- block barriers are paid only for the wide
+// sub-stages (6 instead of 55 for 1024 keys).
+__device__ __forceinline__ void ce(uint64_t &x, uint64_t &y)
+{
+    if (x > y) { uint64_t t = x; x = y; y = t; }
+}
+
+
+constexpr int WAVE_SPAN = 128;   // keys covered by one wave's 64 compare-exchanges
+
+template <int THREADS>
+__device__ __forceinline__ void stage_sync(int span, int &prev_span)
+{
+    if (span > WAVE_SPAN || prev_span > WAVE_SPAN) __syncthreads();
+    else wave_sync();
+    prev_span = span;
+}
+
+// sort m (power of two) keys in LDS: merges k = k0 .. m; with mirror=false the mirror step of the
+// first merge is skipped (the caller did it and the wide strides in global memory).
+template <int THREADS>
+__device__ void lds_bitonic(uint64_t *s, int m, int k0, int j0, bool first_mirror, int tid)
+{
+    int prev = 1 << 30;
+    for (int k = k0, lk = 31 - __builtin_clz(k0); k <= m; k <<= 1, lk++) {   // all sizes are powers of two:
+        const int hk = k >> 1;                                                // index math with shifts/masks only
+        if (k > k0 || first_mirror) {
+            stage_sync<THREADS>(k, prev);
+            for (int i = tid; i < (m >> 1); i += THREADS) {
+                const int blk = i >> (lk - 1), off = i & (hk - 1);
+                const int lo = (blk << lk) + off, hi = (blk << lk) + k - 1 - off;
+                ce(s[lo], s[hi]);
+            }
+        }
+        int j = (k > k0 || first_mirror) ? (k >> 2) : j0;
+        for (int lj = j > 0 ? 31 - __builtin_clz(j) : 0; j >= 1; j >>= 1, lj--) {
+            stage_sync<THREADS>(2 * j, prev);
+            for (int i = tid; i < (m >> 1); i += THREADS) {
+                const int lo = ((i >> lj) << (lj + 1)) + (i & (j - 1));
+                ce(s[lo], s[lo + j]);
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// Per-tile sort in three stages.
+//  (1) presort: grid (T, 8), 256 threads: block (t, c) sorts runs c, c+8, ... of SORT_RUN keys of tile t in registers (the
+//      runs of one tile sort on different CUs).
+//  (2) when some tile is deeper than SORT_BIG_CHUNK keys: merge-path passes for every multi-run tile, run width
+//      doubling per pass; every block produces one 1024-key chunk of the output from the co-ranks of its two ends
+//      (found by a wave-wide 64-ary search), so a deep tile's merge is spread over as many CUs as it has chunks and
+//      each pass is a streaming read + write of the keys that still need merging.  Data ping-pongs between `keys` and a scratch buffer (the segment-state area, unused until
+//      compositing); the presort writes a tile's runs to the side that makes its LAST pass land in `keys`.  The host
+//      launches as many passes as the deepest tile of the PREVIOUS frame needs (the count travels back with N);
+//  (3) merge: 1024 threads per tile with 2..8 runs: loads the tile (<= SORT_BIG_CHUNK keys) into LDS and runs only the
+//      bitonic merge levels above SORT_RUN.  A tile deeper than the launched passes cover (scene changed since the last
+//      frame) is sorted from scratch here by one block: slow, but correct, and the next frame launches enough passes.
+
+enum { SORT_SINGLE = 0, SORT_LDS, SORT_MERGEPATH, SORT_FALLBACK };
+
+__host__ __device__ __forceinline__ int sort_passes(uint64_t n)       // merge levels above SORT_RUN-key runs
+{
+    const uint64_t runs = (n + SORT_RUN - 1) / SORT_RUN;
+    int q = 0;
+    while ((1ull << q) < runs) q++;
+    return q;
+}
+
+__device__ __forceinline__ int sort_class(uint64_t n, int passes_launched, int &q)
+{
+    q = 0;
+    if (n <= (uint64_t)SORT_RUN) return SORT_SINGLE;
+    q = sort_passes(n);
+    if (q <= passes_launched) return SORT_MERGEPATH;      // passes are launched: every multi-run tile they cover takes them
+    return n <= (uint64_t)SORT_BIG_CHUNK ? SORT_LDS : SORT_FALLBACK;
+}
+
+// ---- register-resident presort ------------------------------------------------------------------------------------
+// The all-ascending bitonic network of lds_bitonic (mirror step + half-cleaners: every step pairs element i with i ^ M) on a run of
+// <= 1024 keys, with the keys in REGISTERS: thread t of 256 holds keys 4t .. 4t+3.  A step whose mask only touches bits
+// 0-1 is a compare-exchange between the thread's own registers; bits 2-7 select the partner LANE (lane ^ (M >> 2)): DPP row
+// operations for the lane masks 1, 2, 3, 4, 7, 8, 15 (full rate, no LDS), ds_bpermute for those that cross a 16-lane row; only
+// the four steps with bits 8-9 (k = 512 mirror, k = 1024 mirror, strides 512 and 256) go through LDS.  The LDS version (measured,
+// removed; see docs/HISTORY.md) paid an LDS round trip and a barrier or wave sync for each of its 55 steps (a lone 1024-key block
+// took ~25 us: pure latency, and the launch is a single round of blocks); this one pays four.
+template <int CTRL>
+__device__ __forceinline__ uint64_t dpp64(uint64_t v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xf, 0xf, false);
+    return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
+}
+template <int ML>
+__device__ __forceinline__ uint64_t lane_xor64(uint64_t v)
+{
+    if (ML == 1) return dpp64<0xB1>(v);            // quad_perm [1,0,3,2]
+    if (ML == 2) return dpp64<0x4E>(v);            // quad_perm [2,3,0,1]
+    if (ML == 3) return dpp64<0x1B>(v);            // quad_perm [3,2,1,0]
+    if (ML == 4) return dpp64<0x1B>(dpp64<0x141>(v));      // 7 - i within the half row, then the quad reversed: i ^ 4
+    if (ML == 7) return dpp64<0x141>(v);           // row_half_mirror
+    if (ML == 8) return dpp64<0x128>(v);           // row_ror:8
+    if (ML == 15) return dpp64<0x140>(v);          // row_mirror
+    const int lo = __shfl_xor((int)(uint32_t)v, ML), hi = __shfl_xor((int)(uint32_t)(v >> 32), ML);
+    return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
+}
+
+// one step of the network: element i = 4 t + r is paired with i ^ M; the element whose bit TOP(M) is clear keeps the minimum
+template <int M>
+__device__ __forceinline__ void sort_step(uint64_t (&k)[4], int t, uint64_t *lds)
+{
+    constexpr int MR = M & 3, ML = (M >> 2) & 63, MW = M >> 8;
+    constexpr int TOP = M >= 512 ? 512 : M >= 256 ? 256 : M >= 128 ? 128 : M >= 64 ? 64 : M >= 32 ? 32 : M >= 16 ? 16 : M >= 8 ? 8 : M >= 4 ? 4 : M >= 2 ? 2 : 1;
+    if (ML == 0 && MW == 0) {          // both elements in this thread
+        if (MR == 1) { ce(k[0], k[1]); ce(k[2], k[3]); }
+        else if (MR == 2) { ce(k[0], k[2]); ce(k[1], k[3]); }
+        else { ce(k[0], k[3]); ce(k[1], k[2]); }
+        return;
+    }
+    uint64_t p[4];
+    if (MW != 0) {                     // partner in another wave: through LDS
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 4; r++) lds[4 * t + r] = k[r];
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 4; r++) p[r] = lds[(4 * t + r) ^ M];
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; r++) p[r] = lane_xor64<ML>(k[r ^ MR]);
+    }
+    const bool keep_min = ((4 * t) & TOP) == 0;          // (TOP >= 4 here: the same for the thread's four elements)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const bool less = p[r] < k[r];
+        k[r] = (less == keep_min) ? p[r] : k[r];
+    }
+}
+template <int J>
+__device__ __forceinline__ void sort_half_cleaners(uint64_t (&k)[4], int t, uint64_t *lds)
+{
+    if constexpr (J >= 1) {
+        sort_step<J>(k, t, lds);
+        sort_half_cleaners<J / 2>(k, t, lds);
+    }
+}
+template <int K>
+__device__ __forceinline__ void sort_level(uint64_t (&k)[4], int t, uint64_t *lds)
+{
+    sort_step<K - 1>(k, t, lds);               // mirror: i with i ^ (K - 1)
+    sort_half_cleaners<K / 4>(k, t, lds);      // strides K/4 ... 1
+}
+
+__global__ void __launch_bounds__(256) tile_presort_reg_kernel(const uint32_t *tile_offset, const uint32_t *run_total, const uint2 *run_tab,
+                                                           uint32_t max_runs, uint64_t *keys, uint64_t *tmp, uint64_t capacity,
+                                                           int passes_launched, uint32_t *zero_count, int T)
+{
+    __shared__ uint64_t s[SORT_RUN];
+    const int tid = threadIdx.x;
+    // inline-scan frames: the per-tile counters were read by the emit launch; they are cleared here (all zero between frames)
+    if (zero_count)
+        for (int q = (int)blockIdx.x * 256 + tid; q < T; q += (int)gridDim.x * 256) zero_count[q] = 0u;
+    if (blockIdx.x >= run_total[0] || blockIdx.x >= max_runs) return;      // one block per (tile, run) of the run table
+    const uint2 tr = run_tab[blockIdx.x];
+    const uint64_t beg = tile_offset[tr.x], end64 = tile_offset[tr.x + 1];
+    if (end64 > capacity) return;                 // overflowed launch: results are discarded by the host
+    const long n = (long)(end64 - beg);
+    int q;
+    const int cls = sort_class((uint64_t)n, passes_launched, q);
+    if (cls == SORT_FALLBACK) return;
+    uint64_t *dst_base = (cls == SORT_MERGEPATH && (q & 1)) ? tmp : keys;
+    const long c0 = (long)tr.y * SORT_RUN;
+    const int cn = (int)min((long)SORT_RUN, n - c0);
+    const uint64_t *g = keys + beg + c0;
+    uint64_t *d = dst_base + beg + c0;
+    if (cn <= 1) { if (cn == 1 && tid == 0) d[0] = g[0]; return; }
+    int m = 2;
+    while (m < cn) m <<= 1;
+    uint64_t k[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) k[r] = 4 * tid + r < cn ? g[4 * tid + r] : ~0ull;      // virtual +inf padding
+    sort_level<2>(k, tid, s);
+    sort_level<4>(k, tid, s);
+    if (m >= 8) sort_level<8>(k, tid, s);
+    if (m >= 16) sort_level<16>(k, tid, s);
+    if (m >= 32) sort_level<32>(k, tid, s);
+    if (m >= 64) sort_level<64>(k, tid, s);
+    if (m >= 128) sort_level<128>(k, tid, s);
+    if (m >= 256) sort_level<256>(k, tid, s);
+    if (m >= 512) sort_level<512>(k, tid, s);
+    if (m >= 1024) sort_level<1024>(k, tid, s);
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+        if (4 * tid + r < cn) d[4 * tid + r] = k[r];
+}
+
+// number of elements taken from A among the first o outputs of merge(A, B) (keys are unique)
+template <typename PA, typename PB>
+__device__ __forceinline__ int co_rank(int o, PA A, int la, PB B, int lb)
+{
+    int lo = max(0, o - lb), hi = min(o, la);
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (A[mid] < B[o - mid - 1]) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// The same co-rank found by a whole wave: 64 probes per round instead of one, so a 16 k-wide search takes three memory
+// round trips instead of fourteen (the block cannot start loading before it knows both ends of its chunk).
+__device__ __forceinline__ int co_rank_wave(int o, const uint64_t *A, int la, const uint64_t *B, int lb)
+{
+    const int lane = threadIdx.x & 63;
+    int lo = max(0, o - lb), hi = min(o, la);
+    while (lo < hi) {
+        const int step = (hi - lo + 63) / 64;
+        const int mid = lo + lane * step;
+        const bool need_more = mid < hi && A[mid] < B[o - mid - 1];      // monotone in mid: true ... true false ... false
+        const int cnt = __builtin_popcountll(__ballot(need_more));
+        const int nlo = cnt > 0 ? lo + (cnt - 1) * step + 1 : lo;
+        const int nhi = (cnt < 64 && lo + cnt * step < hi) ? lo + cnt * step : hi;
+        lo = nlo; hi = nhi;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(256) tile_mergepath_kernel(const uint32_t *tile_offset, const uint32_t *deep_first, const uint2 *deep_tab,
+                                                             uint32_t max_deep, uint64_t *keys, uint64_t *tmp, uint64_t capacity,
+                                                             int passes_launched, int pass)
+{
+    __shared__ uint64_t s[MP_CHUNK];
+    __shared__ int s_rank[2];
+    const int tid = threadIdx.x;
+    if (blockIdx.x >= deep_first[0] || blockIdx.x >= max_deep) return;      // deep_first[0] here = total number of chunks
+    const uint2 tc = deep_tab[blockIdx.x];
+    const uint64_t beg = tile_offset[tc.x], end64 = tile_offset[tc.x + 1];
+    if (end64 > capacity) return;
+    const long n = (long)(end64 - beg);
+    int q;
+    if (sort_class((uint64_t)n, passes_launched, q) != SORT_MERGEPATH || pass >= q) return;
+    const bool src_is_tmp = ((q - pass) & 1) != 0;
+    const uint64_t *src = (src_is_tmp ? tmp : keys) + beg;
+    uint64_t *dst = (src_is_tmp ? keys : tmp) + beg;
+    const long w = (long)SORT_RUN << pass;
+    const long j0 = (long)tc.y * MP_CHUNK;
+    const long base = (j0 / (2 * w)) * (2 * w);
+    const long a1 = min(n, base + w), b1 = min(n, base + 2 * w);
+    const int la = (int)(a1 - base), lb = (int)(b1 - a1);
+    const uint64_t *A = src + base, *B = src + a1;
+    const int o0 = (int)(j0 - base), o1 = (int)min((long)(o0 + MP_CHUNK), (long)(la + lb));
+    if (tid < 64) { const int r = co_rank_wave(o0, A, la, B, lb); if (tid == 0) s_rank[0] = r; }
+    else if (tid < 128) { const int r = co_rank_wave(o1, A, la, B, lb); if (tid == 64) s_rank[1] = r; }
+    __syncthreads();
+    const int ra0 = s_rank[0], ra1 = s_rank[1];
+    const int rb0 = o0 - ra0, rb1 = o1 - ra1;
+    const int na = ra1 - ra0, nb = rb1 - rb0;
+    for (int i = tid; i < na; i += 256) s[i] = A[ra0 + i];
+    for (int i = tid; i < nb; i += 256) s[na + i] = B[rb0 + i];
+    __syncthreads();
+    // each thread merges four consecutive outputs from its own co-rank inside the LDS pieces
+    const int cnt = o1 - o0;
+    const int lo = tid * 4;
+    if (lo < cnt) {
+        const uint64_t *LA = s, *LB = s + na;
+        int ia = co_rank(lo, LA, na, LB, nb), ib = lo - ia;
+        uint64_t out[4];
+        const int m = min(4, cnt - lo);
+        for (int k = 0; k < m; k++) {
+            const bool takeA = ib >= nb || (ia < na && LA[ia] < LB[ib]);
+            out[k] = takeA ? LA[ia++] : LB[ib++];
+        }
+        for (int k = 0; k < m; k++) dst[base + o0 + lo + k] = out[k];
+    }
+}
+
+__global__ void __launch_bounds__(1024) tile_merge_kernel(const uint32_t *tile_offset, const uint32_t *multi_total, const uint32_t *multi_tab,
+                                                          uint32_t max_multi, uint64_t *keys, uint64_t capacity, int passes_launched)
+{
+    constexpr int THREADS = 1024, CHUNK = SORT_BIG_CHUNK;
+    __shared__ uint64_t s[CHUNK];
+    const int tid = threadIdx.x;
+    if (blockIdx.x >= multi_total[0] || blockIdx.x >= max_multi) return;     // one block per tile with more than one run
+    const uint32_t tile = multi_tab[blockIdx.x];
+    const uint64_t beg = tile_offset[tile], end64 = tile_offset[tile + 1];
+    if (end64 > capacity) return;
+    const long n = (long)(end64 - beg);
+    int q;
+    const int cls = sort_class((uint64_t)n, passes_launched, q);
+    if (cls == SORT_SINGLE || cls == SORT_MERGEPATH) return;
+    uint64_t *g = keys + beg;
+    long np2 = 2;
+    while (np2 < n) np2 <<= 1;
+    const uint64_t INF = ~0ull;
+
+    if (cls == SORT_LDS) {
+        // The runs of SORT_RUN keys are sorted: merge them level by level inside LDS with merge path -- every thread
+        // finds the co-rank of its K consecutive outputs by binary search, merges them into registers, and the level
+        // is written back after a barrier (no second buffer).  ~30 dependent LDS reads per level instead of the
+        // 11-13 compare-exchange sub-stages of a bitonic merge level.
+        const int m = (int)np2;                   // 2048, 4096 or 8192: runs padded with +inf
+        for (int i = tid; i < m; i += THREADS) s[i] = i < n ? g[i] : INF;
+        __syncthreads();
+        const int K = m / THREADS;                // 2, 4 or 8 outputs per thread
+        for (int w = SORT_RUN; w < m; w <<= 1) {
+            const int o = tid * K;
+            const int base = (o / (2 * w)) * (2 * w);
+            const uint64_t *LA = s + base, *LB = s + base + w;
+            const int lo = o - base;
+            int ia = co_rank(lo, LA, w, LB, w), ib = lo - ia;
+            uint64_t out[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                if (k < K) {
+                    const bool takeA = ib >= w || (ia < w && LA[ia] < LB[ib]);
+                    out[k] = takeA ? LA[ia++] : LB[ib++];
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                if (k < K) s[o + k] = out[k];
+            __syncthreads();
+        }
+        for (int i = tid; i < n; i += THREADS) g[i] = s[i];
+        return;
+    }
+    // fallback (deeper than the launched merge-path passes cover): sort CHUNK-sized runs in LDS, then merge with
+    // wide strides in global memory, all by this one block
+    for (long c = 0; c < n; c += CHUNK) {
+        for (int i = tid; i < CHUNK; i += THREADS) s[i] = (c + i) < n ? g[c + i] : INF;
+        lds_bitonic<THREADS>(s, CHUNK, 2, 0, true, tid);
+        for (int i = tid; i < CHUNK; i += THREADS)
+            if (c + i < n) g[c + i] = s[i];
+        __syncthreads();
+    }
+    for (long k = 2L * CHUNK; k <= np2; k <<= 1) {
+        const long hk = k >> 1;
+        for (long i = tid; i < (np2 >> 1); i += THREADS) {        // mirror step
+            long blk = i / hk, off = i - blk * hk;
+            long lo = blk * k + off, hi = blk * k + k - 1 - off;
+            if (hi < n) { uint64_t x = g[lo], y = g[hi]; if (x > y) { g[lo] = y; g[hi] = x; } }
+        }
+        __syncthreads();
+        for (long j = k >> 2; j >= CHUNK; j >>= 1) {              // strides that cross LDS chunks
+            for (long i = tid; i < (np2 >> 1); i += THREADS) {
+                long lo = 2 * j * (i / j) + (i % j), hi = lo + j;
+                if (hi < n) { uint64_t x = g[lo], y = g[hi]; if (x > y) { g[lo] = y; g[hi] = x; } }
+            }
+            __syncthreads();
+        }
+        for (long c = 0; c < n; c += CHUNK) {                      // remaining strides inside a chunk
+            for (int i = tid; i < CHUNK; i += THREADS) s[i] = (c + i) < n ? g[c + i] : INF;
+            lds_bitonic<THREADS>(s, CHUNK, CHUNK, CHUNK >> 1, false, tid);
+            for (int i = tid; i < CHUNK; i += THREADS)
+                if (c + i < n) g[c + i] = s[i];
+            __syncthreads();
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------ host side
+int merge_path_passes(uint32_t deepest, uint32_t headroom)
+{
+    return deepest > (uint32_t)SORT_BIG_CHUNK ? sort_passes((uint64_t)deepest + headroom) : 0;
+}
+
+// (every emit block repeats the scan and holds the offsets in LDS, 29 KB per block instead of 12: it pays while the emit blocks
+// are one resident round -- headline scene: 2 354 -> 2 434 it/s -- and loses beyond, config-5 size: emit 117 -> 141 us)
+bool inline_scan_fits(int T, int P) { return T <= INLINE_SCAN_MAX_T && (P + BLOCK - 1) / BLOCK <= 1536; }
+
+int32_t launch_tile_scan(const BinningFrame &f, bool debug, hipStream_t stream)
+{
+    const ImageState &img = f.img;
+    GMS_LAUNCH(GMS_K_TILE_SCAN, stream, tile_scan_kernel<<<1, SCAN_THREADS, 0, stream>>>(img.tile_count, img.tile_offset, img.tile_cursor,
+                                                                                   img.unit_first, img.mseg_first, img.class_first, f.T, f.frame_L,
+                                                                                   f.pub_slot, f.seq, f.scan_np, img.scan_out));
+    GMS_KERNEL_CHECK(debug, stream, "tile_scan");
+    return GMS_OK;
+}
+
+int32_t launch_emit_sort(const BinningFrame &f, const BinningState &bin, uint64_t capacity, uint32_t max_units, bool inl, int fill_np, int sort_np,
+                         bool *presort_enqueued, bool debug, hipStream_t stream)
+{
+    const ImageState &img = f.img;
+    const int T = f.T;
+    const uint32_t max_deep = (uint32_t)BinningState::n_deep((size_t)capacity, (size_t)T);
+    const uint32_t max_multi = (uint32_t)BinningState::n_multi((size_t)capacity);
+    FillUnitsArgs fu;
+    fu.class_first = img.class_first; fu.offset = img.tile_offset; fu.mseg_first = img.mseg_first;
+    fu.unit_tile = bin.unit_tile; fu.deep_tab = bin.deep_tab; fu.multi_tab = bin.multi_tab;
+    fu.max_multi = max_multi; fu.T = T; fu.sort_np = fill_np; fu.scan_out = img.scan_out; fu.max_units = max_units;
+    fu.max_deep = max_deep;
+    const unsigned pblocks = (unsigned)((f.P + BLOCK - 1) / BLOCK), fblocks = (unsigned)((T + BLOCK - 1) / BLOCK);
+    InlineScanArgs isa{img.tile_count, img.tile_offset, img.unit_first, img.mseg_first, img.class_first, img.scan_out, f.frame_L};
+    *presort_enqueued = false;
+    if (inl)
+        GMS_LAUNCH(GMS_K_EMIT, stream, emit_instances_kernel<true><<<pblocks + fblocks, BLOCK, 0, stream>>>(f.P, f.gx, f.gy, f.radii, f.geom, img.tile_offset,
+                                                                                                             img.tile_cursor, bin.keys, capacity, pblocks, fu,
+                                                                                                             f.pub_slot, f.seq, img.scan_out, isa));
+    else
+        GMS_LAUNCH(GMS_K_EMIT, stream, emit_instances_kernel<false><<<pblocks + fblocks, BLOCK, 0, stream>>>(f.P, f.gx, f.gy, f.radii, f.geom, img.tile_offset,
+                                                                                                              img.tile_cursor, bin.keys, capacity, pblocks, fu,
+                                                                                                              nullptr, f.seq, img.scan_out, isa));
+    GMS_KERNEL_CHECK(debug, stream, "emit_instances");
+    uint64_t *sort_tmp = reinterpret_cast<uint64_t *>(bin.seg_state);      // free until compositing
+    const uint32_t *run_total = img.class_first + NCLASS * ((size_t)T + 1) + T;
+    const uint32_t *multi_total = img.class_first + (NCLASS + 1) * ((size_t)T + 1) + T;
+    GMS_LAUNCH(GMS_K_TILE_SORT, stream, tile_presort_reg_kernel<<<max_deep, 256, 0, stream>>>(img.tile_offset, run_total, bin.deep_tab, max_deep, bin.keys,
+                                                                                             sort_tmp, capacity, sort_np, inl ? img.tile_count : nullptr, T));
+    *presort_enqueued = true;
+    for (int pass = 0; pass < sort_np; pass++)
+        GMS_LAUNCH(GMS_K_TILE_SORT, stream, tile_mergepath_kernel<<<max_deep, 256, 0, stream>>>(img.tile_offset, run_total, bin.deep_tab, max_deep, bin.keys,
+                                                                                               sort_tmp, capacity, sort_np, pass));
+    // (a merge by RANK -- K interleaved binary searches per thread instead of co-rank + serial merge -- was measured in round 5 and is
+    //  slower, tile_sort 32.5 -> 58 us: profiles/r05c_ab_merge.txt; the code is in the history of round 5)
+    GMS_LAUNCH(GMS_K_TILE_SORT, stream, tile_merge_kernel<<<max_multi, 1024, 0, stream>>>(img.tile_offset, multi_total, bin.multi_tab, max_multi, bin.keys,
+                                                                                         capacity, sort_np));
+    GMS_KERNEL_CHECK(debug, stream, "tile_sort");
+    return GMS_OK;
+}
+
+}  // namespace gms

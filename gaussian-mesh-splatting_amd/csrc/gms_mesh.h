@@ -1,5 +1,5 @@
 // gms_mesh.h -- the face-frame arithmetic of the mesh-face -> Gaussian parameterization (K0), shared by mesh_to_gaussians.hip and
-// by the fused animated forward of raster_forward.hip (which derives centre / scale / rotation inside the preprocess thread).
+// by the fused animated forward of preprocess_fwd.hip (which derives centre / scale / rotation inside the preprocess thread).
 // games/mesh_splatting/scene/gaussian_mesh_model.py:86-169, utils/general_utils.py:43-96; contraction off throughout, so both
 // users produce the same bits.
 #pragma once

@@ -1,6 +1,6 @@
 // gms_points.h -- the pseudo-triangle arithmetic of the flat-Gaussian pseudo-mesh workflow (gs_points): triangle -> Gaussian and its
 // backward, Gaussian -> triangle.  Shared by points.hip (the standalone kernels) and by the fused animated forward of
-// raster_forward.hip (which derives centre / scale / rotation / opacity inside the preprocess thread).
+// preprocess_fwd.hip (which derives centre / scale / rotation / opacity inside the preprocess thread).
 // games/flat_splatting/scene/points_gaussian_model.py:28-109, utils/general_utils.py:43-96 and :158-179; contraction off throughout, so
 // both users produce the same bits.
 #pragma once

@@ -330,7 +330,7 @@ __global__ void __launch_bounds__(BLOCK) det_vertex_gather_wave_kernel(int V, co
     if (lane == 0) { dL_dvertices[3 * (size_t)v] = gx; dL_dvertices[3 * (size_t)v + 1] = gy; dL_dvertices[3 * (size_t)v + 2] = gz; }
 }
 
-// shared with the fused mesh input of gms_rasterize_forward (raster_forward.hip), which reads the same tables in splat_from_face
+// shared with the fused mesh input of gms_rasterize_forward (preprocess_fwd.hip), which reads the same tables in splat_from_face
 int32_t check_mesh_args(const GmsMeshArgs *A, bool need_face_offsets)
 {
     if (!A || A->F < 0 || A->P < 0 || A->V < 0) { set_error("mesh args: negative size"); return GMS_ERR_INVALID_ARGUMENT; }

@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(BLOCK) points_verts_kernel(int64_t P, const fl
     for (int k = 0; k < 9; k++) out_triangles[9 * p + k] = out[k];
 }
 
-// shared with the fused points input of gms_rasterize_forward (raster_forward.hip)
+// shared with the fused points input of gms_rasterize_forward (preprocess_fwd.hip)
 int32_t check_points_args(const GmsPointsArgs *A)
 {
     if (!A || A->P < 0) { set_error("points args: negative size"); return GMS_ERR_INVALID_ARGUMENT; }

@@ -25,7 +25,7 @@ def fma32(a, b, c):
 
 
 def cull_extents(a, d, cA, cB, cC, op):
-    """raster_forward.hip::cull_extents in numpy float32: the box of {Q <= thr_G}."""
+    """gms_blend.h::cull_extents in numpy float32: the box of {Q <= thr_G}."""
     with np.errstate(all="ignore"):
         tau = np.log(F(255.0) * op).astype(F)
         thr0 = (F(2) * (tau + F(1e-3)) * F(1.0001) + F(0.01)).astype(F)

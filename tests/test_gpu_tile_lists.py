@@ -9,7 +9,7 @@ move a pixel by 1e-4.  tests/test_staircase_cpu.py holds the comparer's negative
 these tests from passing by accident.  After the lists, tests/test_gpu_raster.py::_check runs on the same scene under the suite's
 criterion unchanged (image, inverse depth, radii, gradients in deterministic and float-atomics mode).
 
-Sort class per tile and frame (csrc/raster_forward.hip: `sort_class(n, passes_launched)`; the host launches
+Sort class per tile and frame (csrc/binning.hip: `sort_class(n, passes_launched)`; the host launches
 sort_np = sort_passes(1.25 x deepest tile of the PREVIOUS frame of this (device, stream, W, H, P)) merge-path passes when that tile was
 deeper than 8 192 keys, else none; `_sort_class` below restates both and the tests assert the table):
 
@@ -61,7 +61,7 @@ def _sort_np(prev_deepest):
 
 
 def _sort_class(n, passes):
-    """sort_class of csrc/raster_forward.hip -> (class, merge-path passes of the tile)"""
+    """sort_class of csrc/binning.hip -> (class, merge-path passes of the tile)"""
     if n <= 1:
         return "none", 0
     if n <= SORT_RUN:

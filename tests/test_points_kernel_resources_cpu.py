@@ -1,5 +1,5 @@
 """CPU (hipcc cross-compiles gfx950 here): what the gs_points kernels and the preprocess instantiations of the frame straight from
-pseudo-triangles (csrc/points.hip, raster_forward.hip) ask of a CU, from the compiler's own resource remarks (tools/kernel_resources.py)."""
+pseudo-triangles (csrc/points.hip, preprocess_fwd.hip) ask of a CU, from the compiler's own resource remarks (tools/kernel_resources.py)."""
 import os
 import shutil
 import sys
@@ -18,7 +18,7 @@ def table():
     import kernel_resources as kr
     out = {}
     with tempfile.TemporaryDirectory() as tmp:
-        for f in ("points.hip", "raster_forward.hip"):
+        for f in ("points.hip", "preprocess_fwd.hip"):
             ks = kr.remarks(f, tmp)
             for k, n in zip(ks, kr.demangle([k["name"] for k in ks])):
                 out[n] = k

@@ -19,7 +19,7 @@ pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.ex
 def test_headline_preprocess_fwd_fits_five_blocks_per_cu_without_spilling():
     import kernel_resources as kr
     with tempfile.TemporaryDirectory() as tmp:
-        ks = kr.remarks("raster_forward.hip", tmp)
+        ks = kr.remarks("preprocess_fwd.hip", tmp)
     table = dict(zip(kr.demangle([k["name"] for k in ks]), ks))
     k = table["preprocess_fwd_dma_kernel<true, 3>"]
     assert k["occ"] == 5 and k["vgpr"] <= 96 and k["lds"] <= 32768, k
