@@ -1,4 +1,10 @@
-// blend.hip -- per-tile alpha compositing (forward and backward) for gfx950, segment-parallel.
+// blend.hip -- per-tile alpha compositing (forward and backward) for gfx950: the quadrant-wave kernels, and the host launches of
+// both compositing families.
+//
+// The segment-parallel scheme itself -- prefix products, partials, dead-tile check, finalize, the backward's restart -- lives in
+// gms_segments.h and is shared with blend_micro.hip.  This file adds the quadrant walk (tloc_unit, fwd_unit, blend_bwd_kernel: a wave
+// per 8x8 quadrant on a 64-entry LDS queue with ballot culls), the kernel entry points, and the one place on the host that knows there
+// are two families (launch_compositing_forward / launch_compositing_backward at the end of the file).
 //
 // A tile's depth-sorted splat list is cut into segments of at most L entries (L = seg_len,
 // default 128); one work UNIT = (tile, segment).  A unit is walked by four independent waves, each owning an
@@ -32,17 +38,20 @@
 
 #include "gms_common.h"
 #include "gms_blend.h"
+#include "gms_segments.h"
 
 namespace gms {
 
 struct Pix {
     int xi, yi; bool inside; float xf, yf; float wx0, wy0, wx1, wy1;
+    static __device__ __forceinline__ Pix of_tile(const BlendGrid &g, int tile);      // thread threadIdx.x of a 256-thread block per tile
 };
 
-__device__ __forceinline__ Pix pixel_of(const BlendGrid &g, const Unit &u, int wave)
+// pixel `lane` of quadrant `wave` of tile (tx, ty); its index in the segment state is wave * 64 + lane (quadrant-major)
+__device__ __forceinline__ Pix pixel_of(const BlendGrid &g, int tx, int ty, int wave)
 {
     const int lane = threadIdx.x & 63;
-    const int qx = u.tx * TILE + (wave & 1) * 8, qy = u.ty * TILE + (wave >> 1) * 8;
+    const int qx = tx * TILE + (wave & 1) * 8, qy = ty * TILE + (wave >> 1) * 8;
     Pix p;
     p.xi = qx + (lane & 7); p.yi = qy + (lane >> 3);
     p.inside = p.xi < g.W && p.yi < g.H;
@@ -50,7 +59,8 @@ __device__ __forceinline__ Pix pixel_of(const BlendGrid &g, const Unit &u, int w
     p.wx0 = (float)qx; p.wy0 = (float)qy; p.wx1 = (float)(qx + 7); p.wy1 = (float)(qy + 7);
     return p;
 }
-__device__ __forceinline__ Pix pixel_of(const BlendGrid &g, const Unit &u) { return pixel_of(g, u, (int)(threadIdx.x >> 6)); }
+__device__ __forceinline__ Pix pixel_of(const BlendGrid &g, const Unit &u, int wave) { return pixel_of(g, u.tx, u.ty, wave); }
+__device__ __forceinline__ Pix Pix::of_tile(const BlendGrid &g, int tile) { return pixel_of(g, tile % g.gx, tile / g.gx, (int)(threadIdx.x >> 6)); }
 
 __device__ __forceinline__ bool quadrant_hit(const SplatRec *recs, int j, int cnt, const Pix &p, bool bbox_only = false)
 {
@@ -111,21 +121,9 @@ __device__ __forceinline__ void tloc_unit(const BlendGrid &g, const SplatRec *re
     g.seg_state[(size_t)(u.slot0 + u.seg) * SEG_FLOATS + SEG_TLOC * TILE_PIX + tid] = Tl;
 }
 
-// tile_dead[t] = 1 when the product of the first tloc_head(L) segment transmittances is < 1e-4 for every pixel
 __global__ void __launch_bounds__(BLOCK) blend_tloc_check_kernel(BlendGrid g)
 {
-    const int tile = blockIdx.x;
-    const int nseg = (int)(g.unit_first[tile + 1] - g.unit_first[tile]);
-    const int nhead = tloc_head(g.scan_out[3]);
-    if (nseg <= nhead + 1) return;                 // no phase-1 segment exists (the last one needs no product)
-    if ((uint64_t)g.tile_offset[tile + 1] > g.capacity) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int xi = (tile % g.gx) * TILE + (wave & 1) * 8 + (lane & 7), yi = (tile / g.gx) * TILE + (wave >> 1) * 8 + (lane >> 3);
-    const float *st0 = g.seg_state + (size_t)g.mseg_first[tile] * SEG_FLOATS;
-    float T = 1.f;
-    for (int k = 0; k < nhead; k++) T *= st0[(size_t)k * SEG_FLOATS + SEG_TLOC * TILE_PIX + tid];
-    const int dead = __syncthreads_and(T < T_MIN || xi >= g.W || yi >= g.H);
-    if (tid == 0) g.tile_dead[tile] = dead ? 1u : 0u;
+    tile_dead_check<Pix>(g);
 }
 
 // ------------------------------------------------------------------------------------ fwd
@@ -135,18 +133,7 @@ __device__ __forceinline__ void fwd_unit(const BlendGrid &g, const BlendFwdOut &
     const int qt = threadIdx.x, lane = qt & 63, tid = wave * WAVE + lane;
     const Pix p = pixel_of(g, u, wave);
 
-    float T = 1.f;
-    {
-        // prefix product of the segments in front, four independent loads per step (same left-to-right order)
-        const float *tl = g.seg_state + (size_t)u.slot0 * SEG_FLOATS + SEG_TLOC * TILE_PIX + tid;
-        int k = 0;
-        for (; k + 4 <= u.seg; k += 4) {
-            const float t0 = tl[(size_t)k * SEG_FLOATS], t1 = tl[(size_t)(k + 1) * SEG_FLOATS];
-            const float t2 = tl[(size_t)(k + 2) * SEG_FLOATS], t3 = tl[(size_t)(k + 3) * SEG_FLOATS];
-            T = T * t0 * t1 * t2 * t3;
-        }
-        for (; k < u.seg; k++) T *= tl[(size_t)k * SEG_FLOATS];
-    }
+    float T = prefix_transmittance<4>(g, u, tid);
     const bool dead_on_entry = T < T_MIN;          // only possible for seg > 0
     float C0 = 0.f, C1 = 0.f, C2 = 0.f, Dp = 0.f;
     uint32_t last = 0;
@@ -188,27 +175,8 @@ __device__ __forceinline__ void fwd_unit(const BlendGrid &g, const BlendFwdOut &
             }
         }
     }
-    if (u.nseg == 1) {
-        if (p.inside) {
-            const size_t pid = (size_t)p.yi * g.W + p.xi, HW = (size_t)g.W * g.H;
-            o.final_T[pid] = T;
-            o.n_contrib[pid] = last;
-            o.out_color[pid] = C0 + T * o.bg[0];
-            o.out_color[HW + pid] = C1 + T * o.bg[1];
-            o.out_color[2 * HW + pid] = C2 + T * o.bg[2];
-            o.out_invdepth[pid] = Dp;
-        }
-    } else {
-        float *st = g.seg_state + (size_t)(u.slot0 + u.seg) * SEG_FLOATS;
-        st[SEG_C0 * TILE_PIX + tid] = C0; st[SEG_C1 * TILE_PIX + tid] = C1; st[SEG_C2 * TILE_PIX + tid] = C2;
-        st[SEG_D * TILE_PIX + tid] = Dp;
-        st[SEG_TEND * TILE_PIX + tid] = dead_on_entry ? -1.f : T;
-        st[SEG_LAST * TILE_PIX + tid] = __uint_as_float(last);
-        // the first segment's exact walk doubles as its transmittance product: a pixel that terminated here is
-        // dead on entry to every later segment (any value < 1e-4 says so); one that did not has multiplied
-        // exactly the (1 - alpha) factors the product would
-        if (u.seg == 0) st[SEG_TLOC * TILE_PIX + tid] = alive == 0 ? 0.f : T;
-    }
+    if (u.nseg == 1) write_pixel(g, o, p, T, last, C0, C1, C2, Dp);
+    else store_partials(g, u, tid, T, last, C0, C1, C2, Dp, dead_on_entry, alive == 0);
 }
 
 // First launch: every unit that depends on nothing -- the exact walk of each tile's FIRST segment (single-segment
@@ -243,46 +211,7 @@ __global__ void __launch_bounds__(WAVE) blend_fwd_kernel(BlendGrid g, BlendFwdOu
 // ------------------------------------------------------------------------------------ finalize
 __global__ void __launch_bounds__(BLOCK) blend_finalize_kernel(BlendGrid g, BlendFwdOut o)
 {
-    const int tile = blockIdx.x;
-    const uint32_t first = g.unit_first[tile];
-    const int nseg = (int)(g.unit_first[tile + 1] - first);
-    if (nseg <= 1) return;
-    if ((uint64_t)g.tile_offset[tile + 1] > g.capacity) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tx = tile % g.gx, ty = tile / g.gx;
-    const int xi = tx * TILE + (wave & 1) * 8 + (lane & 7), yi = ty * TILE + (wave >> 1) * 8 + (lane >> 3);
-    float *st0 = g.seg_state + (size_t)g.mseg_first[tile] * SEG_FLOATS;
-    float C0 = 0.f, C1 = 0.f, C2 = 0.f, Dp = 0.f, T = 1.f;
-    uint32_t last = 0;
-    // four segments per step, every load issued before the first use: a 27-segment tile is otherwise 27 dependent
-    // memory round trips, and this kernel's duration is its deepest tile
-    constexpr int U = 4;
-    for (int k0 = 0; k0 < nseg; k0 += U) {
-        float te[U], c0[U], c1[U], c2[U], dd[U], la[U];
-#pragma unroll
-        for (int j = 0; j < U; j++) {
-            const float *st = st0 + (size_t)min(k0 + j, nseg - 1) * SEG_FLOATS;
-            te[j] = st[SEG_TEND * TILE_PIX + tid]; c0[j] = st[SEG_C0 * TILE_PIX + tid]; c1[j] = st[SEG_C1 * TILE_PIX + tid];
-            c2[j] = st[SEG_C2 * TILE_PIX + tid]; dd[j] = st[SEG_D * TILE_PIX + tid]; la[j] = st[SEG_LAST * TILE_PIX + tid];
-        }
-#pragma unroll
-        for (int j = 0; j < U; j++) {
-            if (k0 + j < nseg && te[j] >= 0.f) {          // a segment entered dead (te < 0) contributed nothing
-                C0 += c0[j]; C1 += c1[j]; C2 += c2[j]; Dp += dd[j];
-                T = te[j];
-                last = max(last, __float_as_uint(la[j]));
-            }
-        }
-    }
-    if (xi < g.W && yi < g.H) {
-        const size_t pid = (size_t)yi * g.W + xi, HW = (size_t)g.W * g.H;
-        o.final_T[pid] = T;
-        o.n_contrib[pid] = last;
-        o.out_color[pid] = C0 + T * o.bg[0];
-        o.out_color[HW + pid] = C1 + T * o.bg[1];
-        o.out_color[2 * HW + pid] = C2 + T * o.bg[2];
-        o.out_invdepth[pid] = Dp;
-    }
+    finalize_tile<4, Pix>(g, o);          // (four segments per step)
 }
 
 // ------------------------------------------------------------------------------------ bwd
@@ -309,50 +238,12 @@ __global__ void __launch_bounds__(WAVE) blend_bwd_kernel(BlendGrid g, BlendBwdAr
     const int tid = wave * WAVE + lane;                  // pixel index inside the tile (quadrant-major)
     Stamp stamp(dbg_on(g, 16u) ? g.dbg_buf : nullptr);
     const Pix p = pixel_of(g, u, wave);
-    const size_t HW = (size_t)g.W * g.H;
-    const size_t pid = (size_t)p.yi * g.W + p.xi;
-    const float Tfinal = p.inside ? a.final_T[pid] : 0.f;
-    const uint32_t last = p.inside ? a.n_contrib[pid] : 0u;      // 1-based position of the last applied splat
-    float dp0 = 0.f, dp1 = 0.f, dp2 = 0.f, dinvd = 0.f;
-    if (p.inside) {
-        dp0 = a.dL_dpix[pid]; dp1 = a.dL_dpix[HW + pid]; dp2 = a.dL_dpix[2 * HW + pid];
-        if (INVD) dinvd = a.dL_dinvd[pid];
-    }
-    const float Tfinal_bgdot = Tfinal * (a.bg[0] * dp0 + a.bg[1] * dp1 + a.bg[2] * dp2);
+    const BwdPixel bp = bwd_pixel<INVD>(g, a, p);
+    const uint32_t last = bp.last;                               // 1-based position of the last applied splat
+    const float dp0 = bp.dp0, dp1 = bp.dp1, dp2 = bp.dp2, dinvd = bp.dinvd, Tfinal_bgdot = bp.Tfinal_bgdot;
     const uint32_t seg_lo = u.beg - u.tile_beg, seg_hi = u.end - u.tile_beg;   // positions covered by this unit
-
-    BwdState st8 = {Tfinal, 0.f, 0.f, 0.f, 0.f};
-    if (u.nseg > 1) {
-        const float *st = g.seg_state + (size_t)(u.slot0 + u.seg) * SEG_FLOATS;
-        const float te = st[SEG_TEND * TILE_PIX + tid];
-        if (te > 0.f) {
-            // restart of the recurrence at the segment boundary: T after this segment's last applied splat and
-            // the colour composited behind it (sum of the live partials of the later segments) divided by that T
-            st8.T = te;
-            float S0 = 0.f, S1 = 0.f, S2 = 0.f, SD = 0.f;
-            // a pixel that is dead on entry to segment k is dead for every later one: stop at the first.  Four
-            // segments per step with all loads issued up front (a deep tile is otherwise a chain of round trips).
-            bool stop = false;
-            for (int k0 = u.seg + 1; k0 < u.nseg; k0 += 4) {
-                float tk[4], c0[4], c1[4], c2[4], dd[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const float *sk = g.seg_state + (size_t)(u.slot0 + min(k0 + j, u.nseg - 1)) * SEG_FLOATS;
-                    tk[j] = sk[SEG_TEND * TILE_PIX + tid]; c0[j] = sk[SEG_C0 * TILE_PIX + tid];
-                    c1[j] = sk[SEG_C1 * TILE_PIX + tid]; c2[j] = sk[SEG_C2 * TILE_PIX + tid];
-                    dd[j] = INVD ? sk[SEG_D * TILE_PIX + tid] : 0.f;
-                }
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    if (k0 + j >= u.nseg || tk[j] < 0.f) stop = true;
-                    if (!stop) { S0 += c0[j]; S1 += c1[j]; S2 += c2[j]; SD += dd[j]; }
-                }
-                if (__all(stop)) break;
-            }
-            const float inv = FAULT == 2 ? 0.f : 1.f / te;
-            st8.acc0 = S0 * inv; st8.acc1 = S1 * inv; st8.acc2 = S2 * inv; st8.accd = SD * inv;
-        }
-    }
+    BwdState st8 = {bp.Tfinal, 0.f, 0.f, 0.f, 0.f};
+    bwd_restart<INVD, FAULT, 4>(g, u, tid, st8);
 
     // wave_reduce10 leaves the ten totals in lanes 0,8,...,56 (y0) and 4, 36 (y1): those ten lanes add
     // into the ten fields of the splat's 64-byte gradient record with ONE atomic instruction.
@@ -479,49 +370,70 @@ void experiment_switches(BlendGrid &g, uint32_t buf_bits, hipStream_t stream)
         if (g_dbg_buf) { (void)hipMemsetAsync(g_dbg_buf, 0, DBG_BYTES, stream); g.dbg_buf = g_dbg_buf; }
     }
 }
-int32_t launch_blend_forward(const BlendGrid &g_in, const BlendFwdOut &o, uint32_t max_units, bool debug, hipStream_t stream)
+
+const BlendFamily &quadrant_family()
 {
-    BlendGrid g = g_in;
-    experiment_switches(g, 128u | 256u, stream);
-    // two-phase transmittance products pay off when tiles are deep on average (> 2 segments per tile over the
-    // whole image); shallow scenes take one launch
+    static const BlendFamily f = {
+        blend_head_kernel<4>, blend_tloc_check_kernel, blend_fwd_kernel<4>, blend_finalize_kernel,          // (4 entries per trip)
+        {{blend_bwd_kernel<false, 4>, blend_bwd_kernel<false, 4, 0, true>, blend_bwd_kernel<false, 4, 2>},
+         {blend_bwd_kernel<true, 4>, blend_bwd_kernel<true, 4, 0, true>, blend_bwd_kernel<true, 4>}},       // (fault 2 has no inverse-depth form)
+        4u, WAVE, 128u | 256u, 16u, 4u, "blend_head", "blend_fwd", "blend_finalize", "blend_bwd"};
+    return f;
+}
+
+// ---- both families: who takes a frame, and the launch sequences
+static const BlendFamily &family_of(const BlendGrid &g) { return use_micro(g.capacity, g.T) ? micro_family() : quadrant_family(); }
+uint32_t compositing_det_nsub(const BlendGrid &g) { return family_of(g).det_nsub; }
+
+// Two-phase transmittance products pay off when tiles are deep on average (> 2 segments per tile over the whole image);
+// shallow scenes take one launch.  GMS_DEEP = 0 / 1 forces either.
+static bool two_phase_products(const BlendGrid &g)
+{
     static int deep_env = -2;
     if (deep_env == -2) { const char *e = getenv("GMS_DEEP"); deep_env = e ? atoi(e) : -1; }
-    const bool deep = deep_env >= 0 ? deep_env != 0 : g.capacity > 512ull * (uint64_t)g.T;
-    const unsigned blocks = blend_grid_units(max_units);
-    auto head = blend_head_kernel<4>;          // (4 entries per trip)
-    const unsigned wblocks = 4u * blocks;      // one 64-thread block per (unit, quadrant)
-    if (deep) {     // deep scene: head segments, tile-dead check, then the tail segments of the tiles still alive
-        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<wblocks, WAVE, 0, stream>>>(g, o, 0));
-        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, blend_tloc_check_kernel<<<(unsigned)g.T, BLOCK, 0, stream>>>(g));
-        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<wblocks, WAVE, 0, stream>>>(g, o, 1));
-    } else {
-        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<wblocks, WAVE, 0, stream>>>(g, o, -1));
+    return deep_env >= 0 ? deep_env != 0 : g.capacity > 512ull * (uint64_t)g.T;
+}
+
+int32_t launch_compositing_forward(const BlendGrid &g_in, const BlendFwdOut &o, uint32_t frame_L, uint32_t max_units, bool debug, hipStream_t stream,
+                                   bool *used_micro)
+{
+    const BlendFamily &f = family_of(g_in);
+    *used_micro = &f == &micro_family();
+    // the micro-tile kernels index a unit's entries with one byte: never launch them on a frame whose L they cannot hold.  (The
+    // backward of such a frame does not exist: it needs this forward's buffers.)
+    if (*used_micro && (frame_L == 0 || frame_L > SEG_LEN_MICRO)) {
+        set_error("internal: micro-tile compositing chosen for a frame with segment length %u", frame_L);
+        return GMS_ERR_INVALID_ARGUMENT;
     }
-    GMS_KERNEL_CHECK(debug, stream, "blend_head");
-    GMS_LAUNCH(GMS_K_BLEND_FWD, stream, blend_fwd_kernel<4><<<wblocks, WAVE, 0, stream>>>(g, o));
-    GMS_KERNEL_CHECK(debug, stream, "blend_fwd");
-    GMS_LAUNCH(GMS_K_BLEND_FINALIZE, stream, blend_finalize_kernel<<<(unsigned)g.T, BLOCK, 0, stream>>>(g, o));
-    GMS_KERNEL_CHECK(debug, stream, "blend_finalize");
+    BlendGrid g = g_in;
+    experiment_switches(g, f.fwd_stamps, stream);
+    const unsigned blocks = f.blocks_per_unit * blend_grid_units(max_units), tiles = (unsigned)g.T;
+    const auto head = f.head;
+    if (two_phase_products(g)) {     // deep scene: head segments, tile-dead check, then the tail segments of the tiles still alive
+        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<blocks, f.threads, 0, stream>>>(g, o, 0));
+        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, f.check<<<tiles, BLOCK, 0, stream>>>(g));
+        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<blocks, f.threads, 0, stream>>>(g, o, 1));
+    } else {
+        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<blocks, f.threads, 0, stream>>>(g, o, -1));
+    }
+    GMS_KERNEL_CHECK(debug, stream, f.head_name);
+    GMS_LAUNCH(GMS_K_BLEND_FWD, stream, f.fwd<<<blocks, f.threads, 0, stream>>>(g, o));
+    GMS_KERNEL_CHECK(debug, stream, f.fwd_name);
+    GMS_LAUNCH(GMS_K_BLEND_FINALIZE, stream, f.finalize<<<tiles, BLOCK, 0, stream>>>(g, o));
+    GMS_KERNEL_CHECK(debug, stream, f.finalize_name);
     return GMS_OK;
 }
 
-int32_t launch_blend_backward(const BlendGrid &g_in, const BlendBwdArgs &a, uint32_t max_units, bool debug, hipStream_t stream)
+int32_t launch_compositing_backward(const BlendGrid &g_in, const BlendBwdArgs &a, uint32_t max_units, bool debug, hipStream_t stream)
 {
+    const BlendFamily &f = family_of(g_in);
     BlendGrid g = g_in;
-    experiment_switches(g, 16u, stream);
-    const unsigned blocks = blend_grid_units(max_units);
+    experiment_switches(g, f.bwd_stamps, stream);
     const bool invd = a.has_invd && a.dL_dinvd;
-    if (a.part) {                           // deterministic mode (gmsplat.h): stores into per-(instance, quadrant) partial records
-        if (invd) GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (blend_bwd_kernel<true, 4, 0, true><<<4u * blocks, WAVE, 0, stream>>>(g, a)));
-        else GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (blend_bwd_kernel<false, 4, 0, true><<<4u * blocks, WAVE, 0, stream>>>(g, a)));
-    } else if (fault_mode() == 2 && !invd) {       // negative control (gms_set_fault): its own instantiation
-        GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (blend_bwd_kernel<false, 4, 2><<<4u * blocks, WAVE, 0, stream>>>(g, a)));
-    } else {
-        auto kern = invd ? blend_bwd_kernel<true, 4> : blend_bwd_kernel<false, 4>;          // (4 entries per trip)
-        GMS_LAUNCH(GMS_K_BLEND_BWD, stream, kern<<<4u * blocks, WAVE, 0, stream>>>(g, a));
-    }
-    GMS_KERNEL_CHECK(debug, stream, "blend_bwd");
+    // deterministic mode (gmsplat.h; a.part: stores into partial records) before the negative control (gms_set_fault) before production
+    const auto kern = f.bwd[invd ? 1 : 0][a.part ? 1 : (fault_mode() == 2 ? 2 : 0)];
+    GMS_LAUNCH(GMS_K_BLEND_BWD, stream, kern<<<f.blocks_per_unit * blend_grid_units(max_units), f.threads, 0, stream>>>(g, a));
+    GMS_KERNEL_CHECK(debug, stream, f.bwd_name);
     return GMS_OK;
 }
 

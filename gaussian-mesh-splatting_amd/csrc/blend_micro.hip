@@ -17,9 +17,10 @@
 //                  ranks (list order = depth order).  The blocks are ordered by list length and dealt four to a wave.
 //   walks          a row's trip reads list[block][pos] -> record[entry] straight from LDS: no queue, no refill, no global access.
 //   micro_head / micro_fwd / micro_finalize / micro_bwd
-//                  the segment-parallel scheme of blend.hip unchanged -- first segments walked exactly, transmittance
-//                  products of the middle segments, exact walk of segments 1.. from the prefix product, partial sums in
-//                  order, backward restarted at segment boundaries.
+//                  the segment-parallel scheme of gms_segments.h (shared with blend.hip) -- first segments walked exactly,
+//                  transmittance products of the middle segments, exact walk of segments 1.. from the prefix product, partial
+//                  sums in order, backward restarted at segment boundaries.  This file adds the staging, the row walks, the
+//                  fixed-point table and flush, the kernel entry points and its BlendFamily table; blend.hip launches them.
 //   backward sums  go to an LDS table indexed by the splat's entry in the unit (64-bit fixed point since round 5, below) and
 //                  leave the block as ONE set of global atomics per (unit, entry): 5.3 M global float atomics per frame instead
 //                  of the 16.6 M a per-(block, splat) atomic would issue.
@@ -52,11 +53,13 @@
 
 #include "gms_common.h"
 #include "gms_blend.h"
+#include "gms_segments.h"
 
 namespace gms {
 
 struct MPix {
     int xi, yi, tid, b; bool inside; float xf, yf;
+    static __device__ __forceinline__ MPix of_tile(const BlendGrid &g, int tile);      // thread threadIdx.x of a 256-thread block per tile
 };
 
 // pixel `li` of 4x4 block `b` of a tile; index of the pixel in the per-(unit, pixel) segment state = b * 16 + li
@@ -81,63 +84,21 @@ __device__ __forceinline__ uint32_t max4rows(uint32_t v)          // v is row-un
 
 constexpr int LMAX = 256;          // micro mode: segment length <= 256 (entry index in a byte)
 
-// tile_dead[t] = 1 when the product of the first tloc_head(L) segment transmittances is < 1e-4 for every pixel
-__global__ void __launch_bounds__(BLOCK) micro_tloc_check_kernel(BlendGrid g)
+// (thread index = index in the segment state)
+__device__ __forceinline__ MPix MPix::of_tile(const BlendGrid &g, int tile)
 {
-    const int tile = blockIdx.x;
-    const int nseg = (int)(g.unit_first[tile + 1] - g.unit_first[tile]);
-    const int nhead = tloc_head(g.scan_out[3]);
-    if (nseg <= nhead + 1) return;                 // no phase-1 segment exists (the last one needs no product)
-    if ((uint64_t)g.tile_offset[tile + 1] > g.capacity) return;
-    const int tid = threadIdx.x;
-    const MPix p = micro_pixel(g, tile % g.gx, tile / g.gx, tid >> 4, tid & 15);
-    const float *st0 = g.seg_state + (size_t)g.mseg_first[tile] * SEG_FLOATS;
-    float T = 1.f;
-    for (int k = 0; k < nhead; k++) T *= st0[(size_t)k * SEG_FLOATS + SEG_TLOC * TILE_PIX + tid];
-    const int dead = __syncthreads_and(T < T_MIN || !p.inside);
-    if (tid == 0) g.tile_dead[tile] = dead ? 1u : 0u;
+    return micro_pixel(g, tile % g.gx, tile / g.gx, (int)(threadIdx.x >> 4), (int)(threadIdx.x & 15));
 }
 
-// ------------------------------------------------------------------------------------ finalize
+__global__ void __launch_bounds__(BLOCK) micro_tloc_check_kernel(BlendGrid g)
+{
+    tile_dead_check<MPix>(g);
+}
+
+// eight segments per step (four: 10.0 us; the deepest tile of the headline frame has 27)
 __global__ void __launch_bounds__(BLOCK) micro_finalize_kernel(BlendGrid g, BlendFwdOut o)
 {
-    const int tile = blockIdx.x;
-    const uint32_t first = g.unit_first[tile];
-    const int nseg = (int)(g.unit_first[tile + 1] - first);
-    if (nseg <= 1) return;
-    if ((uint64_t)g.tile_offset[tile + 1] > g.capacity) return;
-    const int tid = threadIdx.x;
-    const MPix p = micro_pixel(g, tile % g.gx, tile / g.gx, tid >> 4, tid & 15);
-    float *st0 = g.seg_state + (size_t)g.mseg_first[tile] * SEG_FLOATS;
-    float C0 = 0.f, C1 = 0.f, C2 = 0.f, Dp = 0.f, T = 1.f;
-    uint32_t last = 0;
-    constexpr int U = 8;          // eight segments per step, every load issued before the first use (four: 10.0 us; the deepest tile of the headline frame has 27)
-    for (int k0 = 0; k0 < nseg; k0 += U) {
-        float te[U], c0[U], c1[U], c2[U], dd[U], la[U];
-#pragma unroll
-        for (int j = 0; j < U; j++) {
-            const float *st = st0 + (size_t)min(k0 + j, nseg - 1) * SEG_FLOATS;
-            te[j] = st[SEG_TEND * TILE_PIX + tid]; c0[j] = st[SEG_C0 * TILE_PIX + tid]; c1[j] = st[SEG_C1 * TILE_PIX + tid];
-            c2[j] = st[SEG_C2 * TILE_PIX + tid]; dd[j] = st[SEG_D * TILE_PIX + tid]; la[j] = st[SEG_LAST * TILE_PIX + tid];
-        }
-#pragma unroll
-        for (int j = 0; j < U; j++) {
-            if (k0 + j < nseg && te[j] >= 0.f) {          // a segment entered dead (te < 0) contributed nothing
-                C0 += c0[j]; C1 += c1[j]; C2 += c2[j]; Dp += dd[j];
-                T = te[j];
-                last = max(last, __float_as_uint(la[j]));
-            }
-        }
-    }
-    if (p.inside) {
-        const size_t pid = (size_t)p.yi * g.W + p.xi, HW = (size_t)g.W * g.H;
-        o.final_T[pid] = T;
-        o.n_contrib[pid] = last;
-        o.out_color[pid] = C0 + T * o.bg[0];
-        o.out_color[HW + pid] = C1 + T * o.bg[1];
-        o.out_color[2 * HW + pid] = C2 + T * o.bg[2];
-        o.out_invdepth[pid] = Dp;
-    }
+    finalize_tile<8, MPix>(g, o);
 }
 
 // ------------------------------------------------------------------------------------ bwd
@@ -427,25 +388,7 @@ __device__ __forceinline__ void micro_fwd_unit(const BlendGrid &g, const BlendFw
     const uint8_t *lst = S.list[p.b];
     const uint32_t posbase = (uint32_t)u.seg * u.L;
 
-    float T = 1.f;
-    {
-        // prefix product of the segments in front, four independent loads per step (same left-to-right order)
-        const float *tl = g.seg_state + (size_t)u.slot0 * SEG_FLOATS + SEG_TLOC * TILE_PIX + p.tid;
-        int k = 0;
-        for (; k + 8 <= u.seg; k += 8) {          // (eight loads in flight; the product keeps its left-to-right order)
-            float t[8];
-#pragma unroll
-            for (int j = 0; j < 8; j++) t[j] = tl[(size_t)(k + j) * SEG_FLOATS];
-#pragma unroll
-            for (int j = 0; j < 8; j++) T = T * t[j];
-        }
-        for (; k + 4 <= u.seg; k += 4) {
-            const float t0 = tl[(size_t)k * SEG_FLOATS], t1 = tl[(size_t)(k + 1) * SEG_FLOATS];
-            const float t2 = tl[(size_t)(k + 2) * SEG_FLOATS], t3 = tl[(size_t)(k + 3) * SEG_FLOATS];
-            T = T * t0 * t1 * t2 * t3;
-        }
-        for (; k < u.seg; k++) T *= tl[(size_t)k * SEG_FLOATS];
-    }
+    float T = prefix_transmittance<8>(g, u, p.tid);          // (eight loads in flight, then four)
     const bool dead_on_entry = T < T_MIN;          // only possible for seg > 0
     float C0 = 0.f, C1 = 0.f, C2 = 0.f, Dp = 0.f;
     uint32_t last_rel = LAST_NONE;                                        // (index - count of the last entry composited: fwd_step_exec)
@@ -475,25 +418,8 @@ __device__ __forceinline__ void micro_fwd_unit(const BlendGrid &g, const BlendFw
     } while (__builtin_amdgcn_ballot_w64(rem > 0) != 0ull);
     const bool done = !p.inside || dead_on_entry || rem < REM_STOPPED / 2;      // (the plain form's `done`: outside, dead on entry or stopped)
     const uint32_t last = last_rel == LAST_NONE ? 0u : posbase + cnt + 1u + last_rel;
-    if (u.nseg == 1) {
-        if (p.inside) {
-            const size_t pid = (size_t)p.yi * g.W + p.xi, HW = (size_t)g.W * g.H;
-            o.final_T[pid] = T;
-            o.n_contrib[pid] = last;
-            o.out_color[pid] = C0 + T * o.bg[0];
-            o.out_color[HW + pid] = C1 + T * o.bg[1];
-            o.out_color[2 * HW + pid] = C2 + T * o.bg[2];
-            o.out_invdepth[pid] = Dp;
-        }
-    } else {
-        float *st = g.seg_state + (size_t)(u.slot0 + u.seg) * SEG_FLOATS;
-        st[SEG_C0 * TILE_PIX + p.tid] = C0; st[SEG_C1 * TILE_PIX + p.tid] = C1; st[SEG_C2 * TILE_PIX + p.tid] = C2;
-        st[SEG_D * TILE_PIX + p.tid] = Dp;
-        st[SEG_TEND * TILE_PIX + p.tid] = dead_on_entry ? -1.f : T;
-        st[SEG_LAST * TILE_PIX + p.tid] = __uint_as_float(last);
-        // the first segment's exact walk doubles as its transmittance product (see blend.hip)
-        if (u.seg == 0) st[SEG_TLOC * TILE_PIX + p.tid] = done ? 0.f : T;
-    }
+    if (u.nseg == 1) write_pixel(g, o, p, T, last, C0, C1, C2, Dp);
+    else store_partials(g, u, p.tid, T, last, C0, C1, C2, Dp, dead_on_entry, done);
 }
 
 template <int NE>
@@ -508,16 +434,7 @@ __global__ void __launch_bounds__(BLOCK) micro_head_kernel(BlendGrid g, BlendFwd
                                  : (u.nseg > 1 && u.seg != u.nseg - 1 && (phase < 0 || (u.seg < tloc_head(u.L)) == (phase == 0)));
     if (!walk) return;
     if (u.end == u.beg) {          // an empty tile (1 320 of the headline frame's 2 500): background, nothing to stage
-        const MPix p = micro_pixel(g, u.tx, u.ty, (int)(threadIdx.x >> 4), (int)(threadIdx.x & 15));
-        if (p.inside) {
-            const size_t pid = (size_t)p.yi * g.W + p.xi, HW = (size_t)g.W * g.H;
-            o.final_T[pid] = 1.f;
-            o.n_contrib[pid] = 0u;
-            o.out_color[pid] = 0.f + 1.f * o.bg[0];
-            o.out_color[HW + pid] = 0.f + 1.f * o.bg[1];
-            o.out_color[2 * HW + pid] = 0.f + 1.f * o.bg[2];
-            o.out_invdepth[pid] = 0.f;
-        }
+        write_pixel(g, o, micro_pixel(g, u.tx, u.ty, (int)(threadIdx.x >> 4), (int)(threadIdx.x & 15)), 1.f, 0u, 0.f, 0.f, 0.f, 0.f);
         return;
     }
     if (u.seg > 0 && phase == 1 && g.tile_dead[u.tile]) {          // products of a dead tile: nothing to walk, empty lists on record
@@ -603,7 +520,6 @@ __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdA
     if (!load_unit_at(g, u, blockIdx.x >> 3, blockIdx.x & 7u)) return;
     if (u.end <= u.beg) return;
     if (u.end - u.beg > (uint32_t)LMAX) return;             // (the host launches these kernels only on frames whose segment length fits)
-    const size_t HW = (size_t)g.W * g.H;
     for (int k = threadIdx.x; k < LMAX * NF; k += BLOCK) fxt[k] = 0ll;
     if (threadIdx.x < 5) tile_max[threadIdx.x] = 0u;
     const uint32_t my_id = unit_stage<false, INVD>(g, u, S, a.rec, nullptr);          // (its barriers also order the table clear)
@@ -611,15 +527,9 @@ __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdA
     const int q = (int)(((threadIdx.x >> 6) + (blockIdx.x >> 3)) & 3u);
     const int lane = threadIdx.x & 63, row = lane >> 4, li = lane & 15;
     const MPix p = micro_pixel(g, u.tx, u.ty, (int)S.order[4 * q + row], li);
-    const size_t pid = (size_t)p.yi * g.W + p.xi;
-    const float Tfinal = p.inside ? a.final_T[pid] : 0.f;
-    const uint32_t last = p.inside ? a.n_contrib[pid] : 0u;      // seg * L + index + 1 of the last splat this pixel applied
-    float dp0 = 0.f, dp1 = 0.f, dp2 = 0.f, dinvd = 0.f;
-    if (p.inside) {
-        dp0 = a.dL_dpix[pid]; dp1 = a.dL_dpix[HW + pid]; dp2 = a.dL_dpix[2 * HW + pid];
-        if (INVD) dinvd = a.dL_dinvd[pid];
-    }
-    const float Tfinal_bgdot = Tfinal * (a.bg[0] * dp0 + a.bg[1] * dp1 + a.bg[2] * dp2);
+    const BwdPixel bp = bwd_pixel<INVD>(g, a, p);
+    const uint32_t last = bp.last;                               // seg * L + index + 1 of the last splat this pixel applied
+    const float dp0 = bp.dp0, dp1 = bp.dp1, dp2 = bp.dp2, dinvd = bp.dinvd, Tfinal_bgdot = bp.Tfinal_bgdot;
     FxTile fx = {0, 0, 0, 0, 0};
     // the unit's bounds: largest sum_c |dL/dpixel_c| (the block's 256 lanes hold the tile's 256 pixels), |dL/dinvdepth|, and
     // centre-to-corner distances of its splats (entry threadIdx.x; the records behind the unit's end are zero)
@@ -659,37 +569,9 @@ __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdA
     ph.value(6, maxtop);
 
     if (maxtop > 0) {          // (wave-uniform; a wave with nothing to walk goes straight to the flush barrier)
-    BwdState st8 = {Tfinal, 0.f, 0.f, 0.f, 0.f};
-    if (u.nseg > 1) {
-        const float *st = g.seg_state + (size_t)(u.slot0 + u.seg) * SEG_FLOATS;
-        const float te = st[SEG_TEND * TILE_PIX + p.tid];
-        if (te > 0.f) {
-            // restart of the recurrence at the segment boundary: T after this segment's last applied splat and the colour
-            // composited behind it (sum of the live partials of the later segments) divided by that T
-            st8.T = te;
-            float S0 = 0.f, S1 = 0.f, S2 = 0.f, SD = 0.f;
-            bool stop = false;
-            constexpr int RU = 8;          // later segments per step, every load issued before the first use (4: a chain of up to seven rounds in the deepest tile)
-            for (int k0 = u.seg + 1; k0 < u.nseg; k0 += RU) {
-                float tk[RU], c0[RU], c1[RU], c2[RU], dd[RU];
-#pragma unroll
-                for (int j = 0; j < RU; j++) {
-                    const float *sk = g.seg_state + (size_t)(u.slot0 + min(k0 + j, u.nseg - 1)) * SEG_FLOATS;
-                    tk[j] = sk[SEG_TEND * TILE_PIX + p.tid]; c0[j] = sk[SEG_C0 * TILE_PIX + p.tid];
-                    c1[j] = sk[SEG_C1 * TILE_PIX + p.tid]; c2[j] = sk[SEG_C2 * TILE_PIX + p.tid];
-                    dd[j] = INVD ? sk[SEG_D * TILE_PIX + p.tid] : 0.f;
-                }
-#pragma unroll
-                for (int j = 0; j < RU; j++) {
-                    if (k0 + j >= u.nseg || tk[j] < 0.f) stop = true;
-                    if (!stop) { S0 += c0[j]; S1 += c1[j]; S2 += c2[j]; SD += dd[j]; }
-                }
-                if (__all(stop)) break;
-            }
-            const float inv = FAULT == 2 ? 0.f : 1.f / te;
-            st8.acc0 = S0 * inv; st8.acc1 = S1 * inv; st8.acc2 = S2 * inv; st8.accd = SD * inv;
-        }
-    }
+    // eight later segments per step (4: a chain of up to seven rounds in the deepest tile)
+    BwdState st8 = {bp.Tfinal, 0.f, 0.f, 0.f, 0.f};
+    bwd_restart<INVD, FAULT, 8>(g, u, p.tid, st8);
     ph.mark(2);
 
     // lane -> field of the 64-byte gradient record (the layout row_reduce10 leaves)
@@ -793,47 +675,15 @@ __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdA
 }
 
 // ------------------------------------------------------------------------------------ host
-int32_t launch_micro_forward(const BlendGrid &g_in, const BlendFwdOut &o, uint32_t max_units, bool debug, hipStream_t stream)
+// (the launch sequences are blend.hip's: launch_compositing_forward / _backward)
+const BlendFamily &micro_family()
 {
-    BlendGrid g = g_in;
-    experiment_switches(g, 2048u | 4096u, stream);          // (make EXPERIMENTS=1 only: per-wave stamps of micro_head / micro_fwd)
-    static int deep_env = -2;
-    if (deep_env == -2) { const char *e = getenv("GMS_DEEP"); deep_env = e ? atoi(e) : -1; }
-    const bool deep = deep_env >= 0 ? deep_env != 0 : g.capacity > 512ull * (uint64_t)g.T;
-    const unsigned blocks = blend_grid_units(max_units);
-    auto head = micro_head_kernel<4>;          // (4 entries per trip; 2 was -2 % it/s: docs/HISTORY.md)
-    if (deep) {     // deep scene: head segments, tile-dead check, then the tail segments of the tiles still alive
-        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<blocks, BLOCK, 0, stream>>>(g, o, 0));
-        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, micro_tloc_check_kernel<<<(unsigned)g.T, BLOCK, 0, stream>>>(g));
-        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<blocks, BLOCK, 0, stream>>>(g, o, 1));
-    } else {
-        GMS_LAUNCH(GMS_K_BLEND_HEAD, stream, head<<<blocks, BLOCK, 0, stream>>>(g, o, -1));
-    }
-    GMS_KERNEL_CHECK(debug, stream, "micro_head");
-    GMS_LAUNCH(GMS_K_BLEND_FWD, stream, micro_fwd_kernel<4><<<blocks, BLOCK, 0, stream>>>(g, o));
-    GMS_KERNEL_CHECK(debug, stream, "micro_fwd");
-    GMS_LAUNCH(GMS_K_BLEND_FINALIZE, stream, micro_finalize_kernel<<<(unsigned)g.T, BLOCK, 0, stream>>>(g, o));
-    GMS_KERNEL_CHECK(debug, stream, "micro_finalize");
-    return GMS_OK;
-}
-
-int32_t launch_micro_backward(const BlendGrid &g_in, const BlendBwdArgs &a, uint32_t max_units, bool debug, hipStream_t stream)
-{
-    BlendGrid g = g_in;
-    experiment_switches(g, 1024u, stream);          // (make EXPERIMENTS=1 only: GMS_DBG & 1024 = per-wave phase stamps)
-    const unsigned blocks = blend_grid_units(max_units);
-    const bool invd = a.has_invd && a.dL_dinvd;
-    if (a.part) {                           // deterministic mode (gmsplat.h): per-instance partial records
-        if (invd) GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (micro_bwd_kernel<true, 2, 0, true><<<blocks, BLOCK, 0, stream>>>(g, a)));
-        else GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (micro_bwd_kernel<false, 2, 0, true><<<blocks, BLOCK, 0, stream>>>(g, a)));
-    } else if (fault_mode() == 2 && !invd) {       // negative control (gms_set_fault): its own instantiation
-        GMS_LAUNCH(GMS_K_BLEND_BWD, stream, (micro_bwd_kernel<false, 2, 2><<<blocks, BLOCK, 0, stream>>>(g, a)));
-    } else {
-        auto kern = invd ? micro_bwd_kernel<true, 2, 0> : micro_bwd_kernel<false, 2, 0>;          // (2 entries per trip)
-        GMS_LAUNCH(GMS_K_BLEND_BWD, stream, kern<<<blocks, BLOCK, 0, stream>>>(g, a));
-    }
-    GMS_KERNEL_CHECK(debug, stream, "micro_bwd");
-    return GMS_OK;
+    static const BlendFamily f = {
+        micro_head_kernel<4>, micro_tloc_check_kernel, micro_fwd_kernel<4>, micro_finalize_kernel,          // (4 entries per trip; 2 was -2 % it/s: docs/HISTORY.md)
+        {{micro_bwd_kernel<false, 2, 0>, micro_bwd_kernel<false, 2, 0, true>, micro_bwd_kernel<false, 2, 2>},      // (2 entries per trip)
+         {micro_bwd_kernel<true, 2, 0>, micro_bwd_kernel<true, 2, 0, true>, micro_bwd_kernel<true, 2, 0>}},     // (fault 2 has no inverse-depth form)
+        1u, BLOCK, 2048u | 4096u, 1024u, 1u, "micro_head", "micro_fwd", "micro_finalize", "micro_bwd"};      // (GMS_DBG: per-wave phase stamps)
+    return f;
 }
 
 }  // namespace gms

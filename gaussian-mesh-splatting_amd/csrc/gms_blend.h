@@ -1,4 +1,5 @@
-// gms_blend.h -- work-unit (tile, segment) bookkeeping shared by the binning and blend stages.
+// gms_blend.h -- work-unit (tile, segment) bookkeeping shared by the binning and blend stages, and the compositing stage's interface to
+// the drivers (make_blend_grid, launch_compositing_*).  The segment scheme the two kernel families share is gms_segments.h.
 #pragma once
 #include "gms_common.h"
 
@@ -70,8 +71,19 @@ bool use_micro(uint64_t capacity, int T);           // ... and is, for a frame w
 uint32_t seg_len_forced();     // GMS_SEG_LEN, or 0
 uint32_t seg_len_min();        // the forced L, or SEG_LEN_SHALLOW: what BinningState is sized and carved with
 uint32_t unit_run();
-inline uint32_t max_units(uint32_t T, uint64_t instances, uint32_t L) { return T + (uint32_t)(instances / L) + 1u; }
-inline uint32_t max_slots(uint64_t instances, uint32_t L) { return 2u * (uint32_t)(instances / L) + 2u; }
+
+// The grid of a frame as the compositing launches see it, forward and backward: the image's tile tables and a binning buffer of
+// `capacity` instances carved with segment length L (the frame's own L is in scan_out[3]).  dbg / dbg_buf: experiment_switches.
+inline BlendGrid make_blend_grid(int W, int H, const ImageState &img, const BinningState &bin, uint64_t capacity, uint32_t L)
+{
+    BlendGrid g;
+    g.W = W; g.H = H; g.gx = (W + TILE - 1) / TILE; g.gy = (H + TILE - 1) / TILE; g.T = g.gx * g.gy;
+    g.scan_out = img.scan_out; g.tile_offset = img.tile_offset; g.unit_first = img.unit_first; g.mseg_first = img.mseg_first;
+    g.unit_tile = bin.unit_tile; g.keys = bin.keys; g.seg_state = bin.seg_state; g.tile_dead = img.tile_dead; g.tile_cmax = img.tile_cmax;
+    g.capacity = capacity; g.max_units = (uint32_t)BinningState::n_units((size_t)capacity, (size_t)g.T, L);
+    g.dbg = 0; g.unit_run = unit_run(); g.dbg_buf = nullptr; g.mmask = bin.mmask;
+    return g;
+}
 
 // ---- device-side helpers shared by the blend kernel files -------------------------------------------------------
 #ifndef GMS_MICRO_DEFAULT
@@ -418,9 +430,15 @@ struct Stamp {
 inline uint32_t blend_grid_units(uint32_t max_units) { return 8u * UNIT_RUN_MAX * ((max_units + 8u * UNIT_RUN_MAX - 1u) / (8u * UNIT_RUN_MAX)); }
 
 void experiment_switches(BlendGrid &g, uint32_t buf_bits, hipStream_t stream);     // blend.hip; a no-op outside make EXPERIMENTS=1
-int32_t launch_blend_forward(const BlendGrid &g, const BlendFwdOut &o, uint32_t max_units, bool debug, hipStream_t stream);
-int32_t launch_blend_backward(const BlendGrid &g, const BlendBwdArgs &a, uint32_t max_units, bool debug, hipStream_t stream);
-int32_t launch_micro_forward(const BlendGrid &g, const BlendFwdOut &o, uint32_t max_units, bool debug, hipStream_t stream);
-int32_t launch_micro_backward(const BlendGrid &g, const BlendBwdArgs &a, uint32_t max_units, bool debug, hipStream_t stream);
+// The compositing launches of a frame (blend.hip): the one place that knows there are two kernel families and picks one
+// (use_micro).  `max_units` sizes the launch.  frame_L: the segment length handed to the tile scan (0: the scan chooses);
+// the micro-tile kernels are refused on a frame whose L they cannot index.  *used_micro: which family took the frame.
+int32_t launch_compositing_forward(const BlendGrid &g, const BlendFwdOut &o, uint32_t frame_L, uint32_t max_units, bool debug, hipStream_t stream,
+                                   bool *used_micro);
+int32_t launch_compositing_backward(const BlendGrid &g, const BlendBwdArgs &a, uint32_t max_units, bool debug, hipStream_t stream);
+// deterministic mode: partial records per instance that launch_compositing_backward's kernels write into a.part for this frame.
+// 1: one per instance, every instance written; 4: one per (instance, quadrant), only the pairs that survive the culls (the
+// caller zero-fills).
+uint32_t compositing_det_nsub(const BlendGrid &g);
 
 }  // namespace gms

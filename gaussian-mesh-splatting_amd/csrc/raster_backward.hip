@@ -514,34 +514,29 @@ extern "C" int32_t gms_rasterize_backward(const GmsRasterBackwardArgs *A, void *
     BinningState bin = BinningState::carve(const_cast<void *>(A->binning_buffer), (size_t)cap, (size_t)T, L);
 
     if (A->num_rendered > 0) {
-        BlendGrid g;
-        g.W = W; g.H = H; g.gx = gx; g.gy = gy; g.T = T; g.scan_out = img.scan_out; g.tile_offset = img.tile_offset;
-        g.unit_first = img.unit_first; g.mseg_first = img.mseg_first; g.unit_tile = bin.unit_tile; g.keys = bin.keys;
-        g.seg_state = bin.seg_state; g.capacity = cap;
-        g.max_units = (uint32_t)BinningState::n_units((size_t)cap, (size_t)T, L); g.dbg = 0; g.unit_run = unit_run(); g.dbg_buf = nullptr; g.tile_dead = img.tile_dead; g.tile_cmax = img.tile_cmax;
-        g.mmask = bin.mmask;
+        const BlendGrid g = make_blend_grid(W, H, img, bin, cap, L);
         BlendBwdArgs b;
         b.rec = geom.rec; b.bg = A->background; b.final_T = img.final_T; b.n_contrib = img.n_contrib;
         b.dL_dpix = A->dL_dout_color; b.dL_dinvd = A->dL_dout_invdepth; b.accum = A->grad_accum;
         b.has_invd = A->dL_dout_invdepth != nullptr;
         b.part = nullptr;
-        uint32_t mu = (uint32_t)BinningState::n_units((size_t)cap, (size_t)T, L);
+        uint32_t mu = g.max_units;
         if (A->num_units > 0 && (uint64_t)A->num_units < mu) mu = (uint32_t)A->num_units;      // exact count from the forward
-        const bool micro = use_micro(cap, T);
         const bool det = det_mode() != 0 && fault_mode() == 0;
+        const size_t nsub = compositing_det_nsub(g);      // which compositing family takes the frame: 1 micro-tile, 4 quadrant waves
         if (det) {      // deterministic mode (gmsplat.h): partial records per instance, then an ordered reduction per Gaussian
-            const size_t nsub = micro ? 1 : 4, bytes = (size_t)A->num_rendered * nsub * GRAD_STRIDE * sizeof(float);
+            const size_t bytes = (size_t)A->num_rendered * nsub * GRAD_STRIDE * sizeof(float);
             b.part = static_cast<float *>(det_scratch(0, bytes, stream));
             if (!b.part) { set_error("deterministic mode: scratch allocation of %zu bytes failed", bytes); return GMS_ERR_ALLOC; }
             // the quadrant kernels store only the (instance, quadrant) pairs that survive their culls; the micro-tile flush writes
             // every instance (zeros included) and needs no clearing
-            if (!micro) GMS_HIP_CHECK(hipMemsetAsync(b.part, 0, bytes, stream));
+            if (nsub > 1) GMS_HIP_CHECK(hipMemsetAsync(b.part, 0, bytes, stream));
         }
-        int32_t rc = micro ? launch_micro_backward(g, b, mu, A->debug != 0, stream) : launch_blend_backward(g, b, mu, A->debug != 0, stream);
+        const int32_t rc = launch_compositing_backward(g, b, mu, A->debug != 0, stream);
         if (rc != GMS_OK) return rc;
         if (det) {
             const unsigned rblocks = (unsigned)(((size_t)P * 16 + BLOCK - 1) / BLOCK);
-            if (micro) det_reduce_kernel<1><<<rblocks, BLOCK, 0, stream>>>(P, gx, gy, A->radii, geom.rec, geom.depth, img.tile_offset, bin.keys, cap, b.part, A->grad_accum);
+            if (nsub == 1) det_reduce_kernel<1><<<rblocks, BLOCK, 0, stream>>>(P, gx, gy, A->radii, geom.rec, geom.depth, img.tile_offset, bin.keys, cap, b.part, A->grad_accum);
             else det_reduce_kernel<4><<<rblocks, BLOCK, 0, stream>>>(P, gx, gy, A->radii, geom.rec, geom.depth, img.tile_offset, bin.keys, cap, b.part, A->grad_accum);
             GMS_KERNEL_CHECK(A->debug, stream, "det_reduce");
         }

@@ -5,7 +5,7 @@
 //   K2  tile_scan        binning.hip: launch_tile_scan, or inside the emit launch (inline scan)
 //   K3  emit_instances   binning.hip: launch_emit_sort
 //   K4  tile_sort        binning.hip: launch_emit_sort
-//   K5/K6 compositing    blend.hip (segment-parallel: head / fwd / finalize), blend_micro.hip (gms_blend.h).
+//   K5/K6 compositing    launch_compositing_forward (gms_blend.h): blend.hip or blend_micro.hip on the scheme of gms_segments.h
 //
 // Library state: everything that outlives a call (tile counters, launch-size hints) is keyed by
 // (device, stream[, W, H, P]); see ThreadState below.
@@ -408,22 +408,11 @@ struct ForwardTail {
         const int32_t rc = launch_emit_sort(f, bin, capacity, mu, inl, fill_np, sort_np, &presort_enqueued, debug, stream);
         if (inl && presort_enqueued) ctr->dirty = false;          // the counters are clean again once that launch has run
         if (rc != GMS_OK) return rc;
-        const ImageState &img = f.img;
-        BlendGrid g;
-        g.W = W; g.H = H; g.gx = f.gx; g.gy = f.gy; g.T = T; g.scan_out = img.scan_out; g.tile_offset = img.tile_offset;
-        g.unit_first = img.unit_first; g.mseg_first = img.mseg_first; g.unit_tile = bin.unit_tile; g.keys = bin.keys;
-        g.seg_state = bin.seg_state; g.capacity = capacity; g.max_units = mu; g.dbg = 0; g.unit_run = unit_run(); g.dbg_buf = nullptr; g.tile_dead = img.tile_dead; g.tile_cmax = img.tile_cmax;
-        g.mmask = bin.mmask;
-        t_state.last_used_micro = use_micro(capacity, T) ? 1 : 0;
-        if (use_micro(capacity, T)) {
-            // the micro-tile kernels index a unit's entries with one byte: never launch them on a frame whose L they cannot hold
-            if (f.frame_L == 0 || f.frame_L > SEG_LEN_MICRO) {
-                set_error("internal: micro-tile compositing chosen for a frame with segment length %u", f.frame_L);
-                return GMS_ERR_INVALID_ARGUMENT;
-            }
-            return launch_micro_forward(g, bo, mu_launch, debug, stream);
-        }
-        return launch_blend_forward(g, bo, mu_launch, debug, stream);
+        const BlendGrid g = make_blend_grid(W, H, f.img, bin, capacity, L);
+        bool used_micro = false;
+        const int32_t brc = launch_compositing_forward(g, bo, f.frame_L, mu_launch, debug, stream, &used_micro);
+        t_state.last_used_micro = used_micro ? 1 : 0;
+        return brc;
     }
 };
 

@@ -346,6 +346,26 @@ def test_deep_tiles_take_the_merge_path_sort_from_the_second_frame(P):
         assert rep["radii_unexplained"] == 0 and rep["max_clean"] <= RGB_TOL and rep["max_amb"] <= 0.02, (frame, rep)
 
 
+def _check_in_child(env, P, W, H):
+    """`_check` of the seed-21 scene (P splats, W x H image) in a fresh child process under `env`: the knobs are read once per process."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = (
+        "import sys, os, torch\n"
+        "sys.path.insert(0, os.path.join(%r, 'tests'))\n"
+        "import conftest\n"
+        "import test_gpu_raster as T\n"
+        "from games_hip import synthetic as syn\n"
+        "import _util as U\n"
+        "sc, cam = syn.random_scene(%d, seed=21, scale_lo=0.01, scale_hi=0.15), syn.orbit_camera(2, width=%d, height=%d, radius=2.5)\n"
+        "T._check(T._inputs(sc), U.settings_kwargs(cam, torch.tensor([0.3, 0.1, 0.2])), %d, %d)\n"
+        "print('knob ok')\n" % (root, P, W, H, W, H))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0 and "knob ok" in r.stdout, (env, r.stdout[-2000:], r.stderr[-3000:])
+
+
 # (None: a slot whose setting selected a retired kernel variant; the slots keep every other setting's test id `env<position>`)
 @pytest.mark.parametrize("env", [pytest.param(e, id=f"env{i}") for i, e in enumerate([
     {"GMS_INLINE_SCAN": "0"},
@@ -362,23 +382,32 @@ def test_tuning_knobs_do_not_change_results(env):
     """The knobs of INTEGRATION.md section 6 are read once per process: run the parity check in a child process per
     setting (both compositing implementations; segment lengths other than the default, forced two-phase products, no XCD
     run interleave, synchronous binning)."""
-    import os
-    import subprocess
-    import sys
-    code = (
-        "import sys, os, torch\n"
-        "sys.path.insert(0, os.path.join(%r, 'tests'))\n"
-        "import conftest\n"
-        "import test_gpu_raster as T\n"
-        "from games_hip import synthetic as syn\n"
-        "import _util as U\n"
-        "sc, cam = syn.random_scene(6000, seed=21, scale_lo=0.01, scale_hi=0.15), syn.orbit_camera(2, width=144, height=112, radius=2.5)\n"
-        "T._check(T._inputs(sc), U.settings_kwargs(cam, torch.tensor([0.3, 0.1, 0.2])), 144, 112)\n"
-        "print('knob ok')\n" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    e = dict(os.environ, **env)
-    r = subprocess.run([sys.executable, "-c", code], env=e, capture_output=True, text=True, timeout=600,
-                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    assert r.returncode == 0 and "knob ok" in r.stdout, (env, r.stdout[-2000:], r.stderr[-3000:])
+    _check_in_child(env, 6000, 144, 112)
+
+
+@pytest.fixture(scope="module")
+def edge_tile_lists():
+    """List lengths per tile (9 x 5 tiles, row-major) of the 131 x 77 frame below, from the CPU oracle alone."""
+    sc, cam = syn.random_scene(12000, seed=21, scale_lo=0.01, scale_hi=0.15), syn.orbit_camera(2, width=131, height=77, radius=2.5)
+    rng = U.oracle_render(_inputs(sc), U.settings_kwargs(cam, torch.tensor([0.3, 0.1, 0.2])))["details"]["ranges"]
+    return (rng[:, 1] - rng[:, 0]).astype(np.int64)
+
+
+@pytest.mark.parametrize("env", [{"GMS_SEG_LEN": "64", "GMS_DEEP": "1"}, {"GMS_MICRO": "0", "GMS_SEG_LEN": "64", "GMS_DEEP": "1"}],
+                         ids=["micro", "quadrant"])
+def test_segment_scheme_on_tiles_cut_by_the_image_edges(env, edge_tile_lists):
+    """131 x 77 pixels: the right column of tiles holds 3 of 16 pixel columns and the bottom row 13 of 16 pixel rows, so the
+    lanes outside the image run the dead-tile check, the finalize pass and the backward's restart together with many
+    64-entry segments and the two-phase products, in both kernel families.  What must hold for that is asserted from the
+    oracle's lists before any GPU call."""
+    n = edge_tile_lists
+    assert n.shape == (45,) and n.min() >= 65                           # 9 x 5 tiles, every one multi-segment
+    bottom, right = n[36:45], n[8::9]
+    # more than tloc_head(64) + 1 = 17 segments: the dead-tile check does not return early
+    assert (bottom > 17 * 64).sum() >= 4, bottom
+    # 10 .. 17 segments: the restart and the finalize pass cross both step widths (4 and 8)
+    assert ((right >= 9 * 64) & (right <= 17 * 64)).all(), right
+    _check_in_child(env, 12000, 131, 77)
 
 
 @pytest.mark.parametrize("env", [{}, {"GMS_MICRO": "1"}, {"GMS_MICRO": "0"}, {"GMS_MICRO": "1", "GMS_SEG_LEN": "128"}])
