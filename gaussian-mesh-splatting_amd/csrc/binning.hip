@@ -6,10 +6,10 @@
 //   K3  emit_instances   one 64-bit key (depth bits << 32 | id) per (Gaussian, tile): per-block LDS tile table, ONE
 //                        cursor atomic per distinct tile per block; spare blocks write the (tile, segment) unit records
 //                        (heaviest first) and the sort's run tables.
-//   K4  tile_sort        presort of 1024-key runs (one block per run, wave-local bitonic sub-stages), then merge-path
-//                        levels in LDS per multi-run tile (<= 8192 keys) or multi-block merge-path passes for deeper
-//                        tiles.  Total order on (depth, id): independent of the emission order == the reference's
-//                        stable radix sort.
+//   K4  tile_sort        presort of 1024-key runs (one block per run, wave-local bitonic sub-stages), then a merge by
+//                        rank, one work item per run, for multi-run tiles of <= 8192 keys, or multi-block merge-path
+//                        passes for deeper tiles.  Total order on (depth, id): independent of the emission order == the
+//                        reference's stable radix sort.
 #include "gms_blend.h"
 #include "gms_common.h"
 #include "gms_forward.h"
@@ -490,9 +490,12 @@ __device__ void lds_bitonic(uint64_t *s, int m, int k0, int j0, bool first_mirro
 //      each pass is a streaming read + write of the keys that still need merging.  Data ping-pongs between `keys` and a scratch buffer (the segment-state area, unused until
 //      compositing); the presort writes a tile's runs to the side that makes its LAST pass land in `keys`.  The host
 //      launches as many passes as the deepest tile of the PREVIOUS frame needs (the count travels back with N);
-//  (3) merge: 1024 threads per tile with 2..8 runs: loads the tile (<= SORT_BIG_CHUNK keys) into LDS and runs only the
-//      bitonic merge levels above SORT_RUN.  A tile deeper than the launched passes cover (scene changed since the last
-//      frame) is sorted from scratch here by one block: slow, but correct, and the next frame launches enough passes.
+//  (3) merge: tiles with 2..8 runs that no merge-path pass covers.  One work item per RUN, a 1024-thread block each: it
+//      loads the tile (<= SORT_BIG_CHUNK keys) into LDS and places each key of its run by rank (tile_merge_kernel), reading
+//      the runs in the scratch buffer, where the presort put them, and writing `keys`.  When the scratch is too small the runs stay in
+//      `keys` and one block per tile merges them level by level in LDS.  A tile deeper than the launched passes cover
+//      (scene changed since the last frame) is sorted from scratch here by one block: slow, but correct, and the next frame
+//      launches enough passes.
 
 enum { SORT_SINGLE = 0, SORT_LDS, SORT_MERGEPATH, SORT_FALLBACK };
 
@@ -590,7 +593,7 @@ __device__ __forceinline__ void sort_level(uint64_t (&k)[4], int t, uint64_t *ld
 
 __global__ void __launch_bounds__(256) tile_presort_reg_kernel(const uint32_t *tile_offset, const uint32_t *run_total, const uint2 *run_tab,
                                                            uint32_t max_runs, uint64_t *keys, uint64_t *tmp, uint64_t capacity,
-                                                           int passes_launched, uint32_t *zero_count, int T)
+                                                           int passes_launched, bool by_rank, uint32_t *zero_count, int T)
 {
     __shared__ uint64_t s[SORT_RUN];
     const int tid = threadIdx.x;
@@ -605,7 +608,9 @@ __global__ void __launch_bounds__(256) tile_presort_reg_kernel(const uint32_t *t
     int q;
     const int cls = sort_class((uint64_t)n, passes_launched, q);
     if (cls == SORT_FALLBACK) return;
-    uint64_t *dst_base = (cls == SORT_MERGEPATH && (q & 1)) ? tmp : keys;
+    // the launch that merges the runs reads them on one side and writes the other: an odd number of merge-path passes, or the
+    // one rank-merge of a SORT_LDS tile, ends in `keys` when the runs start in the scratch
+    uint64_t *dst_base = ((cls == SORT_MERGEPATH && (q & 1)) || (cls == SORT_LDS && by_rank)) ? tmp : keys;
     const long c0 = (long)tr.y * SORT_RUN;
     const int cn = (int)min((long)SORT_RUN, n - c0);
     const uint64_t *g = keys + beg + c0;
@@ -613,6 +618,8 @@ __global__ void __launch_bounds__(256) tile_presort_reg_kernel(const uint32_t *t
     if (cn <= 1) { if (cn == 1 && tid == 0) d[0] = g[0]; return; }
     int m = 2;
     while (m < cn) m <<= 1;
+    // (waves whose 256-key slice holds only padding run the network like the others: letting them skip it -- return at once when
+    //  m <= 256, meet only the barriers when m = 512 -- was measured and makes this launch 0.8 us LONGER: docs/HISTORY.md)
     uint64_t k[4];
 #pragma unroll
     for (int r = 0; r < 4; r++) k[r] = 4 * tid + r < cn ? g[4 * tid + r] : ~0ull;      // virtual +inf padding
@@ -711,26 +718,83 @@ __global__ void __launch_bounds__(256) tile_mergepath_kernel(const uint32_t *til
     }
 }
 
-__global__ void __launch_bounds__(1024) tile_merge_kernel(const uint32_t *tile_offset, const uint32_t *multi_total, const uint32_t *multi_tab,
-                                                          uint32_t max_multi, uint64_t *keys, uint64_t capacity, int passes_launched)
+// Number of keys smaller than `key` in the R - 1 sorted runs of the tile other than `run`.  The runs lie in LDS at SORT_RUN-key
+// strides, the last one padded with +inf to full length, so every search is the same eleven probes (ten halvings and the last
+// compare) and the R - 1 of them are independent: each round is R - 1 LDS reads in flight, not one.  Strict `<` on the whole
+// 64-bit key: the keys of a tile are unique (the Gaussian id is the low word).
+template <int R>
+__device__ __forceinline__ int rank_in_other_runs(const uint64_t *s, int run, uint64_t key)
+{
+    const uint64_t *a[R - 1];
+    int p[R - 1];
+#pragma unroll
+    for (int o = 0; o < R - 1; o++) { a[o] = s + (o < run ? o : o + 1) * SORT_RUN; p[o] = 0; }
+#pragma unroll
+    for (int step = SORT_RUN / 2; step >= 1; step >>= 1) {
+#pragma unroll
+        for (int o = 0; o < R - 1; o++) p[o] += a[o][p[o] + step - 1] < key ? step : 0;
+    }
+    int below = 0;
+#pragma unroll
+    for (int o = 0; o < R - 1; o++) below += p[o] + (a[o][p[o]] < key ? 1 : 0);
+    return below;
+}
+
+// The launch behind the presort (and behind the merge-path passes, when some are launched).  A work item is (multi-run tile, run
+// 0 .. 7), done by one 1024-thread block with SORT_BIG_CHUNK keys of LDS:
+//   SORT_LDS tile, by_rank: the presort left its runs in the scratch.  The item of run j loads the whole tile into LDS and every
+//     thread takes one key of run j to its final place in `keys`: its index in the run plus the number of smaller keys in every
+//     other run.  That place is the key's rank in the tile's total order, so the items of a tile write disjoint entries, read only
+//     what the previous launch wrote, and need nothing from each other.
+//   SORT_LDS tile, !by_rank (the segment-state area is too small to be the scratch): the item of run 0 merges level by level
+//     inside LDS, in place.
+//   SORT_FALLBACK tile: the item of run 0 sorts from scratch.   SORT_MERGEPATH tile: nothing left to do.
+// An overflowed launch has no item with work: the host discards its results.
+__device__ __forceinline__ bool merge_item_has_work(const uint32_t *tile_offset, uint32_t tile, int run, uint64_t capacity, int passes_launched,
+                                                    bool by_rank)
+{
+    const uint64_t beg = tile_offset[tile], end64 = tile_offset[tile + 1];
+    if (end64 > capacity) return false;
+    int q;
+    const int cls = sort_class(end64 - beg, passes_launched, q);
+    if (cls == SORT_LDS && by_rank) return (uint64_t)run * SORT_RUN < end64 - beg;
+    return (cls == SORT_LDS || cls == SORT_FALLBACK) && run == 0;
+}
+
+// the n keys of a tile, sorted runs of SORT_RUN at `src`: the keys of run `run` go to their ranks in `g`
+__device__ __forceinline__ void merge_run_by_rank(uint64_t *s, const uint64_t *src, uint64_t *g, int n, int run)
+{
+    const int tid = threadIdx.x;
+    const int R = (n + SORT_RUN - 1) / SORT_RUN;      // 2 .. 8
+    for (int i = tid; i < R * SORT_RUN; i += 1024) s[i] = i < n ? src[i] : ~0ull;
+    __syncthreads();
+    const int own = run * SORT_RUN + tid;
+    if (own >= n) return;
+    const uint64_t key = s[own];
+    int below = 0;
+    switch (R) {
+    case 2: below = rank_in_other_runs<2>(s, run, key); break;
+    case 3: below = rank_in_other_runs<3>(s, run, key); break;
+    case 4: below = rank_in_other_runs<4>(s, run, key); break;
+    case 5: below = rank_in_other_runs<5>(s, run, key); break;
+    case 6: below = rank_in_other_runs<6>(s, run, key); break;
+    case 7: below = rank_in_other_runs<7>(s, run, key); break;
+    default: below = rank_in_other_runs<8>(s, run, key); break;
+    }
+    g[tid + below] = key;
+}
+
+// the two one-block routes, in place in g[0, n): the level-by-level merge of sorted runs inside LDS (n <= CHUNK), or the sort from
+// scratch.  (Its registers, not the rank merge's, are what tile_merge_kernel is allocated: 69 against 49.)
+__device__ __forceinline__ void merge_tile_one_block(uint64_t *s, uint64_t *g, long n, bool runs_in_lds)
 {
     constexpr int THREADS = 1024, CHUNK = SORT_BIG_CHUNK;
-    __shared__ uint64_t s[CHUNK];
     const int tid = threadIdx.x;
-    if (blockIdx.x >= multi_total[0] || blockIdx.x >= max_multi) return;     // one block per tile with more than one run
-    const uint32_t tile = multi_tab[blockIdx.x];
-    const uint64_t beg = tile_offset[tile], end64 = tile_offset[tile + 1];
-    if (end64 > capacity) return;
-    const long n = (long)(end64 - beg);
-    int q;
-    const int cls = sort_class((uint64_t)n, passes_launched, q);
-    if (cls == SORT_SINGLE || cls == SORT_MERGEPATH) return;
-    uint64_t *g = keys + beg;
+    const uint64_t INF = ~0ull;
     long np2 = 2;
     while (np2 < n) np2 <<= 1;
-    const uint64_t INF = ~0ull;
 
-    if (cls == SORT_LDS) {
+    if (runs_in_lds) {
         // The runs of SORT_RUN keys are sorted: merge them level by level inside LDS with merge path -- every thread
         // finds the co-rank of its K consecutive outputs by binary search, merges them into registers, and the level
         // is written back after a barrier (no second buffer).  ~30 dependent LDS reads per level instead of the
@@ -796,6 +860,56 @@ __global__ void __launch_bounds__(1024) tile_merge_kernel(const uint32_t *tile_o
     }
 }
 
+// (called for items with work only)
+__device__ __forceinline__ void merge_tile_run(uint64_t *s, const uint32_t *tile_offset, uint32_t tile, int run, uint64_t *keys,
+                                               const uint64_t *tmp, int passes_launched, bool by_rank)
+{
+    const uint64_t beg = tile_offset[tile];
+    const long n = (long)(tile_offset[tile + 1] - beg);
+    int q;
+    const int cls = sort_class((uint64_t)n, passes_launched, q);
+    if (cls == SORT_LDS && by_rank) merge_run_by_rank(s, tmp + beg, keys + beg, (int)n, run);
+    else merge_tile_one_block(s, keys + beg, n, cls == SORT_LDS);
+}
+
+// The items are (entry of the multi-run tile table, run 0 .. 7); how many entries there are is known on the device only.  A grid of
+// one block per possible item (capacity / 1024 entries x 8) is thousands of blocks that find nothing to do, and with 64 KB of LDS
+// each at most two are resident per CU: measured, that grid alone takes 15 us on the headline frame.  So the launch is at most
+// MERGE_BLOCKS blocks -- one per CU, all resident at once (the kernel's 69 registers admit one 16-wave block per CU) -- and block b
+// takes items b, b + gridDim.x, ...: a static assignment, no block looks at another.  Most items have nothing to do (a two-run tile
+// has six of them) and finding that out is two dependent loads, so a block looks at all of its items at once, one per thread, keeps
+// the ones with work in LDS and then goes through those.  Items are numbered run-major, so the items of one deep tile land on
+// different blocks.  (512 blocks at one per CU measure the same; two per CU would need <= 64 registers, which this compiler only
+// reaches by spilling scalar registers: docs/HISTORY.md.)
+constexpr int MERGE_BLOCKS = 256;
+
+__global__ void __launch_bounds__(1024) tile_merge_kernel(const uint32_t *tile_offset, const uint32_t *multi_total, const uint32_t *multi_tab,
+                                                          uint32_t max_multi, uint64_t *keys, const uint64_t *tmp, uint64_t capacity,
+                                                          int passes_launched, bool by_rank)
+{
+    constexpr int THREADS = 1024;
+    __shared__ uint64_t s[SORT_BIG_CHUNK];
+    __shared__ uint32_t s_work[THREADS], s_nwork;
+    const uint32_t entries = min(multi_total[0], max_multi), items = entries * SORT_RUNS_PER_TILE;
+    for (uint32_t first = blockIdx.x; first < items; first += THREADS * gridDim.x) {      // (one trip unless there are > 64 k tiles to merge)
+        if (threadIdx.x == 0) s_nwork = 0;
+        __syncthreads();
+        const uint32_t item = first + threadIdx.x * gridDim.x;
+        if (item < items) {
+            const uint32_t tile = multi_tab[item % entries], run = item / entries;
+            if (merge_item_has_work(tile_offset, tile, (int)run, capacity, passes_launched, by_rank))
+                s_work[atomicAdd(&s_nwork, 1u)] = tile * SORT_RUNS_PER_TILE + run;
+        }
+        __syncthreads();
+        const uint32_t nwork = s_nwork;
+        for (uint32_t w = 0; w < nwork; w++) {
+            const uint32_t work = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_work[w]);      // (the same in every lane: scalar registers)
+            merge_tile_run(s, tile_offset, work / SORT_RUNS_PER_TILE, (int)(work % SORT_RUNS_PER_TILE), keys, tmp, passes_launched, by_rank);
+            __syncthreads();          // the next item reuses the LDS
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------ host side
 int merge_path_passes(uint32_t deepest, uint32_t headroom)
 {
@@ -817,7 +931,7 @@ int32_t launch_tile_scan(const BinningFrame &f, bool debug, hipStream_t stream)
 }
 
 int32_t launch_emit_sort(const BinningFrame &f, const BinningState &bin, uint64_t capacity, uint32_t max_units, bool inl, int fill_np, int sort_np,
-                         bool *presort_enqueued, bool debug, hipStream_t stream)
+                         bool scratch_fits, bool *presort_enqueued, bool debug, hipStream_t stream)
 {
     const ImageState &img = f.img;
     const int T = f.T;
@@ -844,15 +958,17 @@ int32_t launch_emit_sort(const BinningFrame &f, const BinningState &bin, uint64_
     const uint32_t *run_total = img.class_first + NCLASS * ((size_t)T + 1) + T;
     const uint32_t *multi_total = img.class_first + (NCLASS + 1) * ((size_t)T + 1) + T;
     GMS_LAUNCH(GMS_K_TILE_SORT, stream, tile_presort_reg_kernel<<<max_deep, 256, 0, stream>>>(img.tile_offset, run_total, bin.deep_tab, max_deep, bin.keys,
-                                                                                             sort_tmp, capacity, sort_np, inl ? img.tile_count : nullptr, T));
+                                                                                             sort_tmp, capacity, sort_np, scratch_fits,
+                                                                                             inl ? img.tile_count : nullptr, T));
     *presort_enqueued = true;
     for (int pass = 0; pass < sort_np; pass++)
         GMS_LAUNCH(GMS_K_TILE_SORT, stream, tile_mergepath_kernel<<<max_deep, 256, 0, stream>>>(img.tile_offset, run_total, bin.deep_tab, max_deep, bin.keys,
                                                                                                sort_tmp, capacity, sort_np, pass));
-    // (a merge by RANK -- K interleaved binary searches per thread instead of co-rank + serial merge -- was measured in round 5 and is
-    //  slower, tile_sort 32.5 -> 58 us: profiles/r05c_ab_merge.txt; the code is in the history of round 5)
-    GMS_LAUNCH(GMS_K_TILE_SORT, stream, tile_merge_kernel<<<max_multi, 1024, 0, stream>>>(img.tile_offset, multi_total, bin.multi_tab, max_multi, bin.keys,
-                                                                                         capacity, sort_np));
+    // (a merge by rank on ONE block per tile -- K interleaved binary searches per thread instead of co-rank + serial merge -- was
+    //  measured in round 5 and is slower, tile_sort 32.5 -> 58 us: profiles/r05c_ab_merge.txt; this one spreads a tile over a block per run)
+    const uint32_t merge_blocks = min(max_multi * (uint32_t)SORT_RUNS_PER_TILE, (uint32_t)MERGE_BLOCKS);
+    GMS_LAUNCH(GMS_K_TILE_SORT, stream, tile_merge_kernel<<<merge_blocks, 1024, 0, stream>>>(img.tile_offset, multi_total, bin.multi_tab, max_multi,
+                                                                                            bin.keys, sort_tmp, capacity, sort_np, scratch_fits));
     GMS_KERNEL_CHECK(debug, stream, "tile_sort");
     return GMS_OK;
 }

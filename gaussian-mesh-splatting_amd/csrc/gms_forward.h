@@ -45,9 +45,11 @@ struct BinningFrame {
 int32_t launch_tile_scan(const BinningFrame &f, bool debug, hipStream_t stream);
 // K3 + K4 on a carved BinningState of `capacity` instances and `max_units` unit records: emit (with the tile scan inside when
 // `inline_scan`: then the counts are published from here and the presort clears the tile counters), presort, `sort_np` merge-path
-// passes, merge.  `fill_np` is what the unit tables receive.  *presort_enqueued: the presort launch is in the stream.
+// passes, merge.  `fill_np` is what the unit tables receive.  `scratch_fits`: the segment-state area holds `capacity` keys, so the
+// sort may use it as its second side (always true when sort_np > 0); without it the 1 025 .. 8 192-key tiles are merged in place by
+// one block each.  *presort_enqueued: the presort launch is in the stream.
 int32_t launch_emit_sort(const BinningFrame &f, const BinningState &bin, uint64_t capacity, uint32_t max_units, bool inline_scan, int fill_np,
-                         int sort_np, bool *presort_enqueued, bool debug, hipStream_t stream);
+                         int sort_np, bool scratch_fits, bool *presort_enqueued, bool debug, hipStream_t stream);
 // merge-path passes that cover a tile of `deepest` + `headroom` keys; 0 while `deepest` itself fits the in-LDS merge
 int merge_path_passes(uint32_t deepest, uint32_t headroom);
 bool inline_scan_fits(int T, int P);               // does the emit launch of P Gaussians take the scan of T tiles inside?

@@ -405,7 +405,7 @@ struct ForwardTail {
         if ((uint64_t)BinningState::n_slots((size_t)capacity, L) * 7u * TILE_PIX * 4u < capacity * 8u) scratch_short = true;
         const int sort_np = scratch_short ? 0 : f.scan_np;
         bool presort_enqueued = false;
-        const int32_t rc = launch_emit_sort(f, bin, capacity, mu, inl, fill_np, sort_np, &presort_enqueued, debug, stream);
+        const int32_t rc = launch_emit_sort(f, bin, capacity, mu, inl, fill_np, sort_np, !scratch_short, &presort_enqueued, debug, stream);
         if (inl && presort_enqueued) ctr->dirty = false;          // the counters are clean again once that launch has run
         if (rc != GMS_OK) return rc;
         const BlendGrid g = make_blend_grid(W, H, f.img, bin, capacity, L);
