@@ -294,16 +294,18 @@ __device__ __forceinline__ void face_backward(const GmsMeshArgs &a, int f, const
 // backpropagates its own share through the frame and adds it to the three corners' gradients (9 float atomics per splat instead of 9 per
 // face: taken for <= 4 splats per face; dL_dvertices must be all zero on entry).  The per-splat outputs are plain stores, the formulas those
 // of bwd_splat_body / splat_contrib.
-__device__ __forceinline__ void splat_backward_from_registers(const GmsMeshArgs &a, int64_t p, const float g_xyz[3], const float g_scale[3],
-                                                              const float g_rot[4], float g_opac, float *dL_dvertices, float *dL_dalpha,
-                                                              float *dL_dscale, float *dL_d_opacity)
+// (the per-splat part, which both tails below share: the plain stores, then the splat's share of its face's nine corner sums in out[9];
+// `vi` = the face's three vertex indices)
+__device__ __forceinline__ void splat_backward_share(const GmsMeshArgs &a, int64_t p, int f, const float g_xyz[3], const float g_scale[3],
+                                                     const float g_rot[4], float g_opac, float *dL_dalpha, float *dL_dscale, float *dL_d_opacity,
+                                                     int64_t vi[3], float out[9])
 {
     {   // sigmoid backward: g * (1 - y) * y
         const float y = 1.f / (1.f + expf(-a._opacity[p]));
         dL_d_opacity[p] = g_opac * (1.f - y) * y;
     }
-    const int f = splat_to_face(a, p);
     const int64_t i0 = a.faces[3 * (size_t)f], i1 = a.faces[3 * (size_t)f + 1], i2 = a.faces[3 * (size_t)f + 2];
+    vi[0] = i0; vi[1] = i1; vi[2] = i2;
     const V3 t0 = ldv(a.vertices, (size_t)i0), t1 = ldv(a.vertices, (size_t)i1), t2 = ldv(a.vertices, (size_t)i2);
     const float raw[3] = {a._alpha[3 * p], a._alpha[3 * p + 1], a._alpha[3 * p + 2]};
     float al[3], rsum;
@@ -332,8 +334,16 @@ __device__ __forceinline__ void splat_backward_from_registers(const GmsMeshArgs 
     G.dq[0] = g_rot[0]; G.dq[1] = g_rot[1]; G.dq[2] = g_rot[2]; G.dq[3] = g_rot[3];
     if (sc * fr.s1 > 0.f) G.ds1 = g_scale[1] * sc;
     if (sc * fr.s2 > 0.f) G.ds2 = g_scale[2] * sc;
-    float out[9];
     face_backward(a, f, fr, G, out);
+}
+
+__device__ __forceinline__ void splat_backward_from_registers(const GmsMeshArgs &a, int64_t p, const float g_xyz[3], const float g_scale[3],
+                                                              const float g_rot[4], float g_opac, float *dL_dvertices, float *dL_dalpha,
+                                                              float *dL_dscale, float *dL_d_opacity)
+{
+    int64_t vi[3];
+    float out[9];
+    splat_backward_share(a, p, splat_to_face(a, p), g_xyz, g_scale, g_rot, g_opac, dL_dalpha, dL_dscale, dL_d_opacity, vi, out);
     // The splats of a face are consecutive lanes (uniform splat count, <= 4).  The FIRST lane of a face's run inside this wave collects
     // the run's nine sums (9 atomics per splat on the same three corners in the same instruction: 146 us against 56 for the two
     // launches; one set per run: 59).  A face split between two waves leaves two partial runs: the sum is linear.  Where the run is a
@@ -359,7 +369,6 @@ __device__ __forceinline__ void splat_backward_from_registers(const GmsMeshArgs 
         }
     }
     const bool whole3 = S == 3 && r + tail == 2;
-    const int64_t vi[3] = {i0, i1, i2};
 #pragma unroll
     for (int k = 0; k < 3; k++) {
         const float v1 = __shfl_up(sum[3 * k + 1], 1), v2 = __shfl_up(sum[3 * k + 2], 2);
@@ -367,6 +376,60 @@ __device__ __forceinline__ void splat_backward_from_registers(const GmsMeshArgs 
         if (whole3 && v != 0.f) unsafeAtomicAdd(dL_dvertices + 3 * (size_t)vi[k] + r, v);
     }
     if (whole3 || r != 0) return;
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int c = 0; c < 3; c++)
+            if (sum[3 * k + c] != 0.f) unsafeAtomicAdd(dL_dvertices + 3 * (size_t)vi[k] + c, sum[3 * k + c]);
+}
+
+// lane l <- lane l + 1 of the wave (DPP wave_shl:1, one VALU operation; lane 63 gets 0).  Every lane takes part.
+__device__ __forceinline__ float wave_next_lane(float v)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
+}
+
+// The same for runs of ANY length (more than four splats per face, or per-splat face ids from CSR tables): the nine corner sums of a
+// face are reduced over the wave by a SEGMENTED suffix sum.  A run is a maximal stretch of consecutive lanes with the same face id --
+// nothing else is assumed: not that the ids are monotone, not that a run starts at a face's first splat (a face split between waves
+// leaves partial runs; the sum is linear).  One ballot of "my face differs from the lane below" gives the heads, the next head above a
+// lane its run's end; then log-steps of 1, 2, 4 .. 32 add lane + d where that lane is still inside the run, as many steps as the
+// LONGEST run of this wave needs (runs of 5: three steps, runs that fill the wave: six).  Only a run's first lane issues the nine
+// atomics, exact zeros skipped as above.  EVERY lane of the wave calls this (`valid` = false for the lanes past P of the last wave:
+// they load nothing, hand in zeros and form a run of their own that nobody adds).
+__device__ __forceinline__ void splat_backward_runs_from_registers(const GmsMeshArgs &a, int64_t p, bool valid, const float g_xyz[3],
+                                                                   const float g_scale[3], const float g_rot[4], float g_opac,
+                                                                   float *dL_dvertices, float *dL_dalpha, float *dL_dscale, float *dL_d_opacity)
+{
+    int f = -1;                                          // (no face has a negative id)
+    int64_t vi[3] = {0, 0, 0};
+    float sum[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (valid) {
+        f = splat_to_face(a, p);
+        splat_backward_share(a, p, f, g_xyz, g_scale, g_rot, g_opac, dL_dalpha, dL_dscale, dL_d_opacity, vi, sum);
+    }
+    const int lane = (int)(threadIdx.x & 63);
+    const int below = __shfl_up(f, 1);
+    const uint64_t heads = __ballot(lane == 0 || below != f);
+    const uint64_t above = lane == 63 ? 0ull : heads >> (lane + 1);          // heads of the lanes after this one
+    const int tail = above ? (int)__builtin_ctzll(above) : 63 - lane;       // lanes of the run after this one
+    if (__ballot(tail >= 1)) {                           // d = 1 by DPP
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+            const float o = wave_next_lane(sum[k]);
+            if (tail >= 1) sum[k] += o;
+        }
+    }
+#pragma unroll
+    for (int d = 2; d < 64; d *= 2) {
+        if (!__ballot(tail >= d)) break;                 // (wave-uniform)
+#pragma unroll
+        for (int k = 0; k < 9; k++) {
+            const float o = __shfl_down(sum[k], d);
+            if (tail >= d) sum[k] += o;
+        }
+    }
+    if (!valid || (heads >> lane & 1ull) == 0) return;
 #pragma unroll
     for (int k = 0; k < 3; k++)
 #pragma unroll

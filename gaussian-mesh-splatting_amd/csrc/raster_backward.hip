@@ -92,7 +92,13 @@ constexpr int BWD_RESTF = 45;                                        // floats p
 constexpr int BWD_WAVE_FLOATS = WAVE * SH_PITCH_B;                   // 3 328 >= 64 x 45 + 64 x 3
 static_assert(BWD_WAVE_FLOATS >= WAVE * BWD_RESTF + WAVE * 3, "the split image fits the wave's LDS");
 
-template <bool MESH>
+// MESH: the mesh backward in the tail.  `Runs` empty: for runs of at most four lanes (splat_backward_from_registers); <true, MeshRuns>:
+// for runs of any length (splat_backward_runs_from_registers).  The third kernel is a TAG on a parameter pack because the body has to
+// stay in the __global__ function itself: called through a __device__ template (forced inline) the two instantiations that
+// tests/test_kernel_resources_cpu.py pins by name came out with other registers (<false>: 92 -> 96 VGPRs, 58 -> 54 SGPRs), and an
+// empty pack leaves their names -- preprocess_bwd_kernel<false>, preprocess_bwd_kernel<true> -- and their code as they were.
+struct MeshRuns;
+template <bool MESH, typename... Runs>
 __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int dst_vec)
 {
     // Contraction is held to what ONE source expression allows (the front end's choice, the same in both instantiations).  Under the file's
@@ -101,6 +107,8 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
     // (tests/test_gpu_fused_training.py::test_mesh_backward_inside_preprocess_bwd_equals_the_mesh_backward_launch[203-2] fails under `fast`).
 #pragma clang fp contract(on)
     __shared__ __attribute__((aligned(16))) float sh_lds[4 * BWD_WAVE_FLOATS];
+    constexpr bool RUNS = sizeof...(Runs) > 0;
+    static_assert(MESH || !RUNS, "the runs tail is a mesh tail");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x * BLOCK + tid;
     const bool valid = i < a.P;
@@ -274,12 +282,19 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
         }
     }
 
+    if (MESH && RUNS) {
+        // ... with its per-face sums reduced over runs of any length: every lane of the wave takes part, the ones past P too.  Before
+        // the SH rows, as the other tail
+        const float gs[3] = {dscale[0], dscale[1], dscale[2]}, gq[4] = {drot[0], drot[1], drot[2], drot[3]};
+        splat_backward_runs_from_registers(a.mesh, (int64_t)i, valid, dmean, gs, gq, dop, a.mesh_dvertices, a.mesh_dalpha, a.mesh_dscale,
+                                           a.mesh_dopacity);
+    }
     if (valid) {
-    if (MESH) {
+    if (MESH && !RUNS) {
         // the frame came straight from the mesh (gmsplat.h, ABI 8): on through the face -> Gaussian parameterization from registers
         const float gs[3] = {dscale[0], dscale[1], dscale[2]}, gq[4] = {drot[0], drot[1], drot[2], drot[3]};
         splat_backward_from_registers(a.mesh, (int64_t)i, dmean, gs, gq, dop, a.mesh_dvertices, a.mesh_dalpha, a.mesh_dscale, a.mesh_dopacity);
-    } else {
+    } else if (!MESH) {
         a.dL_dopacity[i] = dop;
     }
     a.dL_dmean2D[3 * (size_t)i] = acc_mx; a.dL_dmean2D[3 * (size_t)i + 1] = acc_my; a.dL_dmean2D[3 * (size_t)i + 2] = 0.f;
@@ -487,10 +502,11 @@ extern "C" int32_t gms_rasterize_backward(const GmsRasterBackwardArgs *A, void *
     if (mesh) {
         const int32_t mrc = check_mesh_args(mesh, false);
         if (mrc != GMS_OK) return mrc;
-        if (mesh->P != (int64_t)P || mesh->splats_per_face <= 0 || mesh->splats_per_face > 4 || !mesh->_opacity || !sr || A->cov3D_precomp ||
+        // (any uniform count, or splats_per_face == 0 with `splat_face`, which check_mesh_args has required then; `face_splat_offset` is not read)
+        if (mesh->P != (int64_t)P || !mesh->_opacity || !sr || A->cov3D_precomp ||
             !A->mesh_dL_dvertices || !A->mesh_dL_dalpha || !A->mesh_dL_dscale || !A->mesh_dL_d_opacity || det_mode()) {
-            set_error("gms_rasterize_backward: the mesh backward inside preprocess_bwd needs a complete GmsMeshArgs (P equal, 1-4 splats per face, "
-                      "_opacity), the scales + rotations path, all four mesh_dL_* outputs, and is not available in deterministic mode");
+            set_error("gms_rasterize_backward: the mesh backward inside preprocess_bwd needs a complete GmsMeshArgs (P equal, a uniform splat count "
+                      "or splat_face [P], _opacity), the scales + rotations path, all four mesh_dL_* outputs, and is not available in deterministic mode");
             return GMS_ERR_INVALID_ARGUMENT;
         }
     }
@@ -555,7 +571,10 @@ extern "C" int32_t gms_rasterize_backward(const GmsRasterBackwardArgs *A, void *
     const int dst_vec = A->shs_rest && !A->sh_factor_mode && (((uintptr_t)A->dL_dsh) & 15u) == 0 && (((uintptr_t)A->dL_dsh_rest) & 15u) == 0;
     if (mesh) {
         p.mesh = *mesh; p.mesh_dvertices = A->mesh_dL_dvertices; p.mesh_dalpha = A->mesh_dL_dalpha; p.mesh_dscale = A->mesh_dL_dscale; p.mesh_dopacity = A->mesh_dL_d_opacity;
-        GMS_LAUNCH(GMS_K_PREPROCESS_BWD, stream, preprocess_bwd_kernel<true><<<(unsigned)((P + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(p, dst_vec));
+        if (mesh->splats_per_face >= 1 && mesh->splats_per_face <= 4)
+            GMS_LAUNCH(GMS_K_PREPROCESS_BWD, stream, preprocess_bwd_kernel<true><<<(unsigned)((P + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(p, dst_vec));
+        else      // longer runs, CSR tables: the segmented reduction
+            GMS_LAUNCH(GMS_K_PREPROCESS_BWD, stream, preprocess_bwd_kernel<true, MeshRuns><<<(unsigned)((P + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(p, dst_vec));
     } else {
         GMS_LAUNCH(GMS_K_PREPROCESS_BWD, stream, preprocess_bwd_kernel<false><<<(unsigned)((P + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(p, dst_vec));
     }

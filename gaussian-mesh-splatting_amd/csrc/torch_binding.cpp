@@ -98,6 +98,9 @@ static int64_t quantize_capacity(int64_t x)
 }
 
 struct LastCall { int64_t num_rendered = 0, num_units = 0, hint = 0, P = 0; int W = 0, H = 0; Tensor radii, image, binning, geom; } g_last;
+// which way the mesh backward of the most recent render_mesh backward went (last_stats()["mesh_backward_route"])
+enum MeshBwdRoute { MESH_BWD_NONE = 0, MESH_BWD_TAIL4, MESH_BWD_TAIL_RUNS, MESH_BWD_LAUNCH };
+static std::atomic<int> g_mesh_bwd_route{MESH_BWD_NONE};
 std::atomic<bool> g_keep_buffers{false};
 
 struct Forward {
@@ -125,6 +128,16 @@ bool fused_mesh_backward()
     return v != 0;
 }
 void set_fused_mesh_backward(bool on) { g_fused_mesh_bwd.store(on ? 1 : 0); }
+// ... for runs of any length (more than four splats per face, CSR tables: preprocess_bwd_kernel<true, MeshRuns>).  GMS_TRAIN_FUSED_BWD_RUNS=0 /
+// set_fused_mesh_backward_runs(False) keeps the mesh_bwd launch for those shapes and leaves 1-4 splats per face as they are.
+static std::atomic<int> g_fused_mesh_bwd_runs{-1};
+bool fused_mesh_backward_runs()
+{
+    int v = g_fused_mesh_bwd_runs.load();
+    if (v < 0) { const char *e = getenv("GMS_TRAIN_FUSED_BWD_RUNS"); int expected = -1; g_fused_mesh_bwd_runs.compare_exchange_strong(expected, (e && atoi(e) == 0) ? 0 : 1); v = g_fused_mesh_bwd_runs.load(); }
+    return v != 0;
+}
+void set_fused_mesh_backward_runs(bool on) { g_fused_mesh_bwd_runs.store(on ? 1 : 0); }
 // what a frame rendered straight from a mesh stores for its backward (GmsRasterForwardArgs.mesh_out_*, ABI 6)
 struct MeshOut { Tensor xyz, scaling_act, rotation_unit, opacity_act; };
 
@@ -541,6 +554,8 @@ py::dict last_stats()
     d["num_rendered"] = g_last.num_rendered; d["num_units"] = g_last.num_units; d["capacity_hint"] = g_last.hint;
     d["P"] = g_last.P; d["width"] = g_last.W; d["height"] = g_last.H; d["deepest_tile"] = gms_last_deepest_tile();
     d["used_micro"] = (int)gms_last_used_micro();
+    static const char *const routes[] = {"none", "tail4", "tail_runs", "launch"};
+    d["mesh_backward_route"] = routes[g_mesh_bwd_route.load()];
     if (g_last.radii.defined()) { d["radii"] = g_last.radii; d["image"] = g_last.image; d["binning"] = g_last.binning; d["geom"] = g_last.geom; }
     return d;
 }
@@ -817,7 +832,7 @@ public:
     static variable_list forward(AutogradContext *ctx, Tensor vertices_, Tensor faces, Tensor alpha_, Tensor scale_, Tensor opacity_,
                                  Tensor sh_dc, Tensor sh_rest, Tensor means2D, int64_t mode, int64_t spf, Tensor splat_face, Tensor bg,
                                  Tensor view, Tensor proj, Tensor campos, int64_t H, int64_t W, double tanx, double tany, double mod,
-                                 bool aa, bool debug, bool vertex_grad, bool will_backward, int64_t sh_degree)
+                                 bool aa, bool debug, bool vertex_grad, bool will_backward, int64_t sh_degree, Tensor face_splat_offset)
     {
         ctx->set_materialize_grads(false);
         TORCH_CHECK(sh_degree >= 0 && sh_degree <= 3, "render_mesh: active SH degree ", sh_degree, " (storage is degree 3: 0 .. 3)");
@@ -830,6 +845,8 @@ public:
         Tensor vgrad = will_backward && vertex_grad ? torch::empty_like(v) : Tensor();
         if (will_backward) stash_backward(ctx, alloc_backward(stored_gaussians(mo, dc, rest)));      // (see Backward)
         Tensor sf = (splat_face.defined() && splat_face.numel()) ? splat_face.to(torch::kInt).contiguous() : Tensor();
+        Tensor fso = (face_splat_offset.defined() && face_splat_offset.numel()) ? face_splat_offset.to(torch::kInt).contiguous() : Tensor();
+        TORCH_CHECK(!fso.defined() || (fso.numel() == faces.size(0) + 1 && fso.device() == dev), "render_mesh: face_splat_offset must hold F + 1 offsets on the mesh's device");
         GmsMeshArgs m = mesh_args(v, faces, al, sc, mode, spf, Tensor(), sf, true, op);
         m.prezero = mf(vgrad); m.prezero_count = vgrad.defined() ? vgrad.numel() : 0;
         // `visibility_filter` (radii > 0, renderer/gaussian_renderer/__init__.py:108) out of the preprocess kernel, as on the two-node route
@@ -837,7 +854,7 @@ public:
         const FrameSettings s = frame_settings(dc.device(), bg, view, proj, campos, H, W, tanx, tany, mod, sh_degree, false, aa, debug);
         Forward f = forward_core(s, P, dc.device(), {dc, rest}, visible, true, &m, &mo, will_backward);
         save_frame(ctx, {v, faces, al, sc, op, sf.defined() ? sf : torch::empty({0}, fopt), vgrad.defined() ? vgrad : torch::empty({0}, fopt),
-                         mo.xyz, mo.scaling_act, mo.rotation_unit, mo.opacity_act, dc, rest}, s, f);
+                         mo.xyz, mo.scaling_act, mo.rotation_unit, mo.opacity_act, dc, rest, fso.defined() ? fso : torch::empty({0}, fopt)}, s, f);
         ctx->saved_data["mode"] = mode; ctx->saved_data["spf"] = spf; ctx->saved_data["used"] = false;
         // the stored Gaussians are by-products for the model's attributes: gradients reach the mesh parameters through THIS node
         ctx->mark_non_differentiable({f.radii, mo.xyz, mo.scaling_act, mo.rotation_unit, mo.opacity_act, visible});
@@ -848,7 +865,7 @@ public:
     {
         auto saved = ctx->get_saved_variables();
         const Tensor &v = saved[0], &faces = saved[1], &al = saved[2], &sc = saved[3], &op = saved[4];
-        Tensor sf = saved[5].numel() ? saved[5] : Tensor();
+        Tensor sf = saved[5].numel() ? saved[5] : Tensor(), fso = saved[13].numel() ? saved[13] : Tensor();
         const Gaussians g = stored_gaussians({saved[7], saved[8], saved[9], saved[10]}, saved[11], saved[12]);
         auto [s, f] = load_frame(ctx, saved);
         const auto dev = v.device();
@@ -861,37 +878,42 @@ public:
         if (saved[6].numel() && !ctx->saved_data["used"].toBool()) { d_vertices = saved[6]; prezeroed = true; ctx->saved_data["used"] = true; }
         else d_vertices = torch::empty_like(v);
         Tensor d_alpha = torch::empty_like(al), d_scale = torch::empty_like(sc), d_opacity = torch::empty_like(op);
-        GmsMeshArgs a = mesh_args(v, faces, al, sc, ctx->saved_data["mode"].toInt(), ctx->saved_data["spf"].toInt(), Tensor(), sf, true, op);
+        GmsMeshArgs a = mesh_args(v, faces, al, sc, ctx->saved_data["mode"].toInt(), ctx->saved_data["spf"].toInt(), fso, sf, true, op);
         a.vertex_grad_prezeroed = prezeroed;
         // The mesh backward INSIDE preprocess_bwd (ABI 8): the thread of a Gaussian carries its gradients on through the face -> Gaussian
         // parameterization from registers -- no dL/dxyz / dL/dscale / dL/drot / dL/dopacity tensors, no mesh_bwd launch.  Needs the vertex
-        // gradient buffer the forward cleared, 1-4 splats per face, float-atomics mode.  GMS_TRAIN_FUSED_BWD=0 keeps the two launches.
-        const bool fused_bwd = fused_mesh_backward() && prezeroed && a.splats_per_face > 0 && a.splats_per_face <= 4 && !gms_get_deterministic() && !g_sh_factor.load();
+        // gradient buffer the forward cleared and float-atomics mode.  1-4 splats per face: the tail of preprocess_bwd_kernel<true>; more, or
+        // CSR tables: the segmented reduction of preprocess_bwd_kernel<true, MeshRuns>.  GMS_TRAIN_FUSED_BWD=0 keeps the two launches for every shape,
+        // GMS_TRAIN_FUSED_BWD_RUNS=0 for the second class alone.
+        const bool tail4 = a.splats_per_face >= 1 && a.splats_per_face <= 4;
+        const bool fused_bwd = fused_mesh_backward() && (tail4 || fused_mesh_backward_runs()) && prezeroed && !gms_get_deterministic() && !g_sh_factor.load();
+        g_mesh_bwd_route.store(!fused_bwd ? MESH_BWD_LAUNCH : tail4 ? MESH_BWD_TAIL4 : MESH_BWD_TAIL_RUNS);
         MeshGrads mg{d_vertices, d_alpha, d_scale, d_opacity};
         Backward b = backward_core(s, g, f, gcol, grads[2], pre ? &*pre : nullptr, fused_bwd ? &a : nullptr, fused_bwd ? &mg : nullptr);
         if (!fused_bwd) {
             // ... else through the mesh -> Gaussian parameterization as a launch of its own (fused activations: gradients w.r.t. exp / normalize /
-            // sigmoid outputs).  Non-uniform splat counts: the per-face part of the mesh backward walks CSR offsets this node does not carry.
-            TORCH_CHECK(a.splats_per_face > 0, "render_mesh backward: non-uniform splat counts take the two-node graph (mesh_to_gaussians + rasterize)");
+            // sigmoid outputs).  Non-uniform splat counts: its per-face part walks the CSR offsets the node carries for this.
+            TORCH_CHECK(a.splats_per_face > 0 || fso.defined(), "render_mesh backward: the mesh backward launch of non-uniform splat counts needs face_splat_offset");
             check_rc(gms_mesh_to_gaussians_backward(&a, cf(b.dmeans3D), cf(b.dscales), cf(b.drots), cf(b.dopacity), mf(d_vertices), mf(d_alpha),
                                                     mf(d_scale), mf(d_opacity), stream_of(v)), "gms_mesh_to_gaussians_backward");
         }
         Tensor none;
         return {d_vertices, none, d_alpha, d_scale, d_opacity, b.dsh, b.dsh_rest, b.dmeans2D,
-                none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none};
+                none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none};
     }
 };
 
 std::vector<Tensor> render_mesh(const Tensor &vertices, const Tensor &faces, const Tensor &_alpha, const Tensor &_scale, const Tensor &_opacity,
                                 const Tensor &sh_dc, const Tensor &sh_rest, const Tensor &means2D, int64_t mode, int64_t spf, const Tensor &splat_face,
                                 const Tensor &bg, const Tensor &view, const Tensor &proj, const Tensor &campos, int64_t H, int64_t W, double tanx,
-                                double tany, double mod, bool aa, bool debug, int64_t sh_degree)
+                                double tany, double mod, bool aa, bool debug, int64_t sh_degree, const std::optional<Tensor> &face_splat_offset)
 {
     const bool will_backward = at::GradMode::is_enabled() &&
         (vertices.requires_grad() || _alpha.requires_grad() || _scale.requires_grad() || _opacity.requires_grad() || sh_dc.requires_grad() ||
          sh_rest.requires_grad() || means2D.requires_grad());
     return RenderMeshFn::apply(vertices, faces, _alpha, _scale, _opacity, sh_dc, sh_rest, means2D, mode, spf, splat_face, bg, view, proj, campos, H, W,
-                               tanx, tany, mod, aa, debug, vertices.requires_grad(), will_backward, sh_degree);
+                               tanx, tany, mod, aa, debug, vertices.requires_grad(), will_backward, sh_degree,
+                               face_splat_offset ? *face_splat_offset : torch::empty({0}, faces.options().dtype(torch::kInt)));      // (a defined tensor: autograd asks every tensor argument for its device)
 }
 
 // ---------------------------------------------------------------------------------------------- fused L1 + SSIM
@@ -1408,7 +1430,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("flame_forward", &flame_forward, "the FLAME layer without a graph: one launch", py::arg("tables"), py::arg("parents"), py::arg("rots"),
           py::arg("rot_joints"), py::arg("shape"), py::arg("expression"), py::arg("transl") = py::none(), py::arg("enlargement") = py::none(),
           py::arg("enlargement_scalar") = 1.0, py::arg("swap") = false, nogil());
-    m.def("render_mesh", &render_mesh, "differentiable frame straight from a mesh: [image, radii, invdepth, xyz, scaling_act, rotation_unit, opacity_act]", nogil());
+    m.def("render_mesh", &render_mesh, "differentiable frame straight from a mesh: [image, radii, invdepth, xyz, scaling_act, rotation_unit, opacity_act]",
+          py::arg("vertices"), py::arg("faces"), py::arg("_alpha"), py::arg("_scale"), py::arg("_opacity"), py::arg("sh_dc"), py::arg("sh_rest"),
+          py::arg("means2D"), py::arg("mode"), py::arg("spf"), py::arg("splat_face"), py::arg("bg"), py::arg("view"), py::arg("proj"), py::arg("campos"),
+          py::arg("H"), py::arg("W"), py::arg("tanx"), py::arg("tany"), py::arg("mod"), py::arg("aa"), py::arg("debug"), py::arg("sh_degree"),
+          py::arg("face_splat_offset") = py::none(), nogil());
     m.def("l1_ssim", &l1_ssim, "differentiable w_l1 * L1 + w_ssim * SSIM + bias; returns (value [0-dim], [l1, ssim])", nogil());
     m.def("image_metrics", &image_metrics, "evaluation sums of image pairs into rows of a device table: (img_u8, gt_u8) or two empty tensors; launches only", nogil());
     m.def("ground_truth_u8", &ground_truth_u8, "decoded bytes [B,H,W,C] -> (ground truth float32 [B,3,out_h,out_w], launches made): composite, Pillow's "
@@ -1426,6 +1452,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("deferred_counts", &deferred_counts);
     m.def("set_fused_mesh_backward", &set_fused_mesh_backward, "frames rendered straight from a mesh: run the mesh backward inside preprocess_bwd (default on)");
     m.def("fused_mesh_backward", &fused_mesh_backward);
+    m.def("set_fused_mesh_backward_runs", &set_fused_mesh_backward_runs, "... for more than four splats per face and CSR tables (the segmented reduction; default on)");
+    m.def("fused_mesh_backward_runs", &fused_mesh_backward_runs);
     m.def("set_capacity", &set_capacity);
     m.def("clear_capacity", &clear_capacity);
     m.def("abi_version", []() { return (int64_t)gms_abi_version(); });

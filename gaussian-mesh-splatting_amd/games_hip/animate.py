@@ -78,10 +78,24 @@ def render_frame(vertices: torch.Tensor, faces: torch.Tensor, view, gaussians, p
 @torch.no_grad()
 def render_time_animated(gaussians, views: Iterable, pipeline, background: torch.Tensor,
                          transform: Callable = transform_hotdog_fly, idxs=None, out_dir: Optional[str] = None,
-                         t_max: float = 10 * math.pi) -> List[torch.Tensor]:
-    """scripts/render_time_animated.py:68-87.  Returns the rendered frames (device tensors [3,H,W])."""
+                         t_max: float = 10 * math.pi, mesh: int = 0) -> List[torch.Tensor]:
+    """scripts/render_time_animated.py:68-87.  Returns the rendered frames (device tensors [3,H,W]).  A multi-mesh model
+    (`gaussians.vertices` a list): the transform moves mesh number `mesh` against the others, every frame goes mesh -> image
+    (`render_mesh_frame` with per-mesh vertices)."""
     views = list(views)
     ts = torch.linspace(0, t_max, max(len(views), 1))
+    if isinstance(gaussians.vertices, (list, tuple)):
+        per_mesh = [v.detach().clone() for v in gaussians.vertices]      # working copies, as below
+        frames = []
+        if out_dir:
+            os.makedirs(out_dir, exist_ok=True)
+        for k, view in enumerate(views):
+            per_mesh[mesh] = transform(per_mesh[mesh], ts[k], idxs)
+            img = render_mesh_frame(per_mesh, None, view, gaussians, pipeline, background)["render"]
+            frames.append(img)
+            if out_dir:
+                _save(img, os.path.join(out_dir, f"{k:05d}.png"))
+        return frames
     vertices = gaussians.vertices.detach().clone()      # working copy: the in-place transforms accumulate in it, as in the reference
     faces = gaussians.faces.long()
     if out_dir:

@@ -97,3 +97,15 @@ def mesh_point_cloud(mesh: TriMesh, num_splats: int, seed: Optional[int] = None,
     shs = rng.random((F * num_splats, 3)) / 255.0
     return MeshPointCloud(alpha=alpha, points=xyz, colors=shs * C0 + 0.5, normals=np.zeros((F * num_splats, 3)),
                           vertices=vertices, faces=faces, transform_vertices_function=transform, triangles=triangles)
+
+
+def multi_mesh_point_clouds(meshes, num_splats, seed: Optional[int] = None, transform=transform_vertices_function):
+    """One MeshPointCloud per mesh of a gs_multi_mesh model (games/multi_mesh_splatting/scene/dataset_readers.py builds the same
+    list from its COLMAP directories): `meshes` holds OBJ paths or TriMesh objects, `num_splats` one count per mesh (or one int for
+    all).  Mesh i draws from `seed + i`, so equal meshes do not get equal splats."""
+    meshes = list(meshes)
+    counts = [int(num_splats)] * len(meshes) if isinstance(num_splats, int) else [int(n) for n in num_splats]
+    if len(counts) != len(meshes):
+        raise ValueError(f"multi_mesh_point_clouds: {len(meshes)} meshes, {len(counts)} splat counts")
+    return [mesh_point_cloud(load_obj(m) if isinstance(m, str) else m, n, None if seed is None else seed + i, transform)
+            for i, (m, n) in enumerate(zip(meshes, counts))]

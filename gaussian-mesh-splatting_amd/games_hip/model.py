@@ -144,12 +144,9 @@ class _HipGetters:
         return SplitSH(self._features_dc, self._features_rest)
 
 
-class HipMeshMixin(_HipGetters):
-    """Host class provides: vertices [V,3], faces [F,3], _alpha [F,S,3], _scale [P,1] (attribute name in
-    `_hip_scale_attr`); optional `_opacity` [P,1].  `alpha_mode`: "relu" (mesh models) or "softmax" (FLAME)."""
-
-    alpha_mode = "relu"
-    _hip_scale_attr = "_scale"
+class _HipDeferredK0(_HipGetters):
+    """The deferred K0 that the mesh and the multi-mesh mixin share.  A user provides `_hip_inputs()` (the tensors the op reads),
+    `_hip_derive()` (the K0 launch: sets `alpha` / `_xyz`, leaves scaling / rotation in `_Derived.geometry`) and prepare_scaling_rot()."""
 
     # ---- deferred K0 (opt-in; games_hip/train.py and bench.py switch it on).  train.py:154-157 calls update_alpha() /
     # prepare_scaling_rot() after every optimizer step and the next thing that happens is render() (train.py:100): with
@@ -191,6 +188,22 @@ class HipMeshMixin(_HipGetters):
         inputs are unchanged, so that e.g. an evaluation pass right after a training step launches no K0 either."""
         self._hip.frame = _Stamp((xyz, scaling_act, rotation_unit, opacity_act), *self._hip_inputs(), self._opacity)
 
+    def update_alpha(self):
+        d = self._hip
+        if self._hip_defer_now():
+            d.pending = True          # render() will derive the Gaussians inside the rasterizer (see hip_defer_k0)
+            return
+        d.pending = d.pending and not torch.is_grad_enabled()
+        self._hip_derive()
+
+
+class HipMeshMixin(_HipDeferredK0):
+    """Host class provides: vertices [V,3], faces [F,3], _alpha [F,S,3], _scale [P,1] (attribute name in
+    `_hip_scale_attr`); optional `_opacity` [P,1].  `alpha_mode`: "relu" (mesh models) or "softmax" (FLAME)."""
+
+    alpha_mode = "relu"
+    _hip_scale_attr = "_scale"
+
     # ---- inputs of the op (overridden by the FLAME mixin, whose vertices come out of the FLAME layer)
     def _hip_inputs(self):
         return self.vertices, self.faces, self._alpha, getattr(self, self._hip_scale_attr)
@@ -211,14 +224,18 @@ class HipMeshMixin(_HipGetters):
         d.geometry = _Stamp(tuple(out[2:6]), vertices, faces, _alpha, _scale) if have_scale else None
         return out[0], out[1]
 
-    def update_alpha(self):
-        d = self._hip
-        if self._hip_defer_now():
-            d.pending = True          # render() will derive the Gaussians inside the rasterizer (see hip_defer_k0)
-            return
-        d.pending = d.pending and not torch.is_grad_enabled()
+    def _hip_derive(self):
         self.alpha, self._xyz = self._hip_run()
-        d.tri_external = None
+        self._hip.tri_external = None
+
+    def _hip_frame_inputs(self):
+        """What games_hip.render hands `_C.render_mesh` / `render_mesh_forward` for this model: (vertices, faces, _alpha, _scale,
+        splats per face, splat_face, face_splat_offset); None while the sizes do not fit a frame straight from the mesh."""
+        vertices, faces, _alpha, _scale = self._hip_inputs()
+        if not (torch.is_tensor(_alpha) and _alpha.dim() == 3 and _alpha.is_cuda and torch.is_tensor(faces) and torch.is_tensor(_scale)
+                and _scale.numel() == _alpha.shape[0] * _alpha.shape[1]):
+            return None
+        return vertices, faces, _alpha, _scale, int(_alpha.shape[1]), None, None
 
     @property
     def triangles(self):
@@ -299,11 +316,49 @@ class HipFlameMixin(HipMeshMixin):
         return super(HipMeshMixin, self).save_ply(path)
 
 
-class HipMultiMeshMixin(_HipGetters):
+class _FlatOfLeaves(torch.autograd.Function):
+    """The flat buffer that a list of leaves are slices of, as a differentiable function of those leaves: forward hands the buffer
+    on (no launch), backward hands every leaf its rows of the flat gradient as a view (no launch either)."""
+
+    @staticmethod
+    def forward(ctx, flat, *leaves):
+        ctx.shapes = [tuple(t.shape) for t in leaves]
+        return flat.view(flat.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        out, row = [None], 0
+        for shape in ctx.shapes:
+            n = 1
+            for k in shape[:-1]:
+                n *= k
+            out.append(g.narrow(0, row, n).reshape(shape))
+            row += n
+        return tuple(out)
+
+
+def _flat_with_slices(tensors, device):
+    """(flat [sum rows, C], [nn.Parameter of a slice of it per tensor]): every parameter is a leaf of its own that shares the flat
+    buffer's storage, so in-place optimizer steps keep the buffer current."""
+    rows = [t.reshape(-1, t.shape[-1]) for t in tensors]
+    flat = torch.cat([r.detach().to(device).float() for r in rows]).contiguous()
+    leaves, row = [], 0
+    for t, r in zip(tensors, rows):
+        leaves.append(nn.Parameter(flat[row:row + r.shape[0]].view(t.shape)))
+        row += r.shape[0]
+    return flat, leaves
+
+
+class HipMultiMeshMixin(_HipDeferredK0):
     """GaussianMultiMeshModel.update_alpha / _calc_xyz / prepare_scaling_rot: the per-mesh python loop and the
     torch.cat of its results become ONE launch over the concatenated meshes (faces re-indexed by the vertex
     offsets, splat ranges as CSR because every mesh may carry a different number of splats per face).
-    Host class provides the reference's list attributes: vertices[i], faces[i], _alpha[i] [F_i,S_i,3], _scale[i] [P_i,1]."""
+    Host class provides the reference's list attributes: vertices[i], faces[i], _alpha[i] [F_i,S_i,3], _scale[i] [P_i,1].
+    With `hip_defer_k0` (HipMeshMixin's, shared) the training frame is rendered straight from the concatenated mesh.
+
+    `_hip_flat_store` (optional, set by the stand-alone model's constructors): {"vertices" | "_alpha" | "_scale": flat buffer} whose
+    slices the list entries are.  While that holds -- checked by address on every use, no launch -- the concatenation IS the
+    buffer; otherwise (the reference's class under this mixin, a list entry somebody reassigned) it is a torch.cat, as before."""
 
     def _hip_topology(self):
         shapes = tuple((int(f.shape[0]), int(a.shape[1]), int(v.shape[0])) for f, a, v in zip(self.faces, self._alpha, self.vertices))
@@ -327,11 +382,37 @@ class HipMultiMeshMixin(_HipGetters):
     def _hip_inputs(self):
         return (*self.vertices, *self.faces, *self._alpha, *self._scale)
 
+    def _hip_flat(self, name, width):
+        """The concatenation [sum rows, width] of the list `name`, differentiable to its entries."""
+        leaves = list(getattr(self, name))
+        flat = self.__dict__.get("_hip_flat_store", {}).get(name)
+        if flat is not None:
+            row, ok = 0, True
+            for t in leaves:
+                n = t.numel() // width
+                ok = ok and (t.dtype == flat.dtype and t.device == flat.device and t.is_contiguous() and t.shape[-1] == width
+                             and t.data_ptr() == flat.data_ptr() + 4 * width * row)
+                row += n
+            if ok and row == flat.shape[0]:
+                return _FlatOfLeaves.apply(flat, *leaves) if torch.is_grad_enabled() and any(t.requires_grad for t in leaves) else flat
+        return torch.cat([t.reshape(-1, width) for t in leaves])
+
+    def _hip_flat_inputs(self):
+        return self._hip_flat("vertices", 3), self._hip_flat("_alpha", 3), self._hip_flat("_scale", 1)
+
+    def _hip_frame_inputs(self):
+        """(see HipMeshMixin._hip_frame_inputs) the concatenated meshes with their CSR splat tables."""
+        if not (len(self._alpha) and all(torch.is_tensor(a) and a.dim() == 3 and a.is_cuda for a in self._alpha)):
+            return None
+        faces, fso, sf = self._hip_topology()
+        V, A, Sc = self._hip_flat_inputs()
+        if Sc.numel() != A.shape[0] or sf.numel() != A.shape[0]:
+            return None
+        return V, faces, A, Sc, 0, sf, fso
+
     def _hip_run(self):
         faces, fso, sf = self._hip_topology()
-        V = torch.cat(list(self.vertices))
-        A = torch.cat([a.reshape(-1, 3) for a in self._alpha])
-        Sc = torch.cat(list(self._scale))
+        V, A, Sc = self._hip_flat_inputs()
         opa = getattr(self, "_opacity", None)
         fuse_opacity = torch.is_tensor(opa) and opa.is_cuda and opa.numel() == Sc.numel()
         out = mesh_to_gaussians(V, faces, A, Sc, "relu", face_splat_offset=fso, splat_face=sf, fused_activations=True,
@@ -341,7 +422,7 @@ class HipMultiMeshMixin(_HipGetters):
         d.geometry = _Stamp(tuple(out[2:6]), *self._hip_inputs())
         return out[0], out[1]
 
-    def update_alpha(self):
+    def _hip_derive(self):
         alpha, xyz = self._hip_run()
         sizes = [a.shape[0] * a.shape[1] for a in self._alpha]
         self.alpha = [x.reshape(a.shape) for x, a in zip(torch.split(alpha, sizes), self._alpha)]
@@ -351,6 +432,8 @@ class HipMultiMeshMixin(_HipGetters):
         self.update_alpha()
 
     def prepare_scaling_rot(self, *unused):
+        if self._hip.pending and self._hip_defer_now():
+            return
         derived = _current(self._hip.geometry, *self._hip_inputs())
         if derived is None:
             self._hip_run()
@@ -568,16 +651,67 @@ class HipGaussianMultiMeshModel(HipMultiMeshMixin, _StandaloneBase):
         m = cls(3)
         m.active_sh_degree = scenes[0].active_sh_degree
         par = lambda t: nn.Parameter(t.to(device).float().contiguous())
-        m.vertices = [par(s.vertices) for s in scenes]
+        m._hip_own_lists([s.vertices for s in scenes], [s._alpha for s in scenes], [s._scale for s in scenes], device)
         m.faces = [s.faces.to(device) for s in scenes]
-        m._alpha = [par(s._alpha) for s in scenes]
-        m._scale = [par(s._scale) for s in scenes]
         m._opacity = par(torch.cat([s._opacity for s in scenes]))
         m._features_dc = par(torch.cat([s._features_dc for s in scenes]))
         m._features_rest = par(torch.cat([s._features_rest for s in scenes]))
         m.update_alpha()
         m.prepare_scaling_rot()
         return m
+
+    def _hip_own_lists(self, vertices, alpha, scale, device):
+        """The three list families as slices of one flat buffer each ([sum V,3], [P,3], [P,1]): the lists keep the reference's shapes
+        and stay leaves with their own `.grad`, and no frame concatenates them (HipMultiMeshMixin._hip_flat)."""
+        store = {}
+        store["vertices"], self.vertices = _flat_with_slices(vertices, device)
+        store["_alpha"], self._alpha = _flat_with_slices(alpha, device)
+        store["_scale"], self._scale = _flat_with_slices(scale, device)
+        self._hip_flat_store = store
+        self.__dict__.pop("_hip_derived", None)
+
+    def create_from_pcd(self, pcds, spatial_lr_scale: float = 1.0, device="cuda"):
+        """gaussian_multi_mesh_model.py:47-89 from a list of MeshPointCloud (games_hip.io_mesh.multi_mesh_point_clouds): per mesh
+        `_alpha` and `_scale` = 1; over the concatenation opacity 0.1, the colours in the SH constant term, zero higher SH."""
+        import math
+        import numpy as np
+        self.point_cloud = list(pcds)
+        self.spatial_lr_scale = spatial_lr_scale
+        par = lambda a: nn.Parameter(a.contiguous().requires_grad_(True))
+        P = sum(int(p.points.shape[0]) for p in self.point_cloud)
+        colors = torch.cat([torch.tensor(np.asarray(p.colors)).float() for p in self.point_cloud]).to(device)
+        features = torch.zeros((P, 3, (self.max_sh_degree + 1) ** 2), device=device)
+        features[:, :3, 0] = (colors - 0.5) / 0.28209479177387814      # RGB2SH
+        self._hip_own_lists([torch.as_tensor(np.asarray(p.vertices)) for p in self.point_cloud], [p.alpha for p in self.point_cloud],
+                            [torch.ones((int(p.points.shape[0]), 1)) for p in self.point_cloud], device)
+        self.faces = [torch.as_tensor(np.asarray(p.faces)).long().to(device) for p in self.point_cloud]
+        self._opacity = par(torch.full((P, 1), math.log(0.1 / 0.9), device=device))
+        self._features_dc = par(features[:, :, 0:1].transpose(1, 2))
+        self._features_rest = par(features[:, :, 1:].transpose(1, 2))
+        self.max_radii2D = torch.zeros((P,), device=device)
+        self.update_alpha()
+        self.prepare_scaling_rot()
+
+    # ---- checkpoints: point_cloud.ply + model_params.pt with the reference's five keys, each a list per mesh
+    # (gaussian_multi_mesh_model.py:222-256)
+    def save_ply(self, path):
+        self._save_point_cloud(path)
+        own = lambda ts: [t.detach().clone() for t in ts]          # (a slice would drag its whole flat buffer into the file)
+        torch.save({"_alpha": own(self._alpha), "_scale": own(self._scale), "point_cloud": [None] * len(self.vertices),
+                    "vertices": own(self.vertices), "faces": list(self.faces)}, path.replace("point_cloud.ply", "model_params.pt"))
+
+    def load_ply(self, path, device="cuda"):
+        pc = self._load_point_cloud(path, device)
+        par = lambda a: nn.Parameter(a.requires_grad_(True))
+        self._features_dc = par(pc["features_dc"])
+        self._features_rest = par(pc["features_rest"])
+        self._opacity = par(pc["opacity"])
+        params = torch.load(path.replace("point_cloud.ply", "model_params.pt"), map_location=device, weights_only=False)
+        self._hip_own_lists(params["vertices"], params["_alpha"], params["_scale"], device)
+        self.faces = [f.to(device) for f in params["faces"]]
+        self.active_sh_degree = self.max_sh_degree
+        self.update_alpha()
+        self.prepare_scaling_rot()
 
     def parameters(self):
         return [*self.vertices, *self._alpha, self._features_dc, self._features_rest, self._opacity, *self._scale]

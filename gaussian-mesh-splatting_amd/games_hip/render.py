@@ -114,38 +114,46 @@ def _mesh_sizes_ok(pc) -> bool:
     return torch.is_tensor(op) and op.numel() == P and torch.is_tensor(sc) and sc.numel() == P
 
 
-def _fused_training_ok(pc, pipe, override_color) -> bool:
-    """Can this DIFFERENTIATED frame be rendered straight from the mesh (games_hip.model.HipMeshMixin.hip_defer_k0)?  The model
-    deferred its K0 (update_alpha() since the last optimizer step, nothing has asked for the derived values with a graph), uniform
-    splats per face, split degree-3 SH STORAGE (any active degree), the rasterizer's native SH / cov3D stages."""
-    return (getattr(pc, "hip_k0_pending", False) and torch.is_grad_enabled()
-            and _native_route("render_mesh", "GMS_TRAIN_FUSED", pc, pipe, override_color) and _mesh_sizes_ok(pc)
-            and 0 <= int(pc.active_sh_degree) <= 3 and pc._features_dc.shape[0] == pc._opacity.numel()
-            and torch.is_tensor(getattr(pc, "faces", None)))
+def _fused_training_inputs(pc, pipe, override_color):
+    """The mesh inputs of this DIFFERENTIATED frame if it can be rendered straight from the mesh (hip_defer_k0 of
+    games_hip.model.HipMeshMixin / HipMultiMeshMixin), else None.  The model deferred its K0 (update_alpha() since the last optimizer
+    step, nothing has asked for the derived values with a graph), any number of splats per face or the CSR tables of a multi-mesh
+    model, split degree-3 SH STORAGE (any active degree), the rasterizer's native SH / cov3D stages."""
+    if not (getattr(pc, "hip_k0_pending", False) and torch.is_grad_enabled() and hasattr(pc, "_hip_frame_inputs")
+            and _native_route("render_mesh", "GMS_TRAIN_FUSED", pc, pipe, override_color) and 0 <= int(pc.active_sh_degree) <= 3):
+        return None
+    op = getattr(pc, "_opacity", None)
+    inputs = pc._hip_frame_inputs()
+    if inputs is None or not torch.is_tensor(op) or op.numel() != inputs[3].numel() or pc._features_dc.shape[0] != op.numel():
+        return None
+    return inputs
 
 
-def _render_training_frame_from_mesh(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
+def _render_training_frame_from_mesh(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, inputs):
     """train.py:100 on a model whose K0 is deferred: ONE C++ autograd node from (vertices, _alpha, _scale, _opacity, SH) to the image
-    (`_C.render_mesh`; GmsRasterForwardArgs.mesh + mesh_out_*).  Same image and gradients as the two-node graph (tests/test_gpu_fused_training.py)."""
-    vertices, faces, _alpha, _scale = pc._hip_inputs()
+    (`_C.render_mesh`; GmsRasterForwardArgs.mesh + mesh_out_*).  Same image and gradients as the two-node graph
+    (tests/test_gpu_fused_training.py, tests/test_gpu_multi_mesh_training.py).  `inputs`: _fused_training_inputs()."""
+    vertices, faces, _alpha, _scale, spf, splat_face, face_splat_offset = inputs
     if faces.dtype != torch.int64 or not faces.is_contiguous():
         faces = faces.long().contiguous()
-    screenspace_points = _zero_points(_alpha.device, (int(_alpha.shape[0] * _alpha.shape[1]), 3))
+    screenspace_points = _zero_points(_alpha.device, (int(_scale.numel()), 3))
     H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
     image, radii, invdepth, xyz, scaling_act, rotation_unit, opacity_act, visible = dgr._C.render_mesh(
         vertices, faces, _alpha, _scale, pc._opacity, pc._features_dc, pc._features_rest, screenspace_points,
-        ALPHA_MODES[getattr(pc, "alpha_mode", "relu")], int(_alpha.shape[1]), dgr._empty(_alpha.device), bg_color,
+        ALPHA_MODES[getattr(pc, "alpha_mode", "relu")], spf, dgr._empty(_alpha.device) if splat_face is None else splat_face, bg_color,
         viewpoint_camera.world_view_transform, viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W,
         math.tan(viewpoint_camera.FoVx * 0.5), math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing),
-        bool(pipe.debug), int(pc.active_sh_degree))          # (the ACTIVE degree: train.py:86-87 raises it every 1 000 iterations)
+        bool(pipe.debug), int(pc.active_sh_degree),          # (the ACTIVE degree: train.py:86-87 raises it every 1 000 iterations)
+        face_splat_offset)
     pc._hip_fused_frame(xyz, scaling_act, rotation_unit, opacity_act)
     # (`visibility_filter` = radii > 0 comes out of the preprocess kernel, as on the two-node route: no elementwise launch)
     return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": visible, "radii": radii, "depth": invdepth}
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None):
-    if _fused_training_ok(pc, pipe, override_color):
-        return _render_training_frame_from_mesh(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
+    inputs = _fused_training_inputs(pc, pipe, override_color)
+    if inputs is not None:
+        return _render_training_frame_from_mesh(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, inputs)
     xyz = pc.get_xyz
     # the reference writes `torch.zeros_like(...) + 0` and retain_grad() (renderer/gaussian_renderer/__init__.py:33-37): a
     # 3.6 MB fill + an elementwise kernel per render for a tensor whose VALUES nobody reads (the rasterizer only hands a
@@ -202,11 +210,21 @@ def render_mesh_frame(vertices: torch.Tensor, faces: torch.Tensor, viewpoint_cam
     Side effects differ from the unfused route ON PURPOSE (the frame materialises no per-Gaussian tensor): `pc._scaling` / `pc._rotation`
     / `pc._xyz` keep the values of the last `prepare_scaling_rot()` (the undeformed mesh), and `viewspace_points` is None -- a
     forward-only frame has no screen-space gradient to receive.  Code that saves or inspects the DEFORMED Gaussians after a frame
-    calls `render_animated` with `GMS_ANIMATE_FUSED=0` (or assigns `pc.triangles` and calls `prepare_scaling_rot()`)."""
+    calls `render_animated` with `GMS_ANIMATE_FUSED=0` (or assigns `pc.triangles` and calls `prepare_scaling_rot()`).
+    A multi-mesh model (games_hip.model.HipMultiMeshMixin) takes a LIST of per-mesh vertices, in the model's order -- one mesh moved
+    against the others, say; `faces` is then ignored (the model's concatenated faces and splat table are used)."""
     H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
+    if isinstance(vertices, (list, tuple)):
+        with torch.no_grad():
+            _, faces, _alpha, _scale, spf, splat_face, _ = pc._hip_frame_inputs()
+            vertices = torch.cat([v.reshape(-1, 3).float() for v in vertices])
+        if vertices.shape[0] != sum(int(v.shape[0]) for v in pc.vertices):
+            raise RuntimeError("render_mesh_frame: the per-mesh vertices do not have the model's vertex counts")
+    else:
+        _alpha, _scale, spf, splat_face = pc._alpha, getattr(pc, getattr(pc, "_hip_scale_attr", "_scale")), int(pc._alpha.shape[1]), None
     color, radii, invdepth, visible = dgr._C.render_mesh_forward(
-        vertices.float(), faces, pc._alpha, getattr(pc, getattr(pc, "_hip_scale_attr", "_scale")), pc._opacity, ALPHA_MODES[getattr(pc, "alpha_mode", "relu")], int(pc._alpha.shape[1]),
-        dgr._empty(vertices.device), pc._features_dc, pc._features_rest, bg_color, viewpoint_camera.world_view_transform,
+        vertices.float(), faces, _alpha, _scale, pc._opacity, ALPHA_MODES[getattr(pc, "alpha_mode", "relu")], spf,
+        dgr._empty(vertices.device) if splat_face is None else splat_face, pc._features_dc, pc._features_rest, bg_color, viewpoint_camera.world_view_transform,
         viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W, math.tan(viewpoint_camera.FoVx * 0.5),
         math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing), bool(pipe.debug))
     return {"render": color, "viewspace_points": None, "visibility_filter": visible, "radii": radii, "depth": invdepth}

@@ -241,9 +241,12 @@ typedef struct GmsRasterBackwardArgs {
      * parameterization itself: dL/d_alpha, dL/d_scale, dL/d_opacity are stored, its share of the face's corner gradients is added to
      * mesh_dL_dvertices (which must be ALL ZERO on entry: GmsMeshArgs.prezero of the forward) -- the arithmetic of
      * gms_mesh_to_gaussians_backward with fused_activations, without the 44 bytes per Gaussian in between and without its launch.
-     * dL_dmeans3D / dL_dscales / dL_drotations / dL_dopacity are then NOT written (may be NULL).  Uniform splats per face, at most 4 (every
-     * splat adds to its face's three corners); not in deterministic mode (which sums corner gradients in a fixed order: use
-     * gms_mesh_to_gaussians_backward). */
+     * dL_dmeans3D / dL_dscales / dL_drotations / dL_dopacity are then NOT written (may be NULL).  Any splat table is accepted (still ABI 10:
+     * additive): splats_per_face 1 .. 4 runs in preprocess_bwd_kernel<true>, whose tail sums a face's splats over runs of at most four
+     * lanes; splats_per_face > 4, or 0 with `splat_face` [P] (`face_splat_offset` is not read), runs in preprocess_bwd_kernel<true, MeshRuns>,
+     * which reduces the nine corner sums of a face over runs of ANY length with a segmented suffix sum (a run = consecutive lanes of a
+     * wave with the same face id; one set of atomics per run).  Both are accounted under GMS_K_PREPROCESS_BWD.  Not in deterministic mode
+     * (which sums corner gradients in a fixed order: use gms_mesh_to_gaussians_backward). */
     const struct GmsMeshArgs *mesh;
     float *mesh_dL_dvertices;         /* [V,3], zero on entry, accumulated with float atomics */
     float *mesh_dL_dalpha;            /* [P,3] */
@@ -284,7 +287,8 @@ typedef struct GmsMeshArgs {
     int32_t F;                    /* faces (all meshes concatenated) */
     int32_t V;                    /* vertices */
     int64_t P;                    /* Gaussians = sum of splats over faces */
-    int32_t splats_per_face;      /* >0: uniform S (P == F*S); 0: use face_splat_offset / splat_face */
+    int32_t splats_per_face;      /* >0: uniform S (P == F*S); 0: use face_splat_offset / splat_face (the per-splat readers --
+                                     the rasterizer's forward and backward with `mesh` -- need `splat_face` alone) */
     int32_t alpha_mode;
     const float *vertices;        /* [V,3] */
     const int64_t *faces;         /* [F,3] vertex indices (int64, as the reference stores them) */
