@@ -1031,6 +1031,39 @@ std::tuple<Tensor, int64_t> ground_truth_u8(const Tensor &src, bool white_backgr
     return {out, (int64_t)launches};
 }
 
+// ---------------------------------------------------------------------------------------------- Pillow's resize to the ground truth (csrc/resize.hip)
+// src uint8 [B,H,W,C] (C 3 or 4) on the device -> (float32 [B,3,out_h,out_w], launches made); the tables as for ground_truth_u8.
+std::tuple<Tensor, int64_t> resize_u8(const Tensor &src, int64_t out_h, int64_t out_w, const Tensor &h_bounds, const Tensor &h_coeffs,
+                                      const Tensor &v_bounds, const Tensor &v_coeffs)
+{
+    require_gpu(src);
+    TORCH_CHECK(src.dim() == 4 && src.scalar_type() == torch::kUInt8 && src.is_contiguous() && src.is_cuda(),
+                "resize_u8: src must be a contiguous uint8 [B,H,W,C] device tensor");
+    const int64_t B = src.size(0), h = src.size(1), w = src.size(2), Cn = src.size(3);
+    TORCH_CHECK(B <= INT32_MAX && h <= INT32_MAX && w <= INT32_MAX && out_h <= INT32_MAX && out_w <= INT32_MAX && out_h > 0 && out_w > 0,
+                "resize_u8: sizes out of range");
+    auto table = [&](const Tensor &bounds, const Tensor &coeffs, int64_t n_out, const char *axis) -> int32_t {
+        TORCH_CHECK(bounds.scalar_type() == torch::kInt && coeffs.scalar_type() == torch::kInt && bounds.is_contiguous() && coeffs.is_contiguous() &&
+                    bounds.device() == src.device() && coeffs.device() == src.device() && bounds.dim() == 2 && coeffs.dim() == 2 &&
+                    bounds.size(0) == n_out && bounds.size(1) == 2 && coeffs.size(0) == n_out && coeffs.size(1) >= 1 && coeffs.size(1) <= INT32_MAX,
+                    "resize_u8: the ", axis, " tables must be contiguous int32 [n_out,2] and [n_out,kmax] on src's device");
+        return (int32_t)coeffs.size(1);
+    };
+    const int32_t hk = out_w != w ? table(h_bounds, h_coeffs, out_w, "horizontal") : 0;
+    const int32_t vk = out_h != h ? table(v_bounds, v_coeffs, out_h, "vertical") : 0;
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(src.device());
+    TORCH_CHECK(src.numel() > 0, "resize_u8: empty batch or image");
+    Tensor out = torch::empty({B, 3, out_h, out_w}, torch::TensorOptions().dtype(torch::kFloat).device(src.device()));
+    const size_t bytes = gms_resize_workspace_bytes((int32_t)B, (int32_t)h, (int32_t)w, (int32_t)Cn, (int32_t)out_h, (int32_t)out_w);
+    Tensor work = torch::empty({(int64_t)bytes}, torch::TensorOptions().dtype(torch::kUInt8).device(src.device()));
+    GmsResizeArgs a{(int32_t)B, (int32_t)h, (int32_t)w, (int32_t)Cn, src.data_ptr<uint8_t>(), (int32_t)out_h, (int32_t)out_w,
+                    hk ? h_bounds.data_ptr<int32_t>() : nullptr, hk ? h_coeffs.data_ptr<int32_t>() : nullptr, hk,
+                    vk ? v_bounds.data_ptr<int32_t>() : nullptr, vk ? v_coeffs.data_ptr<int32_t>() : nullptr, vk, out.data_ptr<float>()};
+    const int32_t launches = gms_resize_u8(&a, work.data_ptr(), bytes, stream_of(src));
+    check_rc(launches, "gms_resize_u8");
+    return {out, (int64_t)launches};
+}
+
 // ---------------------------------------------------------------------------------------------- pseudo-mesh bound to a guide mesh
 // (scripts/edit_pseudomesh_based_on_estimated_mesh.py; csrc/bind.hip)
 struct Guide { Tensor vertices, faces; int32_t V, F; };
@@ -1439,6 +1472,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("image_metrics", &image_metrics, "evaluation sums of image pairs into rows of a device table: (img_u8, gt_u8) or two empty tensors; launches only", nogil());
     m.def("ground_truth_u8", &ground_truth_u8, "decoded bytes [B,H,W,C] -> (ground truth float32 [B,3,out_h,out_w], launches made): composite, Pillow's "
           "8-bit bicubic resize, byte / 255; launches only", nogil());
+    m.def("resize_u8", &resize_u8, "decoded bytes [B,H,W,C] -> (ground truth float32 [B,3,out_h,out_w], launches made): Pillow's 8-bit bicubic "
+          "resize (premultiplied for RGBA, alpha dropped), byte / 255, nothing composited; launches only", nogil());
+    m.def("resize_tile_columns", [](int64_t w, int64_t ow) { return (int64_t)gms_resize_tile_columns((int32_t)w, (int32_t)ow); },
+          "output columns of a horizontal tile (64 or 32) for this width change, 0: the one-output-per-thread kernel");
     m.def("adam_step", &adam_step, nogil());
     m.def("set_scratch_fill", &set_scratch_fill, "fill every scratch buffer with this byte before the library writes into it; -1: off (diagnostics only)");
     m.def("set_keep_buffers", &set_keep_buffers, "keep references to the last forward's scratch tensors (diagnostics only)");

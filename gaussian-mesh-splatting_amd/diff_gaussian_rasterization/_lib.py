@@ -110,6 +110,16 @@ class GroundTruthArgs(C.Structure):
     ]
 
 
+class ResizeArgs(C.Structure):
+    """GmsResizeArgs (include/gmsplat.h)."""
+    _fields_ = [
+        ("images", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("src", C.c_void_p),
+        ("out_height", C.c_int32), ("out_width", C.c_int32),
+        ("h_bounds", C.c_void_p), ("h_coeffs", C.c_void_p), ("h_kmax", C.c_int32),
+        ("v_bounds", C.c_void_p), ("v_coeffs", C.c_void_p), ("v_kmax", C.c_int32), ("out", C.c_void_p),
+    ]
+
+
 class ShGradExpandArgs(C.Structure):
     """GmsShGradExpandArgs (include/gmsplat.h)."""
     _fields_ = [
@@ -184,6 +194,7 @@ EXPORTS = (
     "gms_densify_stats", "gms_densify_plan_workspace_bytes", "gms_densify_plan", "gms_densify_apply",
     "gms_image_metrics_workspace_bytes", "gms_image_metrics",
     "gms_ground_truth_workspace_bytes", "gms_ground_truth_u8",
+    "gms_resize_workspace_bytes", "gms_resize_tile_columns", "gms_resize_u8",
 )
 K_COUNT = 23
 
@@ -269,6 +280,12 @@ def load():
         lib.gms_ground_truth_workspace_bytes.argtypes = [C.c_int32] * 5
         lib.gms_ground_truth_u8.restype = C.c_int32
         lib.gms_ground_truth_u8.argtypes = [C.POINTER(GroundTruthArgs), C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.gms_resize_workspace_bytes.restype = C.c_size_t
+        lib.gms_resize_workspace_bytes.argtypes = [C.c_int32] * 6
+        lib.gms_resize_tile_columns.restype = C.c_int32
+        lib.gms_resize_tile_columns.argtypes = [C.c_int32] * 2
+        lib.gms_resize_u8.restype = C.c_int32
+        lib.gms_resize_u8.argtypes = [C.POINTER(ResizeArgs), C.c_void_p, C.c_size_t, C.c_void_p]
         lib.gms_l1_ssim_partials.restype = C.c_size_t
         lib.gms_l1_ssim_partials.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         lib.gms_l1_ssim_forward.restype = C.c_int32

@@ -1,4 +1,5 @@
-"""Blender-format (NeRF-synthetic) datasets: a directory -> cameras with ground truth on the GPU (csrc/images.hip).
+"""Datasets: a Blender-format (NeRF-synthetic) or COLMAP directory -> cameras with ground truth on the GPU (csrc/images.hip, DESIGN.md
+section 15; csrc/resize.hip, section 17; the COLMAP readers are games_hip/colmap.py).
 
 What the reference's `Scene` does for a `transforms_train.json` directory (scene/__init__.py:50-105), for gs, gs_flat and gs_mesh:
 
@@ -16,7 +17,10 @@ at a time on the CPU.  Here the CPU keeps the PNG decode (a fixed pool of 8 thre
 images are uploaded asynchronously and `ground_truth_u8` turns each chunk into float32 [B,3,H,W] in one call: one launch at native
 resolution, at most three with a resize.  Bytes and floats are the reference's exactly (tests/test_gpu_ground_truth.py).
 
-Host-side parsing is numpy; `PIL` is imported lazily and only to decode.  COLMAP directories, gs_flame and gs_multi_mesh are not read."""
+A COLMAP image is not composited (scene/dataset_readers.py:68-105 hands the file to `loadCam` as it is): `resize_u8` takes its bytes
+straight to the floats, on Pillow's premultiplied route when the file is RGBA.
+
+Host-side parsing is numpy; `PIL` is imported lazily and only to decode.  gs_flame directories and gs_mesh on a COLMAP model are not read."""
 from __future__ import annotations
 
 import ctypes as C
@@ -45,7 +49,9 @@ last_launches = 0                   # kernel launches the most recent ground_tru
 
 # ------------------------------------------------------------------------------------------------ camera records
 class CameraInfo(NamedTuple):
-    """scene/dataset_readers.py:26-36 without the decoded image; `channels`: 3 for an RGB file, 4 for anything else (read as RGBA)."""
+    """scene/dataset_readers.py:26-36 without the decoded image; `channels`: 3 for an RGB file, 4 for anything else (read as RGBA).
+    A COLMAP record (`colmap`) keeps the intrinsics' size in `width` and `height`, as the reference does, and the file's own in
+    `image_width` and `image_height`: the resize target comes from the file."""
     uid: int
     R: np.ndarray
     T: np.ndarray
@@ -56,6 +62,9 @@ class CameraInfo(NamedTuple):
     width: int
     height: int
     channels: int = 4
+    image_width: int = 0
+    image_height: int = 0
+    colmap: bool = False
 
 
 class BasicPointCloud(NamedTuple):
@@ -269,6 +278,40 @@ def resample_numpy(img: np.ndarray, out_w: int, out_h: int) -> np.ndarray:
     return np.ascontiguousarray(img)
 
 
+def premultiply_numpy(img: np.ndarray) -> np.ndarray:
+    """Pillow's RGBA -> RGBa (src/libImaging/Convert.c, MULDIV255): t = c * a + 128; ((t >> 8) + t) >> 8; alpha kept."""
+    out = img.copy()
+    t = img[:, :, :3].astype(np.int64) * img[:, :, 3:4].astype(np.int64) + 128
+    out[:, :, :3] = ((t >> 8) + t) >> 8
+    return out
+
+
+def unpremultiply_numpy(img: np.ndarray) -> np.ndarray:
+    """Pillow's RGBa -> RGBA: the colour itself where alpha is 0 or 255, else min(255, 255 * c // a); alpha kept."""
+    out = img.copy()
+    a = img[:, :, 3:4].astype(np.int64)
+    q = np.minimum(255, (255 * img[:, :, :3].astype(np.int64)) // np.maximum(a, 1))
+    out[:, :, :3] = np.where((a == 0) | (a == 255), img[:, :, :3], q)
+    return out
+
+
+def resize_numpy(img: np.ndarray, out_w: int, out_h: int) -> np.ndarray:
+    """`Image.resize((out_w, out_h))` of an RGB or RGBA image on the host, uint8 [H,W,C] -> [out_h,out_w,C]: a copy at an unchanged
+    size; RGBA through the premultiplied form, all four channels resampled.  What csrc/resize.hip computes, for tests and tools."""
+    if (out_w, out_h) == (img.shape[1], img.shape[0]):
+        return img.copy()
+    if img.shape[2] == 4:
+        return unpremultiply_numpy(resample_numpy(premultiply_numpy(img), out_w, out_h))
+    return resample_numpy(img, out_w, out_h)
+
+
+def colmap_ground_truth_numpy(img: np.ndarray, out_w: int, out_h: int) -> np.ndarray:
+    """float32 [3,out_h,out_w]: `Camera.original_image` of the reference for a COLMAP image (utils/camera_utils.py:41-52 with
+    utils/general_utils.py:101-107): the resized bytes over 255; of an RGBA image the three colours, the alpha mask never applied
+    (`shape[1] == 4` there tests the height)."""
+    return np.ascontiguousarray(resize_numpy(img, out_w, out_h)[:, :, :3].transpose(2, 0, 1)).astype(np.float32) / np.float32(255.0)
+
+
 def composite_table(white_background: bool) -> np.ndarray:
     """uint8 [256 (c), 256 (a)]: the reference's statement (dataset_readers.py:206-210) on every (colour, alpha) pair, in float64."""
     unit = np.arange(256, dtype=np.uint8) / 255.0            # byte / 255.0 in float64, as numpy divides a uint8 array
@@ -320,6 +363,40 @@ def ground_truth_u8(src: torch.Tensor, white_background: bool, size: Optional[Tu
                                     v_bounds=_lib.ptr(vb), v_coeffs=_lib.ptr(vc), v_kmax=int(vc.shape[1]) if oh != h else 0, out=_lib.ptr(out))
         rc = lib.gms_ground_truth_u8(C.byref(args), work.data_ptr(), nbytes, C.c_void_p(_lib.stream_ptr(src.device)))
     last_launches = _lib.check(rc, "gms_ground_truth_u8")
+    return out
+
+
+def resize_u8(src: torch.Tensor, size: Optional[Tuple[int, int]] = None, tables: Optional[dict] = None) -> torch.Tensor:
+    """uint8 [B,H,W,C] (C 3 or 4) on the GPU -> float32 [B,3,out_h,out_w]: Pillow's bicubic resize to `size` = (width, height) and
+    byte / 255, nothing composited (csrc/resize.hip): the ground truth of COLMAP images.  RGBA takes the premultiplied route and
+    loses its alpha.  One launch per axis that changes, one at an unchanged size; `last_launches` holds how many.  `tables` as for
+    ground_truth_u8."""
+    global last_launches
+    import diff_gaussian_rasterization as _dgr
+    from diff_gaussian_rasterization import _lib
+    if not src.is_cuda:
+        raise RuntimeError("resize_u8: the images must live on a GPU (there is no CPU path in the product)")
+    if src.dim() != 4 or src.dtype != torch.uint8:
+        raise ValueError("resize_u8: src must be uint8 [B,H,W,C]")
+    src = src.contiguous()
+    b, h, w, c = (int(v) for v in src.shape)
+    ow, oh = (int(size[0]), int(size[1])) if size is not None else (w, h)
+    empty = torch.empty((0, 2), dtype=torch.int32, device=src.device)
+    hb, hc = _tables_on(src.device, w, ow, tables) if ow != w else (empty, empty)
+    vb, vc = _tables_on(src.device, h, oh, tables) if oh != h else (empty, empty)
+    if _dgr._C is not None:
+        out, last_launches = _dgr._C.resize_u8(src, oh, ow, hb, hc, vb, vc)
+        return out
+    lib = _lib.load()
+    with _lib.on_device(src.device):
+        out = torch.empty((b, 3, oh, ow), dtype=torch.float32, device=src.device)
+        nbytes = lib.gms_resize_workspace_bytes(b, h, w, c, oh, ow)
+        work = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+        args = _lib.ResizeArgs(images=b, height=h, width=w, channels=c, src=_lib.ptr(src), out_height=oh, out_width=ow,
+                               h_bounds=_lib.ptr(hb), h_coeffs=_lib.ptr(hc), h_kmax=int(hc.shape[1]) if ow != w else 0,
+                               v_bounds=_lib.ptr(vb), v_coeffs=_lib.ptr(vc), v_kmax=int(vc.shape[1]) if oh != h else 0, out=_lib.ptr(out))
+        rc = lib.gms_resize_u8(C.byref(args), work.data_ptr(), nbytes, C.c_void_p(_lib.stream_ptr(src.device)))
+    last_launches = _lib.check(rc, "gms_resize_u8")
     return out
 
 
@@ -382,22 +459,37 @@ def pack_camera_tensors(R, T, FoVx, FoVy, znear=0.01, zfar=100.0, trans=np.array
     return row
 
 
+def _file_size(info: CameraInfo) -> Tuple[int, int]:
+    """(width, height) of the record's image file: a COLMAP record's intrinsics may describe another size (`--images images_4`)."""
+    return (info.image_width, info.image_height) if info.colmap else (info.width, info.height)
+
+
 def _decode_into(info: CameraInfo, slot: np.ndarray) -> None:
     from PIL import Image
     with Image.open(info.image_path) as image:
         if image.mode != ("RGB" if info.channels == 3 else "RGBA"):
+            if info.colmap:
+                raise ValueError(f"{info.image_path}: mode {image.mode!r} now, {info.channels} channels when the COLMAP model was read")
             image = image.convert("RGBA")            # (dataset_readers.py:204 converts every image)
-        if image.size != (info.width, info.height):
-            raise ValueError(f"{info.image_path}: {image.size} now, {(info.width, info.height)} when the transforms were read")
+        if image.size != _file_size(info):
+            raise ValueError(f"{info.image_path}: {image.size} now, {_file_size(info)} when the scene was read")
         slot[...] = np.asarray(image)
+
+
+MASK_CORNER = ("{path}: an RGBA image resized to a height of exactly 4 is the one case in which the reference applies the alpha mask "
+               "(utils/camera_utils.py:44 tests `shape[1] == 4` on a [C,H,W] tensor, which is the height); that corner is not reproduced")
 
 
 def load_cameras(cam_infos: Sequence[CameraInfo], white_background: bool, resolution=-1, resolution_scale: float = 1.0, device="cuda") -> List[Camera]:
     """`cameraList_from_camInfos` with the ground truth made on the device: cameras in the order of `cam_infos` (uid = position), each
-    `original_image` a [3,H,W] view of its chunk's output.  Waits for nothing but the decoder threads."""
+    `original_image` a [3,H,W] view of its chunk's output.  Waits for nothing but the decoder threads.  COLMAP records are not
+    composited: their chunks go through `resize_u8` (RGBA: the premultiplied resize, alpha dropped)."""
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("load_cameras: the ground truth is built by HIP kernels; device must be a GPU")
+    for c in cam_infos:         # refused before anything touches the device
+        if c.colmap and c.channels == 4 and target_resolution(*_file_size(c), resolution, resolution_scale)[1] == 4:
+            raise ValueError(MASK_CORNER.format(path=c.image_path))
     if device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
     n = len(cam_infos)
@@ -407,31 +499,40 @@ def load_cameras(cam_infos: Sequence[CameraInfo], white_background: bool, resolu
     # chunks of same-sized images, in order of first appearance
     groups = {}
     for i, c in enumerate(cam_infos):
-        groups.setdefault((c.height, c.width, c.channels), []).append(i)
+        w, h = _file_size(c)
+        groups.setdefault((h, w, c.channels, bool(c.colmap)), []).append(i)
     chunks = []
-    for (h, w, ch), idxs in groups.items():
+    for (h, w, ch, colmap), idxs in groups.items():
         per = min(max(1, CHUNK_BYTES // (h * w * ch)), MAX_IMAGES_PER_CALL)
-        chunks += [((h, w, ch), idxs[k:k + per]) for k in range(0, len(idxs), per)]
+        chunks += [((h, w, ch, colmap), idxs[k:k + per]) for k in range(0, len(idxs), per)]
     images: List[Optional[torch.Tensor]] = [None] * n
     tables = {}                                     # the resize tables of this call's sizes, on the device until it returns
 
     def finish(entry):
-        (h, w, ch), idxs, stage, futures = entry
+        (h, w, ch, colmap), idxs, stage, futures = entry
         for f in futures:
             f.result()
         size = target_resolution(w, h, resolution, resolution_scale)
-        out = ground_truth_u8(stage.to(device, non_blocking=True), white_background, size, tables)
+        if colmap:
+            out = resize_u8(stage.to(device, non_blocking=True), size, tables)
+        else:
+            out = ground_truth_u8(stage.to(device, non_blocking=True), white_background, size, tables)
         for j, i in enumerate(idxs):
             images[i] = out[j]
 
     pending = deque()
     with ThreadPoolExecutor(max_workers=DECODE_WORKERS) as pool:
-        for (h, w, ch), idxs in chunks:
+        for (h, w, ch, colmap), idxs in chunks:
             stage = torch.empty((len(idxs), h, w, ch), dtype=torch.uint8, pin_memory=True)
             slots = stage.numpy()
             futures = [pool.submit(_decode_into, cam_infos[i], slots[j]) for j, i in enumerate(idxs)]
-            pending.append(((h, w, ch), idxs, stage, futures))
-            if len(pending) > 1:                    # the next chunk decodes while this one uploads
+            pending.append(((h, w, ch, colmap), idxs, stage, futures))
+            # the next chunk decodes while this one uploads; chunks of few images (a 12-megapixel photograph is a chunk of its own) stay
+            # in flight until the chunks behind the oldest keep every decoder thread busy.  Chunks of DECODE_WORKERS images or more are
+            # finished as before (two in flight, 2 x CHUNK_BYTES pinned).  Smaller ones, of either format: the chunks behind the oldest
+            # hold fewer than DECODE_WORKERS + (a chunk's images) images when the loop stops, so at most DECODE_WORKERS + 1 chunks of one
+            # image each are pinned at once -- 9 x CHUNK_BYTES = 576 MiB in the worst case, about 450 MB for 12-megapixel RGB photographs
+            while len(pending) > 1 and sum(len(e[1]) for e in pending) - len(pending[0][1]) >= DECODE_WORKERS:
                 finish(pending.popleft())
         while pending:
             finish(pending.popleft())
@@ -451,31 +552,56 @@ class LoadedScene:
 
 
 def write_scene_files(scene_info: SceneInfo, model_path) -> None:
-    """scene/__init__.py:65-82: input.ply (a copy of the scene's point cloud file) and cameras.json (test cameras first, then train)."""
+    """scene/__init__.py:65-82: input.ply (a copy of the scene's point cloud file; input_<i>.ply per mesh when the scene holds a list
+    of them, as a gs_multi_mesh scene does) and cameras.json (test cameras first, then train)."""
     import shutil
     os.makedirs(model_path, exist_ok=True)
-    shutil.copyfile(scene_info.ply_path, os.path.join(model_path, "input.ply"))
+    if isinstance(scene_info.ply_path, (list, tuple)):
+        for i, ply_path in enumerate(scene_info.ply_path):
+            shutil.copyfile(ply_path, os.path.join(model_path, f"input_{i}.ply"))
+    else:
+        shutil.copyfile(scene_info.ply_path, os.path.join(model_path, "input.ply"))
     entries = [camera_json(k, info) for k, info in enumerate(list(scene_info.test_cameras) + list(scene_info.train_cameras))]
     with open(os.path.join(model_path, "cameras.json"), "w") as f:
         json.dump(entries, f)
 
 
 def load_scene(source_path, gs_type, *, white_background=False, eval=False, num_splats=2, resolution=-1, shuffle=True, model_path=None,
-               device="cuda") -> LoadedScene:
-    if gs_type in ("gs_flame", "gs_multi_mesh"):
-        raise NotImplementedError(f"load_scene: gs_type {gs_type!r} is not read (Blender_FLAME and multi-mesh scenes need their own readers); "
-                                  "gs, gs_flat and gs_mesh are")
-    if gs_type not in ("gs", "gs_flat", "gs_mesh"):
+               device="cuda", images=None, meshes=None) -> LoadedScene:
+    """scene/__init__.py:43-94.  A COLMAP model (sparse/0/images.bin or images.txt) is read for gs, gs_flat (read_colmap_scene) and
+    gs_multi_mesh (read_colmap_mesh_scene: `meshes` names the OBJ files under sparse/0, `num_splats` holds one count per mesh or one
+    for all); `images` names the image folder (default "images").  A transforms_train.json directory is read for gs, gs_flat and
+    gs_mesh."""
+    from . import colmap
+    if gs_type not in ("gs", "gs_flat", "gs_mesh", "gs_flame", "gs_multi_mesh"):
         raise ValueError(f"load_scene: unknown gs_type {gs_type!r}")
-    if os.path.exists(os.path.join(source_path, "sparse")):
-        raise NotImplementedError(f"{source_path}: a sparse/ directory is a COLMAP dataset; the COLMAP readers (images.bin / cameras.bin / "
-                                  "points3D.bin) are not implemented, only Blender-format transforms_train.json directories are read")
-    if not os.path.exists(os.path.join(source_path, "transforms_train.json")):
-        raise FileNotFoundError(f"{source_path}: no transforms_train.json; could not recognize scene type")
-    if gs_type == "gs_mesh":
-        scene_info = read_blender_mesh_scene(source_path, white_background, eval, num_splats)
+    if colmap.has_model(source_path):
+        if gs_type == "gs_multi_mesh":
+            if not meshes:
+                raise ValueError("load_scene: a gs_multi_mesh scene needs `meshes`, the names of the OBJ files under sparse/0")
+            counts = [int(num_splats)] * len(meshes) if isinstance(num_splats, int) else [int(n) for n in num_splats]
+            if len(counts) != len(meshes):
+                raise ValueError(f"load_scene: {len(meshes)} meshes, {len(counts)} splat counts")
+            scene_info = colmap.read_colmap_mesh_scene(source_path, images, eval, counts, meshes)
+        elif gs_type in ("gs", "gs_flat"):
+            scene_info = colmap.read_colmap_scene(source_path, images, eval)
+        else:
+            raise NotImplementedError(f"{source_path}: gs_type {gs_type!r} cannot be read from a COLMAP model (the reference has no COLMAP "
+                                      "reader for it); gs, gs_flat and gs_multi_mesh can")
     else:
-        scene_info = read_blender_scene(source_path, white_background, eval)
+        if gs_type in ("gs_flame", "gs_multi_mesh"):
+            raise NotImplementedError(f"load_scene: gs_type {gs_type!r} is not read from this directory (gs_multi_mesh needs a COLMAP model "
+                                      "under sparse/0, Blender_FLAME scenes their own reader); gs, gs_flat and gs_mesh are")
+        if os.path.exists(os.path.join(source_path, "sparse")):
+            looked = ", ".join("sparse/0/" + n for n in colmap.MODEL_FILES)
+            raise NotImplementedError(f"{source_path}: a sparse/ directory is a COLMAP dataset, but it holds no model that can be read "
+                                      f"(looked for {looked})")
+        if not os.path.exists(os.path.join(source_path, "transforms_train.json")):
+            raise FileNotFoundError(f"{source_path}: no transforms_train.json; could not recognize scene type")
+        if gs_type == "gs_mesh":
+            scene_info = read_blender_mesh_scene(source_path, white_background, eval, num_splats)
+        else:
+            scene_info = read_blender_scene(source_path, white_background, eval)
     if model_path is not None:
         write_scene_files(scene_info, model_path)
     if shuffle:         # train first, then test: the two draws a seeded reference run makes (scene/__init__.py:84-86)

@@ -579,6 +579,32 @@ typedef struct GmsGroundTruthArgs {
 size_t gms_ground_truth_workspace_bytes(int32_t images, int32_t height, int32_t width, int32_t out_height, int32_t out_width);
 int32_t gms_ground_truth_u8(const GmsGroundTruthArgs *args, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- Pillow's resize from interleaved bytes straight to the ground truth (csrc/resize.hip; additive to ABI 10) ------------------
+ * What the reference does to a COLMAP image (utils/camera_utils.py:19-52): `image.resize((out_width, out_height))` (8-bit bicubic)
+ * and (float) byte / 255.0f; nothing is composited.  channels == 4 takes Pillow's premultiplied route (RGBA -> RGBa, four channels
+ * resampled, RGBa -> RGBA) and the colours are kept, alpha dropped; at an unchanged size Pillow returns a copy and no premultiply
+ * round trip happens.  src: uint8 [images,height,width,channels] interleaved (4-byte aligned for channels == 4 when a size changes);
+ * out: float32 [images,3,out_height,out_width] planar, bit-equal to Pillow's bytes / 255.  The tables are those of
+ * gms_ground_truth_u8.  Launches: 1 at an unchanged size, 1 when one axis changes, 2 when both do (pixels [images,height,out_width]
+ * of four bytes each, for RGB too, pass through `workspace`, 16-byte aligned, at least gms_resize_workspace_bytes(...) bytes,
+ * read only then; NULL allowed otherwise).  No allocation, no host wait, no atomics, no profile id.
+ * The horizontal pass stages each tile's input span in LDS; gms_resize_tile_columns gives the output columns of a tile (64 or 32)
+ * for a width change, or 0 when no tile's span fits the LDS budget and the one-output-per-thread kernel runs instead.
+ * Returns the number of kernel launches made (1..2), or GMS_ERR_INVALID_ARGUMENT (null pointers, sizes <= 0, more than 65 535
+ * images, channels outside {3, 4}, missing tables of an axis that changes, a misaligned RGBA source or workspace);
+ * GMS_ERR_CAPACITY: workspace too small. */
+typedef struct GmsResizeArgs {
+    int32_t images, height, width, channels;
+    const uint8_t *src;                             /* [images,height,width,channels] */
+    int32_t out_height, out_width;
+    const int32_t *h_bounds, *h_coeffs; int32_t h_kmax;     /* [out_width][2], [out_width][h_kmax]; read when out_width != width */
+    const int32_t *v_bounds, *v_coeffs; int32_t v_kmax;     /* [out_height][2], [out_height][v_kmax]; read when out_height != height */
+    float *out;                                     /* [images,3,out_height,out_width] */
+} GmsResizeArgs;
+size_t gms_resize_workspace_bytes(int32_t images, int32_t height, int32_t width, int32_t channels, int32_t out_height, int32_t out_width);
+int32_t gms_resize_tile_columns(int32_t width, int32_t out_width);
+int32_t gms_resize_u8(const GmsResizeArgs *args, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- per-kernel timing (HIP events on the launch stream; off by default) ------------------
  * When enabled every kernel launch made by this library is bracketed by two hipEvents on the
  * caller's stream.  gms_profile_read() synchronises the recorded events and returns the summed
