@@ -331,3 +331,62 @@ class GraphedBoundAnimation(GraphedPointsAnimation):
         if vertices.dtype != torch.float32 or not vertices.is_contiguous():
             vertices = vertices.float().contiguous()
         return super().render(vertices, check)
+
+
+# ---------------------------------------------------------------------------------------------- gs_flame driven by its FLAME parameters
+class GraphedFlameAnimation(GraphedAnimation):
+    """GraphedAnimation for a gs_flame model (scripts/render_flame.py:29-60): the static input is ONE flat tensor holding the five FLAME
+    parameter tensors (shape, expression, pose, neck pose, translation, in that order; `pack` builds it), and the captured frame is
+    `HipFlameLayer.vertices` on views sliced off it (one launch, the model's transform function and `_vertices_enlargement` included)
+    followed by `render_mesh_frame` (K0 inside the preprocess thread).  A replay copies a few hundred floats.  The model's own five
+    FLAME parameters are neither read nor written.  Overflow / re-capture behaviour is GraphedAnimation's.
+
+        anim = GraphedFlameAnimation(gaussians, view, pipeline, background)
+        for k in range(n_frames):
+            img = anim.render(anim.pack(shape, expression[k], pose[k], neck[k], transl[k]), check=True)
+    """
+
+    def __init__(self, gaussians, view, pipeline, background: torch.Tensor, warmup: int = 3):
+        super().__init__(gaussians, view, pipeline, background, warmup)
+        from . import flame as _flame
+        from .model import _squeeze_and_enlarge
+        from .render import _mesh_sizes_ok, _native_route
+        cloud = gaussians.point_cloud
+        fn = cloud.transform_vertices_function
+        if not isinstance(cloud.flame_model, _flame.HipFlameLayer) or not (fn is _flame.transform_vertices_function or fn is _squeeze_and_enlarge):
+            raise NotImplementedError("GraphedFlameAnimation: the model's layer must be a games_hip.flame.HipFlameLayer with a transform "
+                                      "function the layer fuses (games_hip.flame.transform_vertices_function)")
+        if not (_native_route("render_mesh_forward", "GMS_ANIMATE_FUSED", gaussians, pipeline, None) and _mesh_sizes_ok(gaussians)
+                and int(gaussians.active_sh_degree) == 3):
+            raise NotImplementedError("GraphedFlameAnimation: the frame is rendered straight from the mesh, which needs the rasterizer's "
+                                      "native SH / cov3D stages, split SH storage at degree 3 and one splat count for all faces")
+        self.layer, self.swap = cloud.flame_model, fn is _flame.transform_vertices_function
+        self.sizes = [int(t.numel()) for t in (gaussians._flame_shape, gaussians._flame_exp, gaussians._flame_pose,
+                                               gaussians._flame_neck_pose, gaussians._flame_trans)]
+        self.faces = gaussians.faces.long().contiguous()
+
+    def pack(self, shape, expression, pose, neck_pose, transl) -> torch.Tensor:
+        """The flat float32 tensor `render` takes, from five tensors with the sizes of the model's parameters."""
+        parts = [t.detach().reshape(-1).float() for t in (shape, expression, pose, neck_pose, transl)]
+        if [int(t.numel()) for t in parts] != self.sizes:
+            raise ValueError(f"GraphedFlameAnimation: parameter sizes {[int(t.numel()) for t in parts]}, the model has {self.sizes}")
+        return torch.cat(parts)
+
+    def _frame(self, flat: torch.Tensor) -> dict:
+        views, at = [], 0
+        for n in self.sizes:
+            views.append(flat[at:at + n].view(1, n))
+            at += n
+        vertices = self.layer.vertices(*views, enlargement=self.pc._vertices_enlargement, swap=self.swap)
+        return render_mesh_frame(vertices, self.faces, self.view, self.pc, self.pipe, self.bg)
+
+    def render(self, params, check: bool = True) -> torch.Tensor:
+        """The frame for `params`: the flat tensor of `pack`, or the five tensors themselves (GraphedAnimation.render with the
+        parameters as the graph's static input)."""
+        if isinstance(params, (list, tuple)):
+            params = self.pack(*params)
+        if params.dim() != 1 or int(params.numel()) != sum(self.sizes):
+            raise ValueError(f"GraphedFlameAnimation: {tuple(params.shape)} values, the model's five parameter tensors hold {sum(self.sizes)}")
+        if params.dtype != torch.float32 or not params.is_contiguous():
+            params = params.float().contiguous()
+        return super().render(params, check)

@@ -7,6 +7,7 @@ What the reference's `Scene` does for a `transforms_train.json` directory (scene
     nerfpp_norm                    scene/dataset_readers.py:45-66
     read_blender_scene             scene/dataset_readers.py:221-255 (points3d.ply reused, or 100 000 random points)
     read_blender_mesh_scene        games/mesh_splatting/scene/dataset_readers.py:40-105 (mesh.obj -> MeshPointCloud)
+    read_blender_flame_scene       games/flame_splatting/scene/dataset_readers.py:48-130 (FLAME layer -> FLAMEPointCloud)
     target_resolution              utils/camera_utils.py:20-39
     Camera                         scene/cameras.py:17-57, the four matrices computed on the host by the reference's statements
     load_cameras                   utils/camera_utils.py:54-60 + the image work of all three files, on the device
@@ -20,7 +21,8 @@ resolution, at most three with a resize.  Bytes and floats are the reference's e
 A COLMAP image is not composited (scene/dataset_readers.py:68-105 hands the file to `loadCam` as it is): `resize_u8` takes its bytes
 straight to the floats, on Pillow's premultiplied route when the file is RGBA.
 
-Host-side parsing is numpy; `PIL` is imported lazily and only to decode.  gs_flame directories and gs_mesh on a COLMAP model are not read."""
+Host-side parsing is numpy; `PIL` is imported lazily and only to decode.  A gs_flame directory is read with the caller's FLAME
+layer (read_blender_flame_scene: the model file is licensed and not shipped); gs_mesh on a COLMAP model is not read."""
 from __future__ import annotations
 
 import ctypes as C
@@ -208,6 +210,81 @@ def read_blender_mesh_scene(path, white_background=False, eval=False, num_splats
     ply_path = os.path.join(path, "points3d.ply")
     store_ply(ply_path, cloud.points.numpy(), cloud.colors * 255)
     return SceneInfo(cloud, train, test, nerfpp_norm(train), ply_path)
+
+
+class FLAMEPointCloud(NamedTuple):
+    """games/flame_splatting/utils/graphics_utils.py: the same fourteen fields in the same order, so that the reference's
+    GaussianFlameModel takes it and `flame_params.pt` pickles it as the reference's is pickled."""
+    alpha: torch.Tensor
+    points: torch.Tensor
+    colors: np.ndarray
+    normals: np.ndarray
+    faces: torch.Tensor
+    vertices_init: torch.Tensor
+    flame_model: object
+    transform_vertices_function: object
+    flame_model_shape_init: torch.Tensor
+    flame_model_expression_init: torch.Tensor
+    flame_model_pose_init: torch.Tensor
+    flame_model_neck_pose_init: torch.Tensor
+    flame_model_transl_init: torch.Tensor
+    vertices_enlargement_init: float
+
+
+FLAME_SHAPE_PARAMS, FLAME_EXPRESSION_PARAMS = 100, 50            # games/flame_splatting/FLAME/config.py:11-12
+
+
+def _layer_device(layer) -> torch.device:
+    """Where a FLAME layer computes: its first buffer or parameter, else a `device` attribute, else the CPU."""
+    if isinstance(layer, torch.nn.Module):
+        for t in list(layer.buffers()) + list(layer.parameters()):
+            return t.device
+    return torch.device(getattr(layer, "device", "cpu"))
+
+
+def read_blender_flame_scene(path, white_background, eval, flame_model, *, num_splats=100, vertices_enlargement=8.35,
+                             extension=".png") -> SceneInfo:
+    """gs_flame (games/flame_splatting/scene/dataset_readers.py:48-130).  `flame_model`: a layer with the reference's call signature
+    and a `.faces` array (a games_hip.flame.HipFlameLayer on the GPU); the parameter counts come from its `n_shape` / `n_expr` where it
+    has them (FlameConfig's 100 / 50 otherwise).  The layer is called on FlameConfig's all-zero parameters, on the device it lives on;
+    the random weights are the reference's draws on its generators: `torch.rand(F, num_splats, 3)` on the CPU default generator (raw,
+    not normalised), then `np.random.random((P, 3))` for the colours.  points3d.ply is rewritten every time, as there."""
+    from .flame import transform_vertices_function
+    train, test = _train_test(path, eval, extension)
+    device = _layer_device(flame_model)
+    n_shape = int(getattr(flame_model, "n_shape", FLAME_SHAPE_PARAMS))
+    n_expr = int(getattr(flame_model, "n_expr", FLAME_EXPRESSION_PARAMS))
+    zeros = lambda n: torch.zeros(1, n).float().to(device)
+    f_shape, f_exp, f_pose, f_neck_pose, f_trans = zeros(n_shape), zeros(n_expr), zeros(6), zeros(3), zeros(3)
+    with torch.no_grad():
+        vertices, _ = flame_model(f_shape, f_exp, f_pose, neck_pose=f_neck_pose, transl=f_trans)
+        vertices = transform_vertices_function(vertices, c=vertices_enlargement)
+    faces = torch.squeeze(torch.tensor(np.asarray(flame_model.faces).astype(np.int32))).to(vertices.device).long()
+    triangles = vertices[faces]
+    count = int(num_splats) * triangles.shape[0]
+    alpha = torch.rand(triangles.shape[0], int(num_splats), 3).to(vertices.device)
+    points = torch.matmul(alpha, triangles).reshape(count, 3)
+    sh_dc = np.random.random((count, 3)) / 255.0
+    cloud = FLAMEPointCloud(alpha=alpha, points=points.cpu(), colors=sh_dc * C0 + 0.5, normals=np.zeros((count, 3)),
+                            flame_model=flame_model, faces=faces, vertices_init=vertices,
+                            transform_vertices_function=transform_vertices_function, flame_model_shape_init=f_shape,
+                            flame_model_expression_init=f_exp, flame_model_pose_init=f_pose, flame_model_neck_pose_init=f_neck_pose,
+                            flame_model_transl_init=f_trans, vertices_enlargement_init=vertices_enlargement)
+    ply_path = os.path.join(path, "points3d.ply")
+    store_ply(ply_path, cloud.points, (sh_dc * C0 + 0.5) * 255)
+    return SceneInfo(cloud, train, test, nerfpp_norm(train), ply_path)
+
+
+def _flame_layer(flame, device):
+    """`flame=` of load_scene -> a HipFlameLayer on `device`: the layer itself, a FlameData, or a path FlameData.load opens."""
+    from .flame import FlameData, HipFlameLayer
+    if isinstance(flame, (str, os.PathLike)):
+        flame = FlameData.load(os.fspath(flame))
+    if isinstance(flame, FlameData):
+        flame = HipFlameLayer(flame, min(FLAME_SHAPE_PARAMS, flame.n_shape_full), min(FLAME_EXPRESSION_PARAMS, flame.n_expr_full))
+    if not isinstance(flame, HipFlameLayer):
+        raise TypeError(f"load_scene: `flame` must be a HipFlameLayer, a FlameData or the path of a FLAME model file, not {type(flame).__name__}")
+    return flame.to(device)
 
 
 # ------------------------------------------------------------------------------------------------ resolution and resampling tables
@@ -566,16 +643,28 @@ def write_scene_files(scene_info: SceneInfo, model_path) -> None:
         json.dump(entries, f)
 
 
-def load_scene(source_path, gs_type, *, white_background=False, eval=False, num_splats=2, resolution=-1, shuffle=True, model_path=None,
-               device="cuda", images=None, meshes=None) -> LoadedScene:
+def load_scene(source_path, gs_type, *, white_background=False, eval=False, num_splats=None, resolution=-1, shuffle=True, model_path=None,
+               device="cuda", images=None, meshes=None, flame=None, vertices_enlargement=8.35) -> LoadedScene:
     """scene/__init__.py:43-94.  A COLMAP model (sparse/0/images.bin or images.txt) is read for gs, gs_flat (read_colmap_scene) and
     gs_multi_mesh (read_colmap_mesh_scene: `meshes` names the OBJ files under sparse/0, `num_splats` holds one count per mesh or one
-    for all); `images` names the image folder (default "images").  A transforms_train.json directory is read for gs, gs_flat and
-    gs_mesh."""
+    for all); `images` names the image folder (default "images").  A transforms_train.json directory is read for gs, gs_flat,
+    gs_mesh and -- with `flame`, the FLAME layer (a games_hip.flame.HipFlameLayer, a FlameData, or the path of the licensed model
+    file, which is not shipped) -- gs_flame (read_blender_flame_scene).  `num_splats`: splats per face, by default 2, and the
+    reference's 100 for gs_flame.  `vertices_enlargement`: the factor on the FLAME layer's vertices (FlameConfig's 8.35), gs_flame only."""
     from . import colmap
     if gs_type not in ("gs", "gs_flat", "gs_mesh", "gs_flame", "gs_multi_mesh"):
         raise ValueError(f"load_scene: unknown gs_type {gs_type!r}")
-    if colmap.has_model(source_path):
+    if gs_type == "gs_flame" and flame is None:
+        raise NotImplementedError("load_scene: a gs_flame (Blender_FLAME) scene is read only with `flame=`: a games_hip.flame.HipFlameLayer, "
+                                  "a FlameData, or the path of the FLAME model file (licensed, not shipped) that FlameData.load opens")
+    if num_splats is None:
+        num_splats = 100 if gs_type == "gs_flame" else 2
+    if gs_type == "gs_flame":
+        if not os.path.exists(os.path.join(source_path, "transforms_train.json")):
+            raise FileNotFoundError(f"{source_path}: no transforms_train.json; a gs_flame scene is a Blender-format directory")
+        scene_info = read_blender_flame_scene(source_path, white_background, eval, _flame_layer(flame, device), num_splats=int(num_splats),
+                                              vertices_enlargement=vertices_enlargement)
+    elif colmap.has_model(source_path):
         if gs_type == "gs_multi_mesh":
             if not meshes:
                 raise ValueError("load_scene: a gs_multi_mesh scene needs `meshes`, the names of the OBJ files under sparse/0")
@@ -589,9 +678,9 @@ def load_scene(source_path, gs_type, *, white_background=False, eval=False, num_
             raise NotImplementedError(f"{source_path}: gs_type {gs_type!r} cannot be read from a COLMAP model (the reference has no COLMAP "
                                       "reader for it); gs, gs_flat and gs_multi_mesh can")
     else:
-        if gs_type in ("gs_flame", "gs_multi_mesh"):
+        if gs_type == "gs_multi_mesh":
             raise NotImplementedError(f"load_scene: gs_type {gs_type!r} is not read from this directory (gs_multi_mesh needs a COLMAP model "
-                                      "under sparse/0, Blender_FLAME scenes their own reader); gs, gs_flat and gs_mesh are")
+                                      "under sparse/0); gs, gs_flat, gs_mesh and, with `flame=`, gs_flame are")
         if os.path.exists(os.path.join(source_path, "sparse")):
             looked = ", ".join("sparse/0/" + n for n in colmap.MODEL_FILES)
             raise NotImplementedError(f"{source_path}: a sparse/ directory is a COLMAP dataset, but it holds no model that can be read "

@@ -61,12 +61,13 @@ class _Derived:
                  "tri",             # vertices[faces], gathered on first access                                   <- vertices, faces
                  "tri_external",    # `triangles` as a renderer / loader assigned it; wins over `tri` until the next update_alpha()
                  "centre",          # HipPointsMixin: triangles[:, 0] as the points op returned it                <- the triangles
-                 "topology")        # HipMultiMeshMixin: (shapes, (faces, face_splat_offset, splat_face))         <- the faces
+                 "topology",        # HipMultiMeshMixin: (shapes, (faces, face_splat_offset, splat_face))         <- the faces
+                 "flame")           # HipFlameMixin: the FLAME node's vertices of the last update_alpha()   <- the six FLAME parameters
 
     def __init__(self):
         self.pending = False
         self.geometry = self.activated = self.opacity_act = self.frame = None
-        self.tri = self.tri_external = self.centre = self.topology = None
+        self.tri = self.tri_external = self.centre = self.topology = self.flame = None
 
 
 class _HipGetters:
@@ -145,7 +146,7 @@ class _HipGetters:
 
 
 class _HipDeferredK0(_HipGetters):
-    """The deferred K0 that the mesh and the multi-mesh mixin share.  A user provides `_hip_inputs()` (the tensors the op reads),
+    """The deferred K0 that the mesh, the FLAME and the multi-mesh mixin share.  A user provides `_hip_inputs()` (the tensors the op reads),
     `_hip_derive()` (the K0 launch: sets `alpha` / `_xyz`, leaves scaling / rotation in `_Derived.geometry`) and prepare_scaling_rot()."""
 
     # ---- deferred K0 (opt-in; games_hip/train.py and bench.py switch it on).  train.py:154-157 calls update_alpha() /
@@ -289,10 +290,16 @@ class HipFlameMixin(HipMeshMixin):
     class's FLAME layer (:196-207), scale parameter named `_scales` (:42,:82).  With a `games_hip.flame.HipFlameLayer` as
     `point_cloud.flame_model` the layer, the transform function and the enlargement are one autograd node on csrc/flame.hip
     (one launch forward, two backward); any other layer (the reference's smplx one, the synthetic stand-in) runs as it is, in
-    python/torch.  One more launch derives alpha / xyz / scaling / rotation from the vertices."""
+    python/torch.  One more launch derives alpha / xyz / scaling / rotation from the vertices -- or, with `hip_defer_k0`, none does:
+    update_alpha() runs the FLAME node (the vertices of an iteration carry that iteration's graph) and defers the K0 as a mesh model
+    does; `_hip_inputs()` hands the frame the node's vertices, a non-leaf tensor, and autograd hands the frame's vertex gradient on to
+    the FLAME node."""
 
     alpha_mode = "softmax"
     _hip_scale_attr = "_scales"
+
+    def _hip_flame_parameters(self):
+        return (self._flame_shape, self._flame_exp, self._flame_pose, self._flame_neck_pose, self._flame_trans, self._vertices_enlargement)
 
     def _hip_flame_vertices(self):
         pc = self.point_cloud
@@ -306,13 +313,23 @@ class HipFlameMixin(HipMeshMixin):
         return fn(vertices, self._vertices_enlargement)
 
     def update_alpha(self):
-        self.vertices = self._hip_flame_vertices()
+        d = self._hip
+        params = self._hip_flame_parameters()
+        kept = _current(d.flame, *params) if d.pending and not torch.is_grad_enabled() else None
+        if kept is not None:
+            # a no_grad reader between a deferred update_alpha() and its frame (_hip_materialize): these ARE the vertices of the
+            # unchanged parameters, and they carry the graph the frame will need -- running the layer again here would drop it
+            self.vertices = kept
+        else:
+            self.vertices = self._hip_flame_vertices()
+            d.flame = _Stamp(self.vertices, *params)
         super().update_alpha()
 
-    def _hip_defer_now(self):       # (the FLAME layer runs in update_alpha: K0 stays an eager launch)
-        return False
-
-    def save_ply(self, path):       # GaussianFlameModel.save_ply does not read `triangles`
+    def save_ply(self, path):
+        """GaussianFlameModel.save_ply (gaussian_flame_model.py:232-251) calls update_alpha() / prepare_scaling_rot(), which may defer,
+        and then writes the raw attributes: derive them first.  (It does not read `triangles`.)"""
+        if self._hip_defer_now():
+            self._hip_refresh()
         return super(HipMeshMixin, self).save_ply(path)
 
 
@@ -763,8 +780,9 @@ class _FlameCloud:
 
 
 class HipGaussianFlameModel(HipFlameMixin, _StandaloneBase):
-    """gs_flame (BASELINE config 5) with a synthetic vertex generator in place of the FLAME layer: per-frame
-    vertex animation + on-device re-derivation of the face-local rotation / scale."""
+    """gs_flame (BASELINE config 5): per-frame vertex animation + on-device re-derivation of the face-local rotation / scale.
+    `from_scene` builds it on a synthetic scene (a synthetic vertex generator, or a HipFlameLayer over the scene's vertices),
+    `create_from_pcd` from the FLAMEPointCloud of a Blender_FLAME directory (games_hip.dataset.load_scene)."""
 
     @classmethod
     def from_scene(cls, scene, device="cuda", enlargement=1.0, flame=None):
@@ -797,6 +815,41 @@ class HipGaussianFlameModel(HipFlameMixin, _StandaloneBase):
         m.prepare_scaling_rot()
         return m
 
+    def create_from_pcd(self, pcd, spatial_lr_scale: float = 1.0, device="cuda"):
+        """gaussian_flame_model.py:56-104 from a FLAMEPointCloud (games_hip.dataset.load_scene, or the reference's own): the five FLAME
+        parameters from the cloud's initial values, the enlargement as one factor per vertex coordinate, `_alpha` the cloud's raw
+        weights, `_scales` 1, opacity 0.1, the colours in the SH constant term, zero higher SH; update_alpha() and
+        prepare_scaling_rot() where the reference calls them (the first before `_scales` exists).  The parameters are copies: training
+        does not write into the cloud that flame_params.pt pickles."""
+        import numpy as np
+        self.point_cloud = pcd
+        self.spatial_lr_scale = spatial_lr_scale
+        P = pcd.points.shape[0]
+        par = lambda a: nn.Parameter(a.detach().clone().to(device).contiguous().requires_grad_(True))
+        fused_color = (torch.tensor(np.asarray(pcd.colors)).float().to(device) - 0.5) / 0.28209479177387814      # RGB2SH
+        features = torch.zeros((P, 3, (self.max_sh_degree + 1) ** 2)).float().to(device)
+        features[:, :3, 0] = fused_color
+        tenth = 0.1 * torch.ones((P, 1), dtype=torch.float, device=device)
+        opacities = torch.log(tenth / (1 - tenth))             # inverse_sigmoid on the float32 tensor, as there (utils/general_utils.py:19)
+        self._hip_flame_layer = isinstance(pcd.flame_model, _flame.HipFlameLayer)
+        self.__dict__.pop("_hip_derived", None)
+        self._flame_shape = par(pcd.flame_model_shape_init)
+        self._flame_exp = par(pcd.flame_model_expression_init)
+        self._flame_pose = par(pcd.flame_model_pose_init)
+        self._flame_neck_pose = par(pcd.flame_model_neck_pose_init)
+        self._flame_trans = par(pcd.flame_model_transl_init)
+        self.faces = torch.as_tensor(pcd.faces).to(device)
+        self._vertices_enlargement = par(pcd.vertices_enlargement_init * torch.ones_like(pcd.vertices_init))
+        self._scales = torch.empty(0)
+        self._alpha = par(pcd.alpha.float())
+        self.update_alpha()
+        self._features_dc = par(features[:, :, 0:1].transpose(1, 2))
+        self._features_rest = par(features[:, :, 1:].transpose(1, 2))
+        self._scales = par(torch.ones((P, 1)).float())
+        self.prepare_scaling_rot()
+        self._opacity = par(opacities)
+        self.max_radii2D = torch.zeros((self.get_xyz.shape[0]), device=device)
+
     def parameters(self):
         neck = [self._flame_neck_pose] if getattr(self, "_hip_flame_layer", False) else []
         return [self._flame_exp, self._flame_pose, *neck, self._flame_trans, self._vertices_enlargement, self._alpha,
@@ -806,7 +859,12 @@ class HipGaussianFlameModel(HipFlameMixin, _StandaloneBase):
                        flame_trans_lr=0.001, vertices_enlargement_lr=0.0002, alpha_lr=0.001, feature_lr=0.0025, opacity_lr=0.05,
                        scaling_lr=0.005, fused=True):
         """Parameter groups of gaussian_flame_model.py:209-228, in its order, with the defaults of `OptimizationParamsFlame`
-        (arguments_games/__init__.py:30-47)."""
+        (arguments_games/__init__.py:30-47).  The reference's form works too: one object with those learning rates as attributes
+        (games_hip.train.OptimizationParamsFlame) in place of the first argument."""
+        if hasattr(flame_shape_lr, "flame_shape_lr"):
+            a = flame_shape_lr
+            return self.training_setup(a.flame_shape_lr, a.flame_exp_lr, a.flame_pose_lr, a.flame_neck_pose_lr, a.flame_trans_lr,
+                                       a.vertices_enlargement_lr, a.alpha_lr, a.feature_lr, a.opacity_lr, a.scaling_lr, fused=fused)
         self._make_optimizer([
             {"params": [self._flame_shape], "lr": flame_shape_lr, "name": "shape"},
             {"params": [self._flame_exp], "lr": flame_exp_lr, "name": "expression"},
@@ -858,6 +916,7 @@ class HipGaussianFlameModel(HipFlameMixin, _StandaloneBase):
         # (the getters serve exp(_scaling) / normalize(_rotation) of these new tensors until something re-derives them)
         self.__dict__.pop("_hip_derived", None)
         self.vertices = None
+        self._hip_flame_layer = isinstance(getattr(self.point_cloud, "flame_model", None), _flame.HipFlameLayer)
         if all(k in params for k in self.FLAME_EXTRA_ATTRS):
             self._alpha = nn.Parameter(params["_alpha"].detach().to(device))
             self._scales = nn.Parameter(params["_scales"].detach().to(device))

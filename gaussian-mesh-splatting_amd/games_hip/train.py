@@ -50,6 +50,26 @@ class OptimizationParamsMesh:
 
 
 @dataclass
+class OptimizationParamsFlame:
+    """arguments_games/__init__.py:32-48 (gs_flame), in its order; `HipGaussianFlameModel.training_setup` takes one such object."""
+    iterations: int = 30_000
+    alpha_lr: float = 0.001
+    feature_lr: float = 0.0025
+    opacity_lr: float = 0.05
+    scaling_lr: float = 0.005
+    rotation_lr: float = 0.001
+    flame_shape_lr: float = 0.01
+    flame_exp_lr: float = 0.001
+    flame_pose_lr: float = 0.001
+    flame_neck_pose_lr: float = 0.001
+    flame_trans_lr: float = 0.001
+    vertices_enlargement_lr: float = 0.0002
+    random_background: bool = False
+    use_mesh: bool = True
+    lambda_dssim: float = 0.2
+
+
+@dataclass
 class OptimizationParams:
     """arguments/__init__.py:72-90 (gs / gs_flat)."""
     iterations: int = 30_000
