@@ -17,34 +17,51 @@
 namespace gms {
 
 // ------------------------------------------------------------------------------------ K2
-// One block: exclusive scans over the tiles of (a) instance counts -> tile_offset (offset[T] = N),
-// (b) segments per tile -> unit_first, (c) segments of multi-segment tiles -> mseg_first (slots of
-// the per-unit pixel state).  Also resets the emit cursors.
 // tile sort (K4) sizes, needed by the scan below
 constexpr int SORT_RUN = 1024;
 constexpr int SORT_RUNS_PER_TILE = 8;
 constexpr int SORT_BIG_CHUNK = SORT_RUN * SORT_RUNS_PER_TILE;    // 8192 keys = 64 KiB LDS
 constexpr int MP_CHUNK = 1024;                                   // output keys per merge-path block
 
-constexpr int NSCAN = 11;
-constexpr int NCLASS = 6;     // dispatch classes: full | partial >=3/4 L | >=1/2 L | >=1/4 L | < 1/4 L | empty
+// The per-tile quantities the scan takes exclusive prefixes of, all in one pass.  The dispatch classes order the unit table
+// heaviest first: every full segment, then the partial last segments by length, then the units of empty tiles.
+enum ScanQuantity {
+    Q_INSTANCES = 0,      // keys of the tile                                                   -> ImageState::tile_offset ([T] = N)
+    Q_UNITS,              // work units = segments; an empty tile still gets one (background)   -> unit_first ([T] = number of units)
+    Q_MSEG,               // segments of multi-segment tiles: slots of the per-unit pixel state -> mseg_first
+    Q_FULL,               // dispatch classes -> scan_rows: the full segments of the tile,
+    Q_PART_34,            //   a partial last segment of >= 3/4 L keys,
+    Q_PART_12,            //   of >= 1/2 L,
+    Q_PART_14,            //   of >= 1/4 L,
+    Q_PART_LOW,           //   a shorter one,
+    Q_EMPTY,              //   the unit of an empty tile
+    Q_SORT_RUNS,          // 1024-key sort runs (= merge-path chunks) of a tile with more than one key -> scan_rows; the prefix indexes deep_tab
+    Q_MULTI_RUN,          // the tile has more than one run and needs merging                        -> scan_rows; the prefix indexes multi_tab
+    NSCAN
+};
+static_assert(NSCAN - Q_FULL == 8, "ImageState::scan_rows is carved with eight rows");
 constexpr int SCAN_THREADS = 1024;
 
-// per-tile quantities scanned: instances, segments, segments of multi-segment tiles, then the dispatch classes
-__device__ __forceinline__ void tile_terms(uint32_t c, uint32_t L, uint32_t t[NSCAN], int sort_np = 0)
+// the T + 1 prefixes of quantity q in the image state: entry [t] = the sum over the tiles before t, entry [T] = the total
+__host__ __device__ __forceinline__ uint32_t *scan_row(const ImageState &img, int T, int q)
 {
-    const uint32_t ns = max(1u, (c + L - 1) / L);   // empty tiles still get a unit (background)
-    t[0] = c; t[1] = ns; t[2] = ns > 1 ? ns : 0;
+    return q == Q_INSTANCES ? img.tile_offset : q == Q_UNITS ? img.unit_first : q == Q_MSEG ? img.mseg_first
+                                                                                            : img.scan_rows + (size_t)(q - Q_FULL) * ((size_t)T + 1);
+}
+
+__device__ __forceinline__ void tile_terms(uint32_t c, uint32_t L, uint32_t t[NSCAN])
+{
+    const uint32_t ns = max(1u, (c + L - 1) / L);
     const uint32_t r = c % L;
-    t[3] = c / L;
-    t[4] = r * 4 >= 3 * L ? 1u : 0u;
-    t[5] = (r * 4 < 3 * L && r * 2 >= L) ? 1u : 0u;
-    t[6] = (r * 2 < L && r * 4 >= L) ? 1u : 0u;
-    t[7] = (r * 4 < L && r != 0) ? 1u : 0u;
-    t[8] = c == 0 ? 1u : 0u;
-    t[9] = c > 1 ? (c + MP_CHUNK - 1) / MP_CHUNK : 0u;      // 1024-key sort runs (= merge-path chunks) of the tile
-    t[10] = c > (uint32_t)SORT_RUN ? 1u : 0u;               // tile needs merging
-    (void)sort_np;
+    t[Q_INSTANCES] = c; t[Q_UNITS] = ns; t[Q_MSEG] = ns > 1 ? ns : 0;
+    t[Q_FULL] = c / L;
+    t[Q_PART_34] = r * 4 >= 3 * L ? 1u : 0u;
+    t[Q_PART_12] = (r * 4 < 3 * L && r * 2 >= L) ? 1u : 0u;
+    t[Q_PART_14] = (r * 2 < L && r * 4 >= L) ? 1u : 0u;
+    t[Q_PART_LOW] = (r * 4 < L && r != 0) ? 1u : 0u;
+    t[Q_EMPTY] = c == 0 ? 1u : 0u;
+    t[Q_SORT_RUNS] = c > 1 ? (c + MP_CHUNK - 1) / MP_CHUNK : 0u;
+    t[Q_MULTI_RUN] = c > (uint32_t)SORT_RUN ? 1u : 0u;
 }
 
 // The instance count N goes straight to the host: system-scope stores into pinned memory that the waiting host thread
@@ -60,17 +77,108 @@ __device__ __forceinline__ void publish_counts(int32_t *host_slot, int32_t seq, 
     __hip_atomic_store(&hs[0], tag | n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// One block of 1024 threads: NSCAN exclusive scans over the tiles at once.  Each wave scans its 64 per-thread
-// sums with DPP-free shuffles, the 16 wave totals are scanned by the first wave: two block barriers in all.
-__global__ void __launch_bounds__(SCAN_THREADS) tile_scan_kernel(uint32_t *count, uint32_t *offset, uint32_t *cursor,
-                                                                 uint32_t *unit_first, uint32_t *mseg_first,
-                                                                 uint32_t *class_first, int T, uint32_t L_forced, int32_t *host_slot,
-                                                                 int32_t seq, int sort_np, uint32_t *scan_out)
+template <int WIDTH = WAVE>
+__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane)      // over the first WIDTH lanes
 {
-    __shared__ uint32_t wave_tot[NSCAN][SCAN_THREADS / WAVE];
+    for (int d = 1; d < WIDTH; d <<= 1) {
+        const uint32_t x = (uint32_t)__shfl_up((int)v, d);
+        if (lane >= d) v += x;
+    }
+    return v;
+}
+
+// a THREADS-wide scan gives every thread scan_per consecutive tiles: thread `tid` owns [b, e) (none: threads beyond the tiles)
+template <int THREADS>
+__device__ __forceinline__ int scan_per(int T) { return (T + THREADS - 1) / THREADS; }
+template <int THREADS>
+__device__ __forceinline__ void scan_chunk(int T, int tid, int &b, int &e)
+{
+    b = min(T, tid * scan_per<THREADS>(T)); e = min(T, b + scan_per<THREADS>(T));
+}
+
+template <int THREADS>
+struct BlockScanLds {
+    uint32_t wave_tot[NSCAN][THREADS / WAVE];
+    uint32_t wave_deep[THREADS / WAVE];
+};
+
+// One block of THREADS threads: the NSCAN exclusive scans of count[0, T) for segment length L at once.  Every thread is left with
+// the exclusive prefix `pre` of its chunk (scan_chunk), the totals `tot` and the deepest tile.  Each wave scans its 64 chunk sums
+// with shuffles, then the first wave scans the wave totals: two block barriers, for the 4 waves of an emit block as for the 16 of
+// the scan launch.
+template <int THREADS>
+__device__ __forceinline__ void block_scan_tiles(const uint32_t *count, int T, uint32_t L, BlockScanLds<THREADS> &S, uint32_t pre[NSCAN],
+                                                 uint32_t tot[NSCAN], uint32_t &deepest)
+{
+    constexpr int NW = THREADS / WAVE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = (T + SCAN_THREADS - 1) / SCAN_THREADS;
-    const int b = tid * per, e = min(T, b + per);
+    int b, e;
+    scan_chunk<THREADS>(T, tid, b, e);
+    uint32_t sum[NSCAN];
+    uint32_t deep = 0;
+#pragma unroll
+    for (int k = 0; k < NSCAN; k++) sum[k] = 0;
+    for (int t = b; t < e; t++) {
+        uint32_t q[NSCAN];
+        tile_terms(count[t], L, q);
+        deep = max(deep, q[Q_INSTANCES]);
+#pragma unroll
+        for (int k = 0; k < NSCAN; k++) sum[k] += q[k];
+    }
+    for (int d = 32; d >= 1; d >>= 1) deep = max(deep, (uint32_t)__shfl_xor((int)deep, d));
+    if (lane == 0) S.wave_deep[wave] = deep;
+#pragma unroll
+    for (int k = 0; k < NSCAN; k++) {
+        const uint32_t incl = wave_incl_scan_u32(sum[k], lane);
+        if (lane == WAVE - 1) S.wave_tot[k][wave] = incl;
+        pre[k] = incl - sum[k];
+    }
+    __syncthreads();
+    if (wave == 0) {
+#pragma unroll
+        for (int k = 0; k < NSCAN; k++) {
+            const uint32_t v = wave_incl_scan_u32<NW>(lane < NW ? S.wave_tot[k][lane] : 0u, lane);
+            if (lane < NW) S.wave_tot[k][lane] = v;      // inclusive over waves
+        }
+        uint32_t dm = lane < NW ? S.wave_deep[lane] : 0u;
+        for (int d = NW / 2; d >= 1; d >>= 1) dm = max(dm, (uint32_t)__shfl_xor((int)dm, d));
+        if (lane == 0) S.wave_deep[0] = dm;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NSCAN; k++) {
+        tot[k] = S.wave_tot[k][NW - 1];
+        pre[k] += wave > 0 ? S.wave_tot[k][wave - 1] : 0u;
+    }
+    deepest = S.wave_deep[0];
+}
+
+// What one thread of a scan does with the totals: the device copy of the counts (launches-only frames and re-runs of the tail read
+// it), the host's copy, and entry [T] of every row.
+__device__ __forceinline__ void write_totals(const ImageState &img, int T, const uint32_t tot[NSCAN], uint32_t deepest, uint32_t L,
+                                             int32_t *host_slot, int32_t seq)
+{
+    img.scan_out[0] = tot[Q_INSTANCES]; img.scan_out[1] = deepest; img.scan_out[2] = tot[Q_UNITS]; img.scan_out[3] = L;
+    if (host_slot) publish_counts(host_slot, seq, tot[Q_INSTANCES], deepest, tot[Q_UNITS]);
+#pragma unroll
+    for (int k = 0; k < NSCAN; k++) scan_row(img, T, k)[T] = tot[k];
+}
+
+__device__ __forceinline__ void write_prefixes(const ImageState &img, int T, int t, const uint32_t pre[NSCAN])
+{
+#pragma unroll
+    for (int k = 0; k < NSCAN; k++) scan_row(img, T, k)[t] = pre[k];
+}
+
+// K2 as a launch of its own, one block: chooses the frame's segment length when none is forced, scans, publishes, and clears the
+// emit cursors and the tile counters.
+__global__ void __launch_bounds__(SCAN_THREADS) tile_scan_kernel(ImageState img, int T, uint32_t L_forced, int32_t *host_slot, int32_t seq)
+{
+    __shared__ BlockScanLds<SCAN_THREADS> S;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t *count = img.tile_count;
+    int b, e;
+    scan_chunk<SCAN_THREADS>(T, tid, b, e);
     // segment length of this frame: forced, or chosen from the average list length per tile (gms_blend.h)
     uint32_t L = L_forced;
     if (L == 0) {
@@ -85,298 +193,180 @@ __global__ void __launch_bounds__(SCAN_THREADS) tile_scan_kernel(uint32_t *count
         L = total > (uint64_t)SEG_VERY_DEEP_PER_TILE * (uint64_t)T ? SEG_LEN_VERY_DEEP
           : total > (uint64_t)SEG_DEEP_PER_TILE * (uint64_t)T ? SEG_LEN_DEEP : SEG_LEN_SHALLOW;
     }
-    uint32_t run[NSCAN], own[NSCAN];
-    uint32_t deepest = 0;
-#pragma unroll
-    for (int k = 0; k < NSCAN; k++) run[k] = 0;
+    uint32_t run[NSCAN], tot[NSCAN], deepest;
+    block_scan_tiles<SCAN_THREADS>(count, T, L, S, run, tot, deepest);
+    // {N, deepest tile, work units} go to the host right here, as early as they exist: the host thread that waits for N
+    // then has the rest of the forward (emit, sort, compositing: ~220 us on the headline scene) to get the backward
+    // enqueued before the GPU runs dry.  (Publishing from the emit launch instead was measured: the scan is not
+    // shortened by it -- 15.7 -> 15.4 us -- and the host loses 24 us of that slack.)
+    if (tid == 0) write_totals(img, T, tot, deepest, L, host_slot, seq);
     for (int t = b; t < e; t++) {
         uint32_t q[NSCAN];
-        tile_terms(count[t], L, q, sort_np);
-        deepest = max(deepest, q[0]);
-#pragma unroll
-        for (int k = 0; k < NSCAN; k++) run[k] += q[k];
-    }
-    for (int d = 32; d >= 1; d >>= 1) deepest = max(deepest, (uint32_t)__shfl_xor((int)deepest, d));
-    __shared__ uint32_t wave_deep[SCAN_THREADS / WAVE];
-    if (lane == 0) wave_deep[wave] = deepest;
-    // inclusive scan inside the wave
-#pragma unroll
-    for (int k = 0; k < NSCAN; k++) {
-        own[k] = run[k];
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const uint32_t x = (uint32_t)__shfl_up((int)run[k], d);
-            if (lane >= d) run[k] += x;
-        }
-        if (lane == WAVE - 1) wave_tot[k][wave] = run[k];
-    }
-    __syncthreads();
-    if (wave == 0) {
-#pragma unroll
-        for (int k = 0; k < NSCAN; k++) {
-            uint32_t v = lane < SCAN_THREADS / WAVE ? wave_tot[k][lane] : 0u;
-            for (int d = 1; d < SCAN_THREADS / WAVE; d <<= 1) {
-                const uint32_t x = (uint32_t)__shfl_up((int)v, d);
-                if (lane >= d) v += x;
-            }
-            if (lane < SCAN_THREADS / WAVE) wave_tot[k][lane] = v;      // inclusive over waves
-        }
-    }
-    __syncthreads();
-    uint32_t tot[NSCAN];
-#pragma unroll
-    for (int k = 0; k < NSCAN; k++) {
-        tot[k] = wave_tot[k][SCAN_THREADS / WAVE - 1];
-        run[k] = run[k] - own[k] + (wave > 0 ? wave_tot[k][wave - 1] : 0u);   // exclusive prefix of this thread's chunk
-    }
-    // The instance count N goes straight to the host: two system-scope stores into pinned memory (value, then the
-    // call's sequence number) that the waiting host thread polls -- no copy-engine hop, no event wake-up latency.
-    if (tid == 0) {
-        uint32_t dm = 0;
-        for (int w = 0; w < SCAN_THREADS / WAVE; w++) dm = max(dm, wave_deep[w]);
-        // {N, deepest tile, work units} go to the host right here, as early as they exist: the host thread that waits for N
-        // then has the rest of the forward (emit, sort, compositing: ~220 us on the headline scene) to get the backward
-        // enqueued before the GPU runs dry.  (Publishing from the emit launch instead was measured: the scan is not
-        // shortened by it -- 15.7 -> 15.4 us -- and the host loses 24 us of that slack.)  The device copy serves that variant.
-        scan_out[0] = tot[0]; scan_out[1] = dm; scan_out[2] = tot[1]; scan_out[3] = L;
-        if (host_slot) publish_counts(host_slot, seq, tot[0], dm, tot[1]);
-    }
-    for (int t = b; t < e; t++) {
-        uint32_t q[NSCAN];
-        tile_terms(count[t], L, q, sort_np);
-        offset[t] = run[0]; unit_first[t] = run[1]; mseg_first[t] = run[2];
-#pragma unroll
-        for (int k = 0; k < NCLASS; k++) class_first[k * (T + 1) + t] = run[3 + k];
-        class_first[NCLASS * (T + 1) + t] = run[9];
-        class_first[(NCLASS + 1) * (T + 1) + t] = run[10];
-        cursor[t] = 0;
+        tile_terms(count[t], L, q);
+        write_prefixes(img, T, t, run);
+        img.tile_cursor[t] = 0;
         count[t] = 0;          // the counter array is library-owned and stays all zero between frames (no memset per frame)
 #pragma unroll
         for (int k = 0; k < NSCAN; k++) run[k] += q[k];
-    }
-    if (tid == 0) {
-        offset[T] = tot[0]; unit_first[T] = tot[1]; mseg_first[T] = tot[2];
-#pragma unroll
-        for (int k = 0; k < NCLASS; k++) class_first[k * (T + 1) + T] = tot[3 + k];
-        class_first[NCLASS * (T + 1) + T] = tot[9];
-        class_first[(NCLASS + 1) * (T + 1) + T] = tot[10];
     }
 }
 
 // unit table, heaviest first: [all full segments | partial last segments | units of empty tiles]
 struct FillUnitsArgs {
-    const uint32_t *class_first, *offset, *mseg_first;
+    ImageState img;                // the scan's tables: read here, or written by the spare blocks that scan themselves
     uint4 *unit_tile;
     uint2 *deep_tab;
     uint32_t *multi_tab;
-    int T, sort_np;
-    const uint32_t *scan_out;      // [3] = this frame's segment length
+    int T;
     uint32_t max_units, max_deep, max_multi;
 };
 
-// what fill_units needs to know about one tile: its count, its exclusive prefixes `pre` of the NSCAN scanned quantities and
-// the totals `tot` (tile_scan_kernel's arrays, or the inline scan of the emit launch)
+// what fill_units needs to know about one tile: its count, its exclusive prefixes `pre` of the scanned quantities and their
+// totals `tot` (out of the scan's tables, or straight from the scan inside the emit launch)
 __device__ __forceinline__ void fill_units_tile(const FillUnitsArgs &f, int t, uint32_t c, uint32_t L, const uint32_t pre[NSCAN], const uint32_t tot[NSCAN])
 {
     const uint32_t nfull = c / L;
     uint32_t q[NSCAN];
-    tile_terms(c, L, q, f.sort_np);
-    const uint32_t nseg = q[1];                          // units of this tile (>= 1)
-    const uint4 tail = make_uint4(pre[0], pre[0] + c, 0u, 0u);
-    const uint32_t slot0 = pre[2];
+    tile_terms(c, L, q);
+    const uint32_t nseg = q[Q_UNITS];                   // units of this tile (>= 1)
+    const uint4 tail = make_uint4(pre[Q_INSTANCES], pre[Q_INSTANCES] + c, 0u, 0u);
+    const uint32_t slot0 = pre[Q_MSEG];
     auto put = [&](uint32_t u, uint32_t seg) {
         if (u < f.max_units) {
             f.unit_tile[2 * (size_t)u] = make_uint4((uint32_t)t, seg, nseg, slot0);
             f.unit_tile[2 * (size_t)u + 1] = tail;
         }
     };
-    for (uint32_t j = 0, d = pre[9]; j < q[9]; j++, d++)
+    for (uint32_t j = 0, d = pre[Q_SORT_RUNS]; j < q[Q_SORT_RUNS]; j++, d++)
         if (d < f.max_deep) f.deep_tab[d] = make_uint2((uint32_t)t, j);
-    if (q[10]) { const uint32_t d = pre[10]; if (d < f.max_multi) f.multi_tab[d] = (uint32_t)t; }
-    uint32_t u = pre[3];
+    if (q[Q_MULTI_RUN]) { const uint32_t d = pre[Q_MULTI_RUN]; if (d < f.max_multi) f.multi_tab[d] = (uint32_t)t; }
+    uint32_t u = pre[Q_FULL];
     for (uint32_t s = 0; s < nfull; s++, u++) put(u, s);
-    uint32_t base = tot[3];                             // all full units come first
-    for (int k = 1; k < NCLASS; k++) {
-        if (q[3 + k]) put(base + pre[3 + k], k == NCLASS - 1 ? 0u : nfull);
-        base += tot[3 + k];
+    uint32_t base = tot[Q_FULL];                        // all full units come first
+    for (int k = Q_FULL + 1; k <= Q_EMPTY; k++) {
+        if (q[k]) put(base + pre[k], k == Q_EMPTY ? 0u : nfull);
+        base += tot[k];
     }
 }
 
+// a spare block of a frame whose scan was a launch of its own: 256 tiles, prefixes and totals out of the tables (the loads of
+// entries that fill_units_tile does not read are dropped by the compiler)
 __device__ __forceinline__ void fill_units(const FillUnitsArgs &f, int block)
 {
     const int T = f.T;
     const int t = block * BLOCK + threadIdx.x;
     if (t >= T) return;
-    const uint32_t c = f.offset[t + 1] - f.offset[t];      // (the counters were cleared by the scan)
+    const uint32_t c = f.img.tile_offset[t + 1] - f.img.tile_offset[t];      // (the counters were cleared by the scan)
     uint32_t pre[NSCAN], tot[NSCAN];
-    pre[0] = f.offset[t]; pre[1] = 0u; pre[2] = f.mseg_first[t]; tot[0] = tot[1] = tot[2] = 0u;
 #pragma unroll
-    for (int k = 0; k < NCLASS + 2; k++) { pre[3 + k] = f.class_first[k * (T + 1) + t]; tot[3 + k] = f.class_first[k * (T + 1) + T]; }
-    fill_units_tile(f, t, c, f.scan_out[3], pre, tot);
+    for (int k = 0; k < NSCAN; k++) { const uint32_t *row = scan_row(f.img, T, k); pre[k] = row[t]; tot[k] = row[T]; }
+    fill_units_tile(f, t, c, f.img.scan_out[3], pre, tot);
 }
 
 // ---- the tile scan INSIDE the emit launch (round 4).  tile_scan_kernel is one block whose 13 us sit between preprocess and emit
 // with the rest of the chip idle.  On the capacity-hint path (every frame but the first of a shape) its work is done redundantly
 // instead: every emit block scans the T <= 4096 counters itself (10-16 KB out of L2, ~1.5 us) and keeps the tile offsets in LDS;
-// the launch's spare blocks -- one per 256 tiles, as before -- run the full NSCAN-quantity scan, write the tables later launches
-// read (tile_offset, unit_first, mseg_first, the totals of class_first, scan_out) and their slice of the unit table, and the first
-// of them publishes N to the host.  The counters are cleared by the presort launch, the cursors by preprocess_fwd.
+// the launch's spare blocks -- one per 256 tiles, as before -- run block_scan_tiles, write the tables later launches read and their
+// slice of the unit table, and the first of them publishes N to the host.  The counters are cleared by the presort launch, the
+// cursors by preprocess_fwd.
 constexpr int INLINE_SCAN_MAX_T = 4096;
+constexpr int INLINE_OFFSETS_PER_THREAD = 16;      // tiles a thread of inline_offsets holds in registers
+static_assert(INLINE_SCAN_MAX_T <= INLINE_OFFSETS_PER_THREAD * BLOCK, "inline_offsets scans at most 16 tiles per thread");
 
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane)
-{
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const uint32_t x = (uint32_t)__shfl_up((int)v, d);
-        if (lane >= d) v += x;
-    }
-    return v;
-}
-
-// exclusive scan of count[0..T) into s_off[0..T]; all BLOCK threads
+// What every emit block pays for: the exclusive scan of the instance counts alone, count[0..T) into s_off[0..T]; all BLOCK threads.
 __device__ __forceinline__ void inline_offsets(const uint32_t *count, int T, uint32_t *s_off, uint32_t *s_wave /* [4] */)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = (T + BLOCK - 1) / BLOCK;
-    const int b = min(T, tid * per), e = min(T, b + per);
-    uint32_t c[16];
+    const int per = scan_per<BLOCK>(T);
+    int b, e;
+    scan_chunk<BLOCK>(T, tid, b, e);
+    uint32_t c[INLINE_OFFSETS_PER_THREAD];
     uint32_t sum = 0;
 #pragma unroll
-    for (int k = 0; k < 16; k++) { c[k] = (k < per && b + k < e) ? count[b + k] : 0u; sum += c[k]; }
+    for (int k = 0; k < INLINE_OFFSETS_PER_THREAD; k++) { c[k] = (k < per && b + k < e) ? count[b + k] : 0u; sum += c[k]; }
     const uint32_t incl = wave_incl_scan_u32(sum, lane);
     if (lane == WAVE - 1) s_wave[wave] = incl;
     __syncthreads();
     uint32_t pre = incl - sum;
     for (int w = 0; w < wave; w++) pre += s_wave[w];
 #pragma unroll
-    for (int k = 0; k < 16; k++)
+    for (int k = 0; k < INLINE_OFFSETS_PER_THREAD; k++)
         if (k < per && b + k < e) { s_off[b + k] = pre; pre += c[k]; }
     if (tid == BLOCK - 1) s_off[T] = pre;
     __syncthreads();
 }
 
-struct InlineScanLds {
-    uint32_t chunk[NSCAN][BLOCK];      // exclusive prefix of every thread's chunk of tiles
-    uint32_t wave_tot[NSCAN][BLOCK / WAVE];
-    uint32_t total[NSCAN];
-    uint32_t wave_deep[BLOCK / WAVE];
-    uint32_t deepest;
+// LDS of a spare block that scans: the scan's own, and the chunk prefixes of all 256 scan threads, from which each thread walks to
+// the tile it fills (tile spare_idx * BLOCK + tid lies in another thread's chunk)
+struct SpareScanLds {
+    BlockScanLds<BLOCK> scan;
+    uint32_t chunk[NSCAN][BLOCK];
 };
 
-// the spare blocks' scan of all NSCAN quantities, then tile `t`'s prefixes / totals
-__device__ __forceinline__ void inline_scan_build(const uint32_t *count, int T, uint32_t L, int sort_np, InlineScanLds &S)
+__device__ __forceinline__ void spare_block_scan(const FillUnitsArgs &fu, uint32_t L, unsigned spare_idx, int32_t *host_slot, int32_t seq,
+                                                 SpareScanLds &S)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int per = (T + BLOCK - 1) / BLOCK;
-    const int b = min(T, tid * per), e = min(T, b + per);
-    uint32_t run[NSCAN];
-    uint32_t deepest = 0;
+    const int T = fu.T, tid = threadIdx.x;
+    const uint32_t *count = fu.img.tile_count;
+    uint32_t pre[NSCAN], tot[NSCAN], deepest;
+    block_scan_tiles<BLOCK>(count, T, L, S.scan, pre, tot, deepest);
 #pragma unroll
-    for (int k = 0; k < NSCAN; k++) run[k] = 0;
-    for (int t = b; t < e; t++) {
+    for (int k = 0; k < NSCAN; k++) S.chunk[k][tid] = pre[k];
+    __syncthreads();
+    if (spare_idx == 0 && tid == 0) write_totals(fu.img, T, tot, deepest, L, host_slot, seq);
+    const int t = (int)spare_idx * BLOCK + tid;
+    if (t >= T) return;
+    const int per = scan_per<BLOCK>(T), c0 = t / per;      // the scan thread whose chunk holds tile t
+#pragma unroll
+    for (int k = 0; k < NSCAN; k++) pre[k] = S.chunk[k][c0];
+    for (int u = c0 * per; u < t; u++) {
         uint32_t q[NSCAN];
-        tile_terms(count[t], L, q, sort_np);
-        deepest = max(deepest, q[0]);
+        tile_terms(count[u], L, q);
 #pragma unroll
-        for (int k = 0; k < NSCAN; k++) run[k] += q[k];
+        for (int k = 0; k < NSCAN; k++) pre[k] += q[k];
     }
-    for (int d = 32; d >= 1; d >>= 1) deepest = max(deepest, (uint32_t)__shfl_xor((int)deepest, d));
-    if (lane == 0) S.wave_deep[wave] = deepest;
-    uint32_t incl[NSCAN];
-#pragma unroll
-    for (int k = 0; k < NSCAN; k++) {
-        incl[k] = wave_incl_scan_u32(run[k], lane);
-        if (lane == WAVE - 1) S.wave_tot[k][wave] = incl[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NSCAN; k++) {
-        uint32_t pre = incl[k] - run[k];
-        for (int w = 0; w < wave; w++) pre += S.wave_tot[k][w];
-        S.chunk[k][tid] = pre;
-    }
-    if (tid == 0) {
-#pragma unroll
-        for (int k = 0; k < NSCAN; k++) S.total[k] = S.wave_tot[k][0] + S.wave_tot[k][1] + S.wave_tot[k][2] + S.wave_tot[k][3];
-        S.deepest = max(max(S.wave_deep[0], S.wave_deep[1]), max(S.wave_deep[2], S.wave_deep[3]));
-    }
-    __syncthreads();
+    write_prefixes(fu.img, T, t, pre);      // (a re-run of the tail reads them)
+    fill_units_tile(fu, t, count[t], L, pre, tot);
 }
 
 // ------------------------------------------------------------------------------------ K3
 // The grid's extra blocks (beyond the Gaussians') write the unit table: it only depends on the tile scan, like this
-// kernel, so it rides along instead of costing a launch of its own.
-struct InlineScanArgs {
-    const uint32_t *count;         // [T] per-tile instance counters (preprocess_fwd)
-    uint32_t *offset, *unit_first, *mseg_first, *class_first, *scan_out;
-    uint32_t L;                    // this frame's segment length (forced: the inline path is not taken when the scan has to choose it)
-};
-
+// kernel, so it rides along instead of costing a launch of its own.  `L`: the frame's segment length, for the INLINE scan (forced:
+// the inline path is not taken when the scan has to choose it).
 template <bool INLINE>
-__global__ void __launch_bounds__(BLOCK) emit_instances_kernel(int P, int gx, int gy, const int *radii, GeomState geom,
-                                                               const uint32_t *tile_offset, uint32_t *tile_cursor,
-                                                               uint64_t *keys, uint64_t capacity, unsigned emit_blocks, FillUnitsArgs fu,
-                                                               int32_t *host_slot, int32_t seq, const uint32_t *scan_out, InlineScanArgs is)
+__global__ void __launch_bounds__(BLOCK) emit_instances_kernel(int P, int gx, GeomState geom, uint64_t *keys, uint64_t capacity, unsigned emit_blocks,
+                                                               FillUnitsArgs fu, uint32_t L, int32_t *host_slot, int32_t seq)
 {
-    // one LDS buffer: emit blocks = [tile offsets (inline scan) | tile table keys, counts, bases | wave sums]; spare blocks = InlineScanLds
+    // one LDS buffer: emit blocks = [tile offsets (inline scan) | tile table keys, counts, bases | wave sums]; spare blocks = SpareScanLds
     constexpr int OFFW = INLINE ? INLINE_SCAN_MAX_T + 4 : 0;
     __shared__ uint32_t smem[OFFW + 3 * TT_SLOTS + BLOCK / WAVE];
-    static_assert(sizeof(InlineScanLds) <= sizeof(uint32_t) * (INLINE_SCAN_MAX_T + 4 + 3 * TT_SLOTS), "spare blocks alias the emit blocks' LDS");
+    static_assert(sizeof(SpareScanLds) <= sizeof(uint32_t) * (INLINE_SCAN_MAX_T + 4 + 3 * TT_SLOTS), "spare blocks alias the emit blocks' LDS");
     uint32_t *s_off = smem, *s_wave = smem + OFFW + 3 * TT_SLOTS;
     // INLINE: the spare blocks come FIRST in the grid (the first of them publishes N: the host should not wait for it behind
-    // thousands of emit blocks); otherwise they follow the emit blocks as before
+    // thousands of emit blocks); otherwise they follow the emit blocks
     const unsigned nspare = gridDim.x - emit_blocks;
     const bool spare = INLINE ? blockIdx.x < nspare : blockIdx.x >= emit_blocks;
     const unsigned spare_idx = INLINE ? blockIdx.x : blockIdx.x - emit_blocks;
     const unsigned emit_idx = INLINE ? blockIdx.x - nspare : blockIdx.x;
     if (spare) {
-        if (INLINE) {
-            InlineScanLds &S = *reinterpret_cast<InlineScanLds *>(smem);
-            const int T = fu.T;
-            inline_scan_build(is.count, T, is.L, fu.sort_np, S);
-            const int t = (int)spare_idx * BLOCK + (int)threadIdx.x;
-            if (spare_idx == 0 && threadIdx.x == 0) {
-                is.scan_out[0] = S.total[0]; is.scan_out[1] = S.deepest; is.scan_out[2] = S.total[1]; is.scan_out[3] = is.L;
-                if (host_slot) publish_counts(host_slot, seq, S.total[0], S.deepest, S.total[1]);
-                is.offset[T] = S.total[0]; is.unit_first[T] = S.total[1]; is.mseg_first[T] = S.total[2];
-#pragma unroll
-                for (int k = 0; k < NCLASS + 2; k++) is.class_first[k * (T + 1) + T] = S.total[3 + k];
-            }
-            if (t < T) {
-                const int per = (T + BLOCK - 1) / BLOCK;
-                const int c0 = t / per;
-                uint32_t pre[NSCAN], tot[NSCAN];
-#pragma unroll
-                for (int k = 0; k < NSCAN; k++) { pre[k] = S.chunk[k][c0]; tot[k] = S.total[k]; }
-                for (int u = c0 * per; u < t; u++) {
-                    uint32_t q[NSCAN];
-                    tile_terms(is.count[u], is.L, q, fu.sort_np);
-#pragma unroll
-                    for (int k = 0; k < NSCAN; k++) pre[k] += q[k];
-                }
-                is.offset[t] = pre[0]; is.unit_first[t] = pre[1]; is.mseg_first[t] = pre[2];
-#pragma unroll
-                for (int k = 0; k < NCLASS + 2; k++) is.class_first[k * (T + 1) + t] = pre[3 + k];      // (a re-run of the tail reads them)
-                fill_units_tile(fu, t, is.count[t], is.L, pre, tot);
-            }
-            return;
-        }
-        // (first spare block: this frame's counts go to the host from here when the scan left that to us)
-        if (spare_idx == 0 && threadIdx.x == 0 && host_slot) publish_counts(host_slot, seq, scan_out[0], scan_out[1], scan_out[2]);
-        fill_units(fu, (int)spare_idx);
+        if (INLINE) spare_block_scan(fu, L, spare_idx, host_slot, seq, *reinterpret_cast<SpareScanLds *>(smem));
+        else fill_units(fu, (int)spare_idx);
         return;
     }
-    if (INLINE) { inline_offsets(is.count, fu.T, s_off, s_wave); tile_offset = s_off; }
+    const uint32_t *tile_offset = fu.img.tile_offset;
+    uint32_t *tile_cursor = fu.img.tile_cursor;
+    if (INLINE) { inline_offsets(fu.img.tile_count, fu.T, s_off, s_wave); tile_offset = s_off; }
     const int i = (int)emit_idx * BLOCK + threadIdx.x;
-    // (the three loads are independent: the pixel centre and the depth of a culled Gaussian are stale words that nothing reads --
-    // loading them only after `r > 0` was known put a second memory round trip into a kernel that waits 85 % of its cycles)
     // (two independent loads, 12 bytes per Gaussian: the tile rectangle preprocess_fwd counted over -- all zero for a culled Gaussian --
-    //  and the depth; rounds 1-5 read the radius and the pixel centre, i.e. every cache line of the 48-byte records for 8 bytes each)
+    //  and the depth, a stale word for a culled Gaussian that nothing reads: loading it only once the rectangle is known would put a
+    //  second memory round trip into a kernel that waits 85 % of its cycles.  Reading the radius and the pixel centre instead would
+    //  touch every cache line of the 48-byte records for 8 bytes each.)
     const ushort4 rc = i < P ? geom.rect[i] : make_ushort4(0, 0, 0, 0);
     const uint32_t dbits = i < P ? __float_as_uint(geom.depth[i]) : 0u;
     const int minx = rc.x, miny = rc.y, maxx = rc.z, maxy = rc.w;
     const int rw = maxx - minx;
     const int area = rw * (maxy - miny);
     const uint64_t key = area > 0 ? (((uint64_t)dbits << 32) | (uint32_t)i) : 0ull;
-    (void)radii; (void)gy;
     const bool small = area <= SMALL_AREA;
     const int lane = threadIdx.x & 63;
     int cx = minx, cy = miny;
@@ -507,13 +497,29 @@ __host__ __device__ __forceinline__ int sort_passes(uint64_t n)       // merge l
     return q;
 }
 
-__device__ __forceinline__ int sort_class(uint64_t n, int passes_launched, int &q)
+// How a tile of n keys is sorted when `passes_launched` merge-path passes are launched and the scratch side exists (`by_rank`),
+// and on which of the two sides -- `keys` or the scratch -- its runs lie at every step.  The launch that merges runs reads them
+// on one side and writes the other, and the last one has to land in `keys`: an odd number of merge-path passes, or the one rank
+// merge of a SORT_LDS tile, starts in the scratch.  The three sort kernels take every such decision from here.
+struct SortPlan {
+    int cls;              // SORT_*
+    int q;                // merge levels above its runs (the merge-path passes it takes when cls == SORT_MERGEPATH)
+    bool rank_merge;      // SORT_LDS with the scratch: one item per run places its keys by rank, scratch -> `keys`
+    bool runs_in_tmp;     // the presort writes the tile's runs to the scratch, not to `keys`
+    __host__ __device__ bool takes_pass(int p) const { return cls == SORT_MERGEPATH && p < q; }
+    __host__ __device__ bool pass_reads_tmp(int p) const { return ((q - p) & 1) != 0; }      // (pass p writes the other side)
+};
+
+__host__ __device__ __forceinline__ SortPlan sort_plan(uint64_t n, int passes_launched, bool by_rank)
 {
-    q = 0;
-    if (n <= (uint64_t)SORT_RUN) return SORT_SINGLE;
-    q = sort_passes(n);
-    if (q <= passes_launched) return SORT_MERGEPATH;      // passes are launched: every multi-run tile they cover takes them
-    return n <= (uint64_t)SORT_BIG_CHUNK ? SORT_LDS : SORT_FALLBACK;
+    SortPlan s{SORT_SINGLE, 0, false, false};
+    if (n <= (uint64_t)SORT_RUN) return s;
+    s.q = sort_passes(n);
+    // passes are launched: every multi-run tile they cover takes them
+    s.cls = s.q <= passes_launched ? SORT_MERGEPATH : n <= (uint64_t)SORT_BIG_CHUNK ? SORT_LDS : SORT_FALLBACK;
+    s.rank_merge = s.cls == SORT_LDS && by_rank;
+    s.runs_in_tmp = s.rank_merge || (s.cls == SORT_MERGEPATH && s.pass_reads_tmp(0));
+    return s;
 }
 
 // ---- register-resident presort ------------------------------------------------------------------------------------
@@ -605,12 +611,9 @@ __global__ void __launch_bounds__(256) tile_presort_reg_kernel(const uint32_t *t
     const uint64_t beg = tile_offset[tr.x], end64 = tile_offset[tr.x + 1];
     if (end64 > capacity) return;                 // overflowed launch: results are discarded by the host
     const long n = (long)(end64 - beg);
-    int q;
-    const int cls = sort_class((uint64_t)n, passes_launched, q);
-    if (cls == SORT_FALLBACK) return;
-    // the launch that merges the runs reads them on one side and writes the other: an odd number of merge-path passes, or the
-    // one rank-merge of a SORT_LDS tile, ends in `keys` when the runs start in the scratch
-    uint64_t *dst_base = ((cls == SORT_MERGEPATH && (q & 1)) || (cls == SORT_LDS && by_rank)) ? tmp : keys;
+    const SortPlan plan = sort_plan((uint64_t)n, passes_launched, by_rank);
+    if (plan.cls == SORT_FALLBACK) return;
+    uint64_t *dst_base = plan.runs_in_tmp ? tmp : keys;
     const long c0 = (long)tr.y * SORT_RUN;
     const int cn = (int)min((long)SORT_RUN, n - c0);
     const uint64_t *g = keys + beg + c0;
@@ -681,9 +684,9 @@ __global__ void __launch_bounds__(256) tile_mergepath_kernel(const uint32_t *til
     const uint64_t beg = tile_offset[tc.x], end64 = tile_offset[tc.x + 1];
     if (end64 > capacity) return;
     const long n = (long)(end64 - beg);
-    int q;
-    if (sort_class((uint64_t)n, passes_launched, q) != SORT_MERGEPATH || pass >= q) return;
-    const bool src_is_tmp = ((q - pass) & 1) != 0;
+    const SortPlan plan = sort_plan((uint64_t)n, passes_launched, true);      // (passes are launched only when the scratch exists)
+    if (!plan.takes_pass(pass)) return;
+    const bool src_is_tmp = plan.pass_reads_tmp(pass);
     const uint64_t *src = (src_is_tmp ? tmp : keys) + beg;
     uint64_t *dst = (src_is_tmp ? keys : tmp) + beg;
     const long w = (long)SORT_RUN << pass;
@@ -755,10 +758,9 @@ __device__ __forceinline__ bool merge_item_has_work(const uint32_t *tile_offset,
 {
     const uint64_t beg = tile_offset[tile], end64 = tile_offset[tile + 1];
     if (end64 > capacity) return false;
-    int q;
-    const int cls = sort_class(end64 - beg, passes_launched, q);
-    if (cls == SORT_LDS && by_rank) return (uint64_t)run * SORT_RUN < end64 - beg;
-    return (cls == SORT_LDS || cls == SORT_FALLBACK) && run == 0;
+    const SortPlan plan = sort_plan(end64 - beg, passes_launched, by_rank);
+    if (plan.rank_merge) return (uint64_t)run * SORT_RUN < end64 - beg;
+    return (plan.cls == SORT_LDS || plan.cls == SORT_FALLBACK) && run == 0;
 }
 
 // the n keys of a tile, sorted runs of SORT_RUN at `src`: the keys of run `run` go to their ranks in `g`
@@ -866,10 +868,9 @@ __device__ __forceinline__ void merge_tile_run(uint64_t *s, const uint32_t *tile
 {
     const uint64_t beg = tile_offset[tile];
     const long n = (long)(tile_offset[tile + 1] - beg);
-    int q;
-    const int cls = sort_class((uint64_t)n, passes_launched, q);
-    if (cls == SORT_LDS && by_rank) merge_run_by_rank(s, tmp + beg, keys + beg, (int)n, run);
-    else merge_tile_one_block(s, keys + beg, n, cls == SORT_LDS);
+    const SortPlan plan = sort_plan((uint64_t)n, passes_launched, by_rank);
+    if (plan.rank_merge) merge_run_by_rank(s, tmp + beg, keys + beg, (int)n, run);
+    else merge_tile_one_block(s, keys + beg, n, plan.cls == SORT_LDS);
 }
 
 // The items are (entry of the multi-run tile table, run 0 .. 7); how many entries there are is known on the device only.  A grid of
@@ -922,41 +923,31 @@ bool inline_scan_fits(int T, int P) { return T <= INLINE_SCAN_MAX_T && (P + BLOC
 
 int32_t launch_tile_scan(const BinningFrame &f, bool debug, hipStream_t stream)
 {
-    const ImageState &img = f.img;
-    GMS_LAUNCH(GMS_K_TILE_SCAN, stream, tile_scan_kernel<<<1, SCAN_THREADS, 0, stream>>>(img.tile_count, img.tile_offset, img.tile_cursor,
-                                                                                   img.unit_first, img.mseg_first, img.class_first, f.T, f.frame_L,
-                                                                                   f.pub_slot, f.seq, f.scan_np, img.scan_out));
+    GMS_LAUNCH(GMS_K_TILE_SCAN, stream, tile_scan_kernel<<<1, SCAN_THREADS, 0, stream>>>(f.img, f.T, f.frame_L, f.pub_slot, f.seq));
     GMS_KERNEL_CHECK(debug, stream, "tile_scan");
     return GMS_OK;
 }
 
-int32_t launch_emit_sort(const BinningFrame &f, const BinningState &bin, uint64_t capacity, uint32_t max_units, bool inl, int fill_np, int sort_np,
+int32_t launch_emit_sort(const BinningFrame &f, const BinningState &bin, uint64_t capacity, uint32_t max_units, bool inl, int sort_np,
                          bool scratch_fits, bool *presort_enqueued, bool debug, hipStream_t stream)
 {
     const ImageState &img = f.img;
     const int T = f.T;
     const uint32_t max_deep = (uint32_t)BinningState::n_deep((size_t)capacity, (size_t)T);
     const uint32_t max_multi = (uint32_t)BinningState::n_multi((size_t)capacity);
-    FillUnitsArgs fu;
-    fu.class_first = img.class_first; fu.offset = img.tile_offset; fu.mseg_first = img.mseg_first;
-    fu.unit_tile = bin.unit_tile; fu.deep_tab = bin.deep_tab; fu.multi_tab = bin.multi_tab;
-    fu.max_multi = max_multi; fu.T = T; fu.sort_np = fill_np; fu.scan_out = img.scan_out; fu.max_units = max_units;
-    fu.max_deep = max_deep;
+    const FillUnitsArgs fu{img, bin.unit_tile, bin.deep_tab, bin.multi_tab, T, max_units, max_deep, max_multi};
     const unsigned pblocks = (unsigned)((f.P + BLOCK - 1) / BLOCK), fblocks = (unsigned)((T + BLOCK - 1) / BLOCK);
-    InlineScanArgs isa{img.tile_count, img.tile_offset, img.unit_first, img.mseg_first, img.class_first, img.scan_out, f.frame_L};
     *presort_enqueued = false;
+    // (only the launch that scans publishes: on the other frames tile_scan_kernel already has)
     if (inl)
-        GMS_LAUNCH(GMS_K_EMIT, stream, emit_instances_kernel<true><<<pblocks + fblocks, BLOCK, 0, stream>>>(f.P, f.gx, f.gy, f.radii, f.geom, img.tile_offset,
-                                                                                                             img.tile_cursor, bin.keys, capacity, pblocks, fu,
-                                                                                                             f.pub_slot, f.seq, img.scan_out, isa));
+        GMS_LAUNCH(GMS_K_EMIT, stream, emit_instances_kernel<true><<<pblocks + fblocks, BLOCK, 0, stream>>>(f.P, f.gx, f.geom, bin.keys, capacity, pblocks, fu,
+                                                                                                             f.frame_L, f.pub_slot, f.seq));
     else
-        GMS_LAUNCH(GMS_K_EMIT, stream, emit_instances_kernel<false><<<pblocks + fblocks, BLOCK, 0, stream>>>(f.P, f.gx, f.gy, f.radii, f.geom, img.tile_offset,
-                                                                                                              img.tile_cursor, bin.keys, capacity, pblocks, fu,
-                                                                                                              nullptr, f.seq, img.scan_out, isa));
+        GMS_LAUNCH(GMS_K_EMIT, stream, emit_instances_kernel<false><<<pblocks + fblocks, BLOCK, 0, stream>>>(f.P, f.gx, f.geom, bin.keys, capacity, pblocks, fu,
+                                                                                                              f.frame_L, nullptr, f.seq));
     GMS_KERNEL_CHECK(debug, stream, "emit_instances");
     uint64_t *sort_tmp = reinterpret_cast<uint64_t *>(bin.seg_state);      // free until compositing
-    const uint32_t *run_total = img.class_first + NCLASS * ((size_t)T + 1) + T;
-    const uint32_t *multi_total = img.class_first + (NCLASS + 1) * ((size_t)T + 1) + T;
+    const uint32_t *run_total = scan_row(img, T, Q_SORT_RUNS) + T, *multi_total = scan_row(img, T, Q_MULTI_RUN) + T;
     GMS_LAUNCH(GMS_K_TILE_SORT, stream, tile_presort_reg_kernel<<<max_deep, 256, 0, stream>>>(img.tile_offset, run_total, bin.deep_tab, max_deep, bin.keys,
                                                                                              sort_tmp, capacity, sort_np, scratch_fits,
                                                                                              inl ? img.tile_count : nullptr, T));

@@ -76,8 +76,9 @@ struct ImageState {
     uint32_t *tile_offset;  // [T+1]   exclusive scan of tile_count; tile_offset[T] = N
     uint32_t *unit_first;   // [T+1]   exclusive scan of segments per tile; unit_first[T] = #units
     uint32_t *mseg_first;   // [T+1]   exclusive scan of segments of multi-segment tiles only
-    uint32_t *class_first;  // [8][T+1] exclusive scans per dispatch class (full, 4 partial size classes, empty), of the
-                            //          1024-key sort runs of every tile (row 6) and of the tiles with more than one run (row 7)
+    uint32_t *scan_rows;    // [8][T+1] the tile scan's other exclusive prefixes, a row each: the six dispatch classes of the unit
+                            //          table (full segments, four partial size classes, empty tiles), the 1024-key sort runs of every
+                            //          tile and the tiles with more than one run (binning.hip: ScanQuantity, scan_row)
     uint32_t *tile_dead;    // [T]     all pixels of the tile finished within the first few segments
     uint32_t *tile_cmax;    // [T]     bits of the largest |colour component| among the tile's splats (cleared by preprocess_fwd, raised by
                             //          the forward micro-tile launches that stage the tile's units): bounds the colour behind any splat in
@@ -101,7 +102,7 @@ struct ImageState {
         s.tile_offset = (uint32_t *)p; p += align_up((T + 1) * 4, 256);
         s.unit_first = (uint32_t *)p;  p += align_up((T + 1) * 4, 256);
         s.mseg_first = (uint32_t *)p;  p += align_up((T + 1) * 4, 256);
-        s.class_first = (uint32_t *)p; p += align_up(8 * (T + 1) * 4, 256);
+        s.scan_rows = (uint32_t *)p;   p += align_up(8 * (T + 1) * 4, 256);
         s.tile_dead = (uint32_t *)p;   p += align_up(T * 4, 256);
         s.tile_cmax = (uint32_t *)p;   p += align_up(T * 4, 256);
         s.scan_out = (uint32_t *)p;

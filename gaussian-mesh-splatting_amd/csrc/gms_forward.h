@@ -29,27 +29,26 @@ struct PreArgs {
 int32_t launch_preprocess_forward(const PreArgs &a, const GmsPointsArgs *points, bool fused_mesh, bool fast_layout, bool debug, hipStream_t stream);
 
 // What the binning launches of one frame share.  `pub_slot`: the pinned words the frame's counts are published to (NULL: nobody
-// reads them); `scan_np`: the merge-path passes the frame was planned with, as the scan and the unit tables receive it.
+// reads them); `planned_np`: the merge-path passes the frame was planned with (a run whose scratch is too short sorts with 0).
 struct BinningFrame {
-    int P, gx, gy, T;
-    const int *radii;
+    int P, gx, T;
     GeomState geom;
     ImageState img;
     uint32_t frame_L;        // the frame's segment length; 0: the scan chooses it from the depth
     int32_t *pub_slot;
     int32_t seq;
-    int scan_np;
+    int planned_np;
 };
 
 // K2 as a launch of its own (frames that do not scan inside the emit launch): fills the tables of `img`, clears the tile counters
 int32_t launch_tile_scan(const BinningFrame &f, bool debug, hipStream_t stream);
 // K3 + K4 on a carved BinningState of `capacity` instances and `max_units` unit records: emit (with the tile scan inside when
 // `inline_scan`: then the counts are published from here and the presort clears the tile counters), presort, `sort_np` merge-path
-// passes, merge.  `fill_np` is what the unit tables receive.  `scratch_fits`: the segment-state area holds `capacity` keys, so the
-// sort may use it as its second side (always true when sort_np > 0); without it the 1 025 .. 8 192-key tiles are merged in place by
-// one block each.  *presort_enqueued: the presort launch is in the stream.
-int32_t launch_emit_sort(const BinningFrame &f, const BinningState &bin, uint64_t capacity, uint32_t max_units, bool inline_scan, int fill_np,
-                         int sort_np, bool scratch_fits, bool *presort_enqueued, bool debug, hipStream_t stream);
+// passes, merge.  `scratch_fits`: the segment-state area holds `capacity` keys, so the sort may use it as its second side (always
+// true when sort_np > 0); without it the 1 025 .. 8 192-key tiles are merged in place by one block each.  *presort_enqueued: the
+// presort launch is in the stream.
+int32_t launch_emit_sort(const BinningFrame &f, const BinningState &bin, uint64_t capacity, uint32_t max_units, bool inline_scan, int sort_np,
+                         bool scratch_fits, bool *presort_enqueued, bool debug, hipStream_t stream);
 // merge-path passes that cover a tile of `deepest` + `headroom` keys; 0 while `deepest` itself fits the in-LDS merge
 int merge_path_passes(uint32_t deepest, uint32_t headroom);
 bool inline_scan_fits(int T, int P);               // does the emit launch of P Gaussians take the scan of T tiles inside?

@@ -399,13 +399,11 @@ struct ForwardTail {
         *launched_units = blend_grid_units(mu_launch);
         const bool inl = inline_scan && !scanned;
         scanned = true;
-        // Who sees which pass count (tile sort): the unit tables get what the runs before this one left, the sort
-        // launches what this run's buffer allows -- the sort reads its scratch in the segment-state area (very long segments)
-        const int fill_np = scratch_short ? 0 : f.scan_np;
+        // the sort's scratch is the segment-state area: too small for `capacity` keys only with very long segments
         if ((uint64_t)BinningState::n_slots((size_t)capacity, L) * 7u * TILE_PIX * 4u < capacity * 8u) scratch_short = true;
-        const int sort_np = scratch_short ? 0 : f.scan_np;
+        const int sort_np = scratch_short ? 0 : f.planned_np;
         bool presort_enqueued = false;
-        const int32_t rc = launch_emit_sort(f, bin, capacity, mu, inl, fill_np, sort_np, !scratch_short, &presort_enqueued, debug, stream);
+        const int32_t rc = launch_emit_sort(f, bin, capacity, mu, inl, sort_np, !scratch_short, &presort_enqueued, debug, stream);
         if (inl && presort_enqueued) ctr->dirty = false;          // the counters are clean again once that launch has run
         if (rc != GMS_OK) return rc;
         const BlendGrid g = make_blend_grid(W, H, f.img, bin, capacity, L);
@@ -472,9 +470,9 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
     const int32_t seq = (ts.seq_counter = ts.seq_counter == 0x7fffffff ? 1 : ts.seq_counter + 1);
     // pub_slot: the launches-only form never reads the slot, so its launches publish nothing and a captured graph does not hold this
     // thread's slot and a stale sequence number (a replay would otherwise overwrite a count an eager call on another stream has just received).
-    // scan_np: merge-path passes for tiles deeper than the in-LDS merge holds, as many as the deepest tile of the previous frame
+    // planned_np: merge-path passes for tiles deeper than the in-LDS merge holds, as many as the deepest tile of the previous frame
     // (+25 %) needs; a deeper tile than that falls back to the one-block sort and raises the count for the next frame
-    const BinningFrame bf{P, gx, gy, T, A->radii, geom, img, frame_L, A->no_host_wait ? nullptr : slot, seq,
+    const BinningFrame bf{P, gx, T, geom, img, frame_L, A->no_host_wait ? nullptr : slot, seq,
                           merge_path_passes(fs->deepest_seen, fs->deepest_seen / 4)};
     if (!inline_scan) {
         if (const int32_t rc = launch_tile_scan(bf, debug, stream)) return rc;

@@ -35,6 +35,21 @@ def ladder_A(L):
     return sorted(s)
 
 
+WIDE_GRIDS = [(257, 1), (129, 2), (41, 25), (64, 64), (65, 64)]
+
+
+def wide_counts(T):
+    """Counts for grids of hundreds to thousands of tiles, where a thread of the tile scan owns several tiles: tile t gets
+    ladder_A(256)[(7 t) % 30]; outside every eighth block of 30 tiles a length above 65 is folded to length % 66, which keeps the
+    scene at about 72 keys per tile (45 distinct lengths, the deepest 1 025)."""
+    A = ladder_A(256)
+    t = np.arange(T)
+    c = np.asarray(A, np.int64)[(7 * t) % 30]
+    fold = ((t // 30) % 8 != 0) & (c > 65)
+    c[fold] %= 66
+    return c
+
+
 def staircase(counts, gx, gy, seed=0, opacity=OP_SHORT, D=D_CAM, fovx=0.5):
     """-> (inputs, cam): tile t (row-major) of a 16 gx x 16 gy image receives exactly counts[t] Gaussians; tiles beyond
     len(counts) stay empty.  The first third of every tile with >= 4 Gaussians lies at camera depth float32(D) exactly (depth
@@ -108,3 +123,102 @@ def compare_lists(keys_u64, N_hip, details):
     raise AssertionError(f"tile lists: tile {t} (length {r1 - r0}): {kind}; first difference at entry {p - r0} of the tile: "
                          f"got id {int(ids[p])} depth bits {int(dbits[p]):#010x}, oracle id {int(pl[p])} depth bits "
                          f"{int(want_bits[p]):#010x}; {ntiles} tile(s) differ")
+
+
+# ---- the tables of the tile scan and of fill_units (csrc/binning.hip), restated, and where they lie in the scratch buffers
+SORT_RUN = 1024
+TABLE_NAMES = ("tile_offset", "unit_first", "mseg_first", "scan_rows", "scan_out", "units", "deep_tab", "multi_tab")
+
+
+def _exclusive(x):
+    return np.concatenate([[0], np.cumsum(np.asarray(x, np.int64))]).astype(np.uint32)
+
+
+def expected_tables(counts, L):
+    """What the scan and fill_units must leave for per-tile counts c[T] and segment length L.  Every prefix is exclusive with T + 1
+    entries.  `scan_rows` [8][T + 1]: full segments, the four partial classes by remainder r = c % L (>= 3/4 L, >= 1/2 L, >= 1/4 L,
+    below), empty tiles, 1 024-key sort runs of tiles with more than one key, tiles with more than one run.  `units` [U][8]: the records
+    {tile, seg, nseg, mseg_first[tile]} {offset, offset + c, 0, 0}, all full segments first (tile order, segments ascending), then each
+    partial class in tile order with seg = c // L, then the empty tiles' units with seg = 0."""
+    c = np.asarray(counts, np.int64)
+    T = len(c)
+    ns = np.maximum(1, -(-c // L))
+    r, nfull = c % L, c // L
+    runs = np.where(c > 1, -(-c // SORT_RUN), 0)
+    rows = [nfull, 4 * r >= 3 * L, (4 * r < 3 * L) & (2 * r >= L), (2 * r < L) & (4 * r >= L), (4 * r < L) & (r != 0), c == 0,
+            runs, c > SORT_RUN]
+    offset, mseg_first = _exclusive(c), _exclusive(np.where(ns > 1, ns, 0))
+    tiles = np.arange(T)
+    order = [(np.repeat(tiles, nfull), np.arange(int(nfull.sum())) - np.repeat(np.cumsum(nfull) - nfull, nfull))]
+    for k in range(1, 5):
+        sel = tiles[rows[k]]
+        order.append((sel, nfull[sel]))
+    order.append((tiles[c == 0], np.zeros(int((c == 0).sum()), np.int64)))
+    ut = np.concatenate([o[0] for o in order])
+    us = np.concatenate([o[1] for o in order])
+    units = np.zeros((len(ut), 8), np.uint32)
+    units[:, 0], units[:, 1], units[:, 2], units[:, 3] = ut, us, ns[ut], mseg_first[ut]
+    units[:, 4], units[:, 5] = offset[ut], offset[ut] + c[ut].astype(np.uint32)
+    assert len(ut) == int(ns.sum())
+    deep = np.stack([np.repeat(tiles, runs), np.arange(int(runs.sum())) - np.repeat(np.cumsum(runs) - runs, runs)], 1).astype(np.uint32)
+    return dict(tile_offset=offset, unit_first=_exclusive(ns), mseg_first=mseg_first, scan_rows=np.stack([_exclusive(x) for x in rows]),
+                scan_out=np.array([c.sum(), c.max(), ns.sum(), L], np.uint32), units=units, deep_tab=deep.reshape(-1, 2),
+                multi_tab=tiles[c > SORT_RUN].astype(np.uint32))
+
+
+def _align(v):
+    return (v + 255) // 256 * 256
+
+
+def _carve(chunks):
+    """[(name, bytes)] in order, every chunk aligned up to 256 bytes -> ({name: byte offset}, end)"""
+    at, p = {}, 0
+    for name, nbytes in chunks:
+        at[name] = p
+        p += _align(nbytes)
+    return at, p
+
+
+def image_layout(W, H):
+    """ImageState::carve / ::bytes of csrc/gms_common.h -> ({name: byte offset}, total bytes)"""
+    T = ((W + 15) // 16) * ((H + 15) // 16)
+    at, end = _carve([("final_T", W * H * 4), ("n_contrib", W * H * 4), ("tile_count", T * 4), ("tile_cursor", T * 4),
+                      ("tile_offset", (T + 1) * 4), ("unit_first", (T + 1) * 4), ("mseg_first", (T + 1) * 4), ("scan_rows", 8 * (T + 1) * 4),
+                      ("tile_dead", T * 4), ("tile_cmax", T * 4)])
+    at["scan_out"] = end
+    return at, end + 256
+
+
+def binning_layout(N, T, L, micro):
+    """BinningState::carve / ::bytes for a capacity of N instances, carved with segment length L -> ({name: byte offset}, total bytes)"""
+    n1 = max(N, 1)
+    return _carve([("keys", n1 * 8), ("units", (T + N // L + 1) * 32), ("seg_state", (2 * (N // L) + 2) * 7 * 256 * 4),
+                   ("deep_tab", (N // 1024 + T + 2) * 8), ("multi_tab", (N // 1024 + 2) * 4)] + ([("mmask", n1 * 2)] if micro else []))
+
+
+def read_tables(image, binning, W, H, capacity, L_carve, micro):
+    """The tables as a frame left them in the raw `image` and `binning` byte buffers (torch uint8, any device) -> dict as
+    `expected_tables` gives it.  The lengths of units / deep_tab / multi_tab are the totals the device wrote."""
+    T = ((W + 15) // 16) * ((H + 15) // 16)
+    ia, _ = image_layout(W, H)
+    ba, _ = binning_layout(capacity, T, L_carve, micro)
+    words = lambda buf, off, n: buf[off:off + 4 * n].view(torch.int32).cpu().numpy().view(np.uint32)
+    out = {k: words(image, ia[k], T + 1) for k in ("tile_offset", "unit_first", "mseg_first")}
+    out["scan_rows"] = words(image, ia["scan_rows"], 8 * (T + 1)).reshape(8, T + 1)
+    out["scan_out"] = words(image, ia["scan_out"], 4)
+    out["units"] = words(binning, ba["units"], 8 * int(out["unit_first"][T])).reshape(-1, 8)
+    out["deep_tab"] = words(binning, ba["deep_tab"], 2 * int(out["scan_rows"][6, T])).reshape(-1, 2)
+    out["multi_tab"] = words(binning, ba["multi_tab"], int(out["scan_rows"][7, T]))
+    return out
+
+
+def compare_tables(got, want):
+    """Every table equal, entry for entry.  Raises AssertionError naming the table and its first differing entry."""
+    for name in TABLE_NAMES:
+        a, b = np.asarray(got[name]), np.asarray(want[name])
+        if a.shape != b.shape:
+            raise AssertionError(f"tables: {name} has shape {a.shape}, expected {b.shape}")
+        bad = np.argwhere(a != b)
+        if len(bad):
+            i = tuple(int(x) for x in bad[0])
+            raise AssertionError(f"tables: {name}{list(i)} is {int(a[i])}, expected {int(b[i])}; {len(bad)} entries differ")

@@ -9,7 +9,7 @@ move a pixel by 1e-4.  tests/test_staircase_cpu.py holds the comparer's negative
 these tests from passing by accident.  After the lists, tests/test_gpu_raster.py::_check runs on the same scene under the suite's
 criterion unchanged (image, inverse depth, radii, gradients in deterministic and float-atomics mode).
 
-Sort class per tile and frame (csrc/binning.hip: `sort_class(n, passes_launched)`; the host launches
+Sort class per tile and frame (csrc/binning.hip: `sort_plan(n, passes_launched, by_rank)`; the host launches
 sort_np = sort_passes(1.25 x deepest tile of the PREVIOUS frame of this (device, stream, W, H, P)) merge-path passes when that tile was
 deeper than 8 192 keys, else none; `_sort_class` below restates both and the tests assert the table):
 
@@ -26,7 +26,13 @@ deeper than 8 192 keys, else none; `_sort_class` below restates both and the tes
 
 Segment lengths (scan_out[3], asserted per frame): ladder A runs on the micro-tile kernels with L = 256 (children: 64, 128); ladder B
 on the quadrant kernels with L = 256 on frame 1 (no capacity hint) and 512 from frame 2 (hint above 2 048 entries per tile); the
-GMS_MICRO=0 children take 128 (chosen by the scan), 256 and 512."""
+GMS_MICRO=0 children take 128 (chosen by the scan), 256 and 512.
+
+The wide grids (S.WIDE_GRIDS, 257 .. 4 160 tiles of S.wide_counts) reach what the ladders' 48 and 16 tiles cannot: scan threads that own
+several tiles, the spare emit blocks' walk to a tile inside another thread's chunk, and the 4 096-tile limit of the scan inside the emit
+launch.  There every table the scan and fill_units leave (tile_offset, unit_first, mseg_first, the eight scan rows, scan_out, the unit
+records, the run and multi-run tables) is read out of the kept buffers and held to EQUALITY with S.expected_tables, a numpy restatement
+from the per-tile counts and the frame's segment length."""
 import json
 import os
 import subprocess
@@ -61,7 +67,7 @@ def _sort_np(prev_deepest):
 
 
 def _sort_class(n, passes):
-    """sort_class of csrc/binning.hip -> (class, merge-path passes of the tile)"""
+    """the class and pass count of sort_plan, csrc/binning.hip -> (class, merge-path passes of the tile)"""
     if n <= 1:
         return "none", 0
     if n <= SORT_RUN:
@@ -72,10 +78,43 @@ def _sort_class(n, passes):
     return ("lds" if n <= SORT_BIG_CHUNK else "fallback"), q
 
 
-def _frame(inputs, kw):
-    """One forward-only frame with the scratch buffers kept -> (outputs, sorted keys, N, stats, stored final_T, scan_out words)."""
-    import diff_gaussian_rasterization as dgr
+def _carve_settings():
+    """(seg_len_min(), micro_mode()) of csrc/raster_forward.hip: the segment length and the mode the binning buffer is sized and carved
+    with in this process"""
+    e = os.environ.get("GMS_MICRO")
+    micro = True if e is None else int(e) != 0
+    v = 0
+    if "GMS_SEG_LEN" in os.environ:
+        v = (max(64, int(os.environ["GMS_SEG_LEN"])) + 63) // 64 * 64
+    if micro:
+        v = min(v or 256, 256)
+    return v or 128, micro
+
+
+def _tables(raw, st, W, H):
+    """The scan's and fill_units' tables out of the kept buffers (S.read_tables).  The restated carving is trusted only after its
+    sizes and the scan_out offset equal the library's own."""
+    lib = _lib_load()
+    N, hint = int(st["num_rendered"]), int(st["capacity_hint"])
+    cap = hint if hint > 0 and hint >= N else N
+    L_carve, micro = _carve_settings()
+    T = ((W + 15) // 16) * ((H + 15) // 16)
+    ia, ibytes = S.image_layout(W, H)
+    assert ibytes == int(lib.gms_image_bytes(W, H)) and ia["scan_out"] == int(lib.gms_image_counts_offset(W, H)), (W, H, ibytes)
+    bbytes = S.binning_layout(cap, T, L_carve, micro)[1]
+    assert bbytes == int(lib.gms_binning_bytes(cap, W, H)) and raw["binning"].numel() >= bbytes, (cap, bbytes, raw["binning"].numel())
+    return S.read_tables(raw["image"], raw["binning"], W, H, cap, L_carve, micro)
+
+
+def _lib_load():
     from diff_gaussian_rasterization import _lib
+    return _lib.load()
+
+
+def _frame(inputs, kw, with_tables=False):
+    """One forward-only frame with the scratch buffers kept -> (outputs, sorted keys, N, stats, stored final_T, scan_out words);
+    `with_tables` adds the tables of `_tables` to the stats as stats["tables"]."""
+    import diff_gaussian_rasterization as dgr
     W, H = kw["image_width"], kw["image_height"]
     dgr.keep_buffers(True)
     try:
@@ -85,8 +124,10 @@ def _frame(inputs, kw):
         raw = dgr.raw_buffers()
         keys = raw["binning"][:8 * N].view(torch.int64).cpu().numpy()
         fT = raw["image"][:4 * W * H].view(torch.float32).cpu().numpy().reshape(H, W)
-        off = int(_lib.load().gms_image_counts_offset(W, H))
+        off = int(_lib_load().gms_image_counts_offset(W, H))
         scan = raw["image"][off:off + 16].view(torch.int32).cpu().numpy().astype(np.int64)
+        if with_tables:
+            st = dict(st, tables=_tables(raw, st, W, H))
     finally:
         dgr.keep_buffers(False)
     return h, keys, N, st, fT, scan
@@ -101,12 +142,13 @@ def _assert_forward(rep, where):
     assert rep["max_amb"] <= 0.02, (where, rep)
 
 
-def _pin(inputs, kw, o, where, L=None, micro=None, hint=None):
+def _pin(inputs, kw, o, where, L=None, micro=None, hint=None, tables=False):
     """One frame: lists equal to the oracle's, forward report within _check's bounds, stored final_T within 1e-4 on unflagged pixels,
-    and the path the frame was meant to take (capacity hint or not, compositing implementation, segment length)."""
+    and the path the frame was meant to take (capacity hint or not, compositing implementation, segment length).  `tables`: the
+    scan's and fill_units' tables equal S.expected_tables of the oracle's list lengths at the frame's segment length, entry for entry."""
     det = o["details"]
     W, H = kw["image_width"], kw["image_height"]
-    h, keys, N, st, fT, scan = _frame(inputs, kw)
+    h, keys, N, st, fT, scan = _frame(inputs, kw, with_tables=tables)
     counts = det["ranges"][:, 1] - det["ranges"][:, 0]
     assert int(scan[0]) == det["N"] and int(scan[1]) == int(counts.max()) == int(st["deepest_tile"]), (where, scan, st)
     if hint is not None:
@@ -116,6 +158,8 @@ def _pin(inputs, kw, o, where, L=None, micro=None, hint=None):
     if L is not None:
         assert int(scan[3]) == L, (where, scan)
     compare_lists(keys, N, det)
+    if tables:
+        S.compare_tables(st["tables"], S.expected_tables(counts, int(scan[3])))
     rep = U.forward_report(h, o, W, H)
     _assert_forward(rep, where)
     clean = (det["pix_ambig"] & 1) == 0
@@ -217,6 +261,45 @@ def test_ladder_a_under_the_tuning_knobs(env, L, micro):
         "import test_gpu_tile_lists as TL\n"
         "TL.run_ladder_a(%d, %r, 3, tag=%r)\n"
         "print('staircase ok')\n" % (root, L, micro, tag))
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600, cwd=root)
+    for line in r.stdout.splitlines():
+        if line.startswith("STAIRCASE "):
+            print(line, flush=True)
+    assert r.returncode == 0 and "staircase ok" in r.stdout, (env, r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+
+
+def run_wide(grid, L, micro, tag="default"):
+    """S.wide_counts on `grid`: three frames (the first without history, the others on the capacity hint), each with the lists,
+    the tables of the scan and of fill_units, and the forward bounds.  No _check: gradients do not depend on the grid."""
+    import diff_gaussian_rasterization as dgr
+    inputs, cam, kw, o = _scene(S.wide_counts(grid[0] * grid[1]), grid, S.OP_SHORT, S.SEED)
+    dgr.clear_capacity_hints()
+    reps = [_pin(inputs, kw, o, f"wide {grid} {tag} frame {f + 1}", L=L, micro=micro, hint=f > 0, tables=True) for f in range(3)]
+    return _figures(f"wide {grid[0]}x{grid[1]} {tag}", reps)
+
+
+@pytest.mark.parametrize("grid", S.WIDE_GRIDS, ids=lambda g: f"{g[0]}x{g[1]}")
+def test_wide_grids_pin_the_scan_and_unit_tables(grid):
+    """Grids on which a scan thread owns 2 .. 16 tiles: 257 and 258 tiles (inline scan, two per thread, threads without a tile),
+    1 025 (stand-alone scan with two per thread, inline with five), 4 096 (the inline scan's limit, sixteen per thread in the emit
+    blocks' offset scan) and 4 160 (one past it: the stand-alone scan on hint frames too)."""
+    run_wide(grid, 256, True)
+
+
+@pytest.mark.parametrize("env", [{"GMS_INLINE_SCAN": "0"}, {"GMS_MICRO": "0"}], ids=lambda e: "-".join(f"{k[4:]}={v}" for k, v in e.items()))
+@pytest.mark.parametrize("grid", [(64, 64), (41, 25)], ids=lambda g: f"{g[0]}x{g[1]}")
+def test_wide_grids_under_the_scan_knobs(grid, env):
+    """Fresh children: the stand-alone scan on every frame, and GMS_MICRO=0, where the scan chooses the segment length itself: 128
+    (about 72 keys per tile against SEG_DEEP_PER_TILE = 512), asserted, and the expected tables are built with it."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    micro = env.get("GMS_MICRO") != "0"
+    code = (
+        "import sys, os\n"
+        "sys.path.insert(0, os.path.join(%r, 'tests'))\n"
+        "import conftest\n"
+        "import test_gpu_tile_lists as TL\n"
+        "TL.run_wide(%r, %d, %r, tag=%r)\n"
+        "print('staircase ok')\n" % (root, grid, 256 if micro else 128, micro, " ".join(f"{k}={v}" for k, v in env.items())))
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600, cwd=root)
     for line in r.stdout.splitlines():
         if line.startswith("STAIRCASE "):

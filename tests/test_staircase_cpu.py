@@ -4,7 +4,9 @@ by some pixel, no list is cut short by the T < 1e-4 stop rule (except on the opa
 pixels are flagged ambiguous -- and the negative controls of the list comparer.
 
 Measured on the scenes below (seed S.SEED): lengths exact on every ladder; last entry composited in 48 of 48 and 16 of 16 tiles;
-smallest final_T 0.29 (ladder A, L = 256), 0.146 (L = 512), 0.0188 (ladder B); flagged pixels 1.6e-4 ... 2.4e-4 (A), 3.7e-3 (B)."""
+smallest final_T 0.29 (ladder A, L = 256), 0.146 (L = 512), 0.0188 (ladder B); flagged pixels 1.6e-4 ... 2.4e-4 (A), 3.7e-3 (B).
+The wide grids (S.WIDE_GRIDS, S.wide_counts): lengths exact, flagged pixels at most 1.4e-4, smallest final_T 0.23, deepest tile 1 025
+keys, 45 distinct lengths."""
 import functools
 
 import numpy as np
@@ -19,13 +21,15 @@ SCENES = {
     "A64": (64, S.LADDER_A_GRID, S.OP_SHORT), "A128": (128, S.LADDER_A_GRID, S.OP_SHORT), "A256": (256, S.LADDER_A_GRID, S.OP_SHORT),
     "A512": (512, S.LADDER_A_GRID, S.OP_SHORT), "A256_opaque": (256, S.LADDER_A_GRID, S.OP_OPAQUE), "B": (None, S.LADDER_B_GRID, S.OP_DEEP),
 }
+WIDE = [f"wide{gx}x{gy}" for gx, gy in S.WIDE_GRIDS]
+SCENES.update({name: ("wide", grid, S.OP_SHORT) for name, grid in zip(WIDE, S.WIDE_GRIDS)})
 
 
 @functools.lru_cache(maxsize=None)
 def _scene(name):
     """(counts per tile, oracle details): one forward of the float32 oracle per scene, shared by the tests below (read-only)."""
     L, grid, op = SCENES[name]
-    counts = S.LADDER_B if L is None else S.ladder_A(L)
+    counts = S.LADDER_B if L is None else S.wide_counts(grid[0] * grid[1]) if L == "wide" else S.ladder_A(L)
     inputs, cam = S.staircase(counts, *grid, seed=S.SEED_OPAQUE if op is S.OP_OPAQUE else S.SEED, opacity=op)
     o = U.oracle_render(inputs, U.settings_kwargs(cam, torch.tensor(BG)))
     c = np.zeros(grid[0] * grid[1], np.int64)
@@ -50,7 +54,7 @@ def test_ladders_hold_the_lengths_they_are_named_for():
     assert len(S.LADDER_B) == S.LADDER_B_GRID[0] * S.LADDER_B_GRID[1]
 
 
-@pytest.mark.parametrize("name", ["A64", "A128", "A256", "A512", "A256_opaque", "B"])
+@pytest.mark.parametrize("name", ["A64", "A128", "A256", "A512", "A256_opaque", "B"] + WIDE)
 def test_oracle_list_lengths_equal_the_prescribed_counts(name):
     c, d, _ = _scene(name)
     assert np.array_equal(d["ranges"][:, 1] - d["ranges"][:, 0], c)
@@ -65,7 +69,7 @@ def test_the_last_entry_of_every_list_is_composited_and_no_list_is_cut_short(nam
     assert float(np.min(d["final_T"])) > 1e-2, float(np.min(d["final_T"]))
 
 
-@pytest.mark.parametrize("name", ["A64", "A128", "A256", "A512", "A256_opaque", "B"])
+@pytest.mark.parametrize("name", ["A64", "A128", "A256", "A512", "A256_opaque", "B"] + WIDE)
 def test_flagged_pixels_stay_below_half_of_the_parity_check_cap(name):
     _, d, _ = _scene(name)
     assert float((d["pix_ambig"] != 0).mean()) < 0.005
@@ -174,3 +178,56 @@ def test_compare_lists_rejects_a_depth_word_one_ulp_off():
     p = int(d["ranges"][TILE_8193, 0]) + 17
     keys[p] += np.uint64(1) << np.uint64(32)
     _raises_naming(keys, d["N"], d, TILE_8193, 8193, "DEPTH WORD")
+
+
+# ---- the wide grids' counts, and negative controls of compare_tables: the restated tables of the 41 x 25 grid with one defect each
+def test_wide_counts_hold_what_the_grids_are_chosen_for():
+    want = {(257, 1): 21761, (129, 2): 22786, (41, 25): 78616, (64, 64): 294273, (65, 64): 301003}
+    for grid in S.WIDE_GRIDS:
+        c = S.wide_counts(grid[0] * grid[1])
+        assert int(c.sum()) == want[grid] and int(c.max()) == 1025 and len(set(c.tolist())) == 45
+        assert (int(c.sum()) + 255) // 256 <= 1536          # the emit blocks of one frame: within the inline scan's limit
+        for L in (128, 256):
+            e = S.expected_tables(c, L)
+            assert int(e["scan_rows"][1:6, -1].sum()) == int(((c % L != 0) | (c == 0)).sum())     # a partial or an empty unit
+            assert int(e["scan_rows"][7, -1]) == int((c > 1024).sum()) >= 1
+            assert len(e["units"]) == int(e["unit_first"][-1]) == int(e["scan_out"][2]) and int(e["scan_out"][0]) == int(c.sum())
+
+
+def _wide_tables():
+    return S.expected_tables(S.wide_counts(1025), 256)
+
+
+def _tables_raise(got, name):
+    with pytest.raises(AssertionError) as e:
+        S.compare_tables(got, _wide_tables())
+    assert f"tables: {name}" in str(e.value), str(e.value)
+
+
+def test_compare_tables_accepts_the_restated_tables_and_rejects_another_segment_length():
+    S.compare_tables(_wide_tables(), _wide_tables())
+    _tables_raise(S.expected_tables(S.wide_counts(1025), 128), "unit_first")
+
+
+def test_compare_tables_rejects_two_swapped_unit_records():
+    t = _wide_tables()
+    t["units"][[40, 41]] = t["units"][[41, 40]]
+    _tables_raise(t, "units[40, 0]")
+
+
+def test_compare_tables_rejects_one_prefix_entry_off_by_one():
+    t = _wide_tables()
+    t["scan_rows"][3, 700] += 1
+    _tables_raise(t, "scan_rows[3, 700]")
+    t = _wide_tables()
+    t["mseg_first"][1025] -= 1
+    _tables_raise(t, "mseg_first[1025]")
+
+
+def test_compare_tables_rejects_a_dropped_run_table_entry():
+    t = _wide_tables()
+    t["deep_tab"] = np.delete(t["deep_tab"], 17, axis=0)
+    _tables_raise(t, "deep_tab has shape")
+    t = _wide_tables()
+    t["multi_tab"] = t["multi_tab"][:-1]
+    _tables_raise(t, "multi_tab has shape")
