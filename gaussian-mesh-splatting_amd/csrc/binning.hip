@@ -77,16 +77,7 @@ __device__ __forceinline__ void publish_counts(int32_t *host_slot, int32_t seq, 
     __hip_atomic_store(&hs[0], tag | n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-template <int WIDTH = WAVE>
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane)      // over the first WIDTH lanes
-{
-    for (int d = 1; d < WIDTH; d <<= 1) {
-        const uint32_t x = (uint32_t)__shfl_up((int)v, d);
-        if (lane >= d) v += x;
-    }
-    return v;
-}
-
+// (wave_incl_scan_u32: gms_common.h, shared with the unit order of gms_blend.h)
 // a THREADS-wide scan gives every thread scan_per consecutive tiles: thread `tid` owns [b, e) (none: threads beyond the tiles)
 template <int THREADS>
 __device__ __forceinline__ int scan_per(int T) { return (T + THREADS - 1) / THREADS; }

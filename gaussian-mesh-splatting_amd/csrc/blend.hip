@@ -211,7 +211,7 @@ __global__ void __launch_bounds__(WAVE) blend_fwd_kernel(BlendGrid g, BlendFwdOu
 // ------------------------------------------------------------------------------------ finalize
 __global__ void __launch_bounds__(BLOCK) blend_finalize_kernel(BlendGrid g, BlendFwdOut o)
 {
-    finalize_tile<4, Pix>(g, o);          // (four segments per step)
+    finalize_tile<4, Pix>(g, o, (int)blockIdx.x);          // (four segments per step)
 }
 
 // ------------------------------------------------------------------------------------ bwd
@@ -371,6 +371,10 @@ void experiment_switches(BlendGrid &g, uint32_t buf_bits, hipStream_t stream)
     }
 }
 
+// gms_set_bwd_unit_order (gmsplat.h): 0 = the finalize launch writes the identity order
+static uint32_t g_bwd_unit_order = 1;
+uint32_t bwd_unit_order() { return g_bwd_unit_order; }
+
 const BlendFamily &quadrant_family()
 {
     static const BlendFamily f = {
@@ -419,7 +423,8 @@ int32_t launch_compositing_forward(const BlendGrid &g_in, const BlendFwdOut &o, 
     GMS_KERNEL_CHECK(debug, stream, f.head_name);
     GMS_LAUNCH(GMS_K_BLEND_FWD, stream, f.fwd<<<blocks, f.threads, 0, stream>>>(g, o));
     GMS_KERNEL_CHECK(debug, stream, f.fwd_name);
-    GMS_LAUNCH(GMS_K_BLEND_FINALIZE, stream, f.finalize<<<tiles, BLOCK, 0, stream>>>(g, o));
+    // (the micro-tile family's launch begins with the blocks that build the backward's unit order, one per class: blend_micro.hip)
+    GMS_LAUNCH(GMS_K_BLEND_FINALIZE, stream, f.finalize<<<tiles + (*used_micro && g.bwd_order ? UNIT_ORDER_CLASSES : 0u), BLOCK, 0, stream>>>(g, o));
     GMS_KERNEL_CHECK(debug, stream, f.finalize_name);
     return GMS_OK;
 }
@@ -438,6 +443,8 @@ int32_t launch_compositing_backward(const BlendGrid &g_in, const BlendBwdArgs &a
 }
 
 }  // namespace gms
+
+extern "C" void gms_set_bwd_unit_order(int32_t on) { gms::g_bwd_unit_order = on ? 1u : 0u; }
 
 extern "C" int gms_debug_read(unsigned long long *host, size_t bytes)
 {

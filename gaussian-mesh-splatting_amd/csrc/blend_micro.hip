@@ -96,9 +96,21 @@ __global__ void __launch_bounds__(BLOCK) micro_tloc_check_kernel(BlendGrid g)
 }
 
 // eight segments per step (four: 10.0 us; the deepest tile of the headline frame has 27)
+// The first UNIT_ORDER_CLASSES blocks (they start first) build the backward's unit order from the costs the first-touch launches left,
+// one class each: every one of those launches precedes this one on the stream (gms_blend.h, unit_order_partition).  Then a block per tile.
 __global__ void __launch_bounds__(BLOCK) micro_finalize_kernel(BlendGrid g, BlendFwdOut o)
 {
-    finalize_tile<8, MPix>(g, o);
+    const uint32_t order_blocks = g.bwd_order ? UNIT_ORDER_CLASSES : 0u;          // (as blend.hip sizes the grid)
+    if (blockIdx.x < order_blocks) {
+        __shared__ UnitOrderLds S;
+        const uint32_t n = min(g.unit_first[g.T], g.max_units);
+        unit_order_partition(blockIdx.x, n, blend_grid_units(g.max_units), g.order_on ? UNIT_ORDER_CLASSES : 0u,
+                             [&](uint32_t i) { return (uint32_t)g.unit_cost[i]; },
+                             [&](uint32_t i) { const uint2 r = reinterpret_cast<const uint2 *>(g.unit_tile)[4 * (size_t)i + 2]; return r.x != r.y; },
+                             g.bwd_order, S);
+        return;
+    }
+    finalize_tile<8, MPix>(g, o, (int)(blockIdx.x - order_blocks));
 }
 
 // ------------------------------------------------------------------------------------ bwd
@@ -286,6 +298,7 @@ __device__ __forceinline__ uint32_t unit_stage(const BlendGrid &g, const Unit &u
             rank += (cs > c || (cs == c && s0 < tid)) ? 1u : 0u;
         }
         S.order[rank] = (uint8_t)tid; S.ocnt[rank] = (uint16_t)c;
+        if (FILTER && rank == 0) g.unit_cost[u.idx] = (uint16_t)c;          // the unit's longest list: the backward's order (gms_blend.h)
     }
     __syncthreads();
     return id;
@@ -439,6 +452,7 @@ __global__ void __launch_bounds__(BLOCK) micro_head_kernel(BlendGrid g, BlendFwd
     }
     if (u.seg > 0 && phase == 1 && g.tile_dead[u.tile]) {          // products of a dead tile: nothing to walk, empty lists on record
         if (threadIdx.x < u.end - u.beg) g.mmask[u.beg + threadIdx.x] = 0;
+        if (threadIdx.x == 0) g.unit_cost[u.idx] = 0;
         g.seg_state[(size_t)(u.slot0 + u.seg) * SEG_FLOATS + SEG_TLOC * TILE_PIX + threadIdx.x] = 0.f;
         return;
     }
@@ -517,7 +531,7 @@ __global__ void __launch_bounds__(BLOCK) micro_bwd_kernel(BlendGrid g, BlendBwdA
     Phases ph(g);
     ph.mark(0);
     Unit u;
-    if (!load_unit_at(g, u, blockIdx.x >> 3, blockIdx.x & 7u)) return;
+    if (!load_unit_at(g, u, blockIdx.x >> 3, blockIdx.x & 7u, g.bwd_order)) return;          // (longest units first: gms_blend.h)
     if (u.end <= u.beg) return;
     if (u.end - u.beg > (uint32_t)LMAX) return;             // (the host launches these kernels only on frames whose segment length fits)
     for (int k = threadIdx.x; k < LMAX * NF; k += BLOCK) fxt[k] = 0ll;

@@ -29,6 +29,9 @@ struct BlendGrid {
     uint32_t unit_run;             // consecutive units dealt to one XCD (power of two <= 64)
     unsigned long long *dbg_buf;   // GMS_DBG&16: per block {start, end} wall clock (100 MHz), else NULL
     uint16_t *mmask;               // micro mode: [capacity] block masks per instance, see BinningState
+    uint16_t *unit_cost;           // micro mode: [max_units] longest block list of every unit, left by the launch that first touches it
+    uint32_t *bwd_order;           // micro mode: [blend_grid_units(max_units)] units by rank for the backward (unit_order_partition); NULL: identity
+    uint32_t order_on;             // 0: the finalize launch writes the identity order (gms_set_bwd_unit_order)
 };
 
 struct BlendFwdOut {
@@ -71,6 +74,7 @@ bool use_micro(uint64_t capacity, int T);           // ... and is, for a frame w
 uint32_t seg_len_forced();     // GMS_SEG_LEN, or 0
 uint32_t seg_len_min();        // the forced L, or SEG_LEN_SHALLOW: what BinningState is sized and carved with
 uint32_t unit_run();
+uint32_t bwd_unit_order();     // 1, or 0 after gms_set_bwd_unit_order(0): the backward takes the units in table order
 
 // The grid of a frame as the compositing launches see it, forward and backward: the image's tile tables and a binning buffer of
 // `capacity` instances carved with segment length L (the frame's own L is in scan_out[3]).  dbg / dbg_buf: experiment_switches.
@@ -82,6 +86,8 @@ inline BlendGrid make_blend_grid(int W, int H, const ImageState &img, const Binn
     g.unit_tile = bin.unit_tile; g.keys = bin.keys; g.seg_state = bin.seg_state; g.tile_dead = img.tile_dead; g.tile_cmax = img.tile_cmax;
     g.capacity = capacity; g.max_units = (uint32_t)BinningState::n_units((size_t)capacity, (size_t)g.T, L);
     g.dbg = 0; g.unit_run = unit_run(); g.dbg_buf = nullptr; g.mmask = bin.mmask;
+    const bool micro = micro_mode();          // (the arrays exist where the binning buffer was sized for the micro-tile kernels)
+    g.unit_cost = micro ? bin.unit_cost : nullptr; g.bwd_order = micro ? bin.bwd_order : nullptr; g.order_on = bwd_unit_order();
     return g;
 }
 
@@ -387,12 +393,18 @@ struct Unit {
 // heavy image centre and the empty border are spread over all of them (units are far from equal work).
 constexpr uint32_t UNIT_RUN_MAX = 64;   // grid padding granularity; the run length itself is g.unit_run
 
-__device__ __forceinline__ bool load_unit_at(const BlendGrid &g, Unit &u, uint32_t s, uint32_t xcd)
+// `order` (the micro-tile backward): the block's index is a RANK and the unit is order[rank] (unit_order_partition below; the runs
+// dealt to an XCD are runs of ranks); UNIT_ORDER_NONE = no unit.  NULL: the identity.
+__device__ __forceinline__ bool load_unit_at(const BlendGrid &g, Unit &u, uint32_t s, uint32_t xcd, const uint32_t *order = nullptr)
 {
     const uint32_t nunits = g.unit_first[g.T];
     const uint32_t run = g.unit_run;
-    const uint32_t idx = ((s / run) * 8u + xcd) * run + (s % run);
+    uint32_t idx = ((s / run) * 8u + xcd) * run + (s % run);
     if (idx >= nunits || idx >= g.max_units) return false;   // (max_units: overflowed optimistic launch)
+    if (order) {
+        idx = order[idx];
+        if (idx >= nunits || idx >= g.max_units) return false;          // (the sentinel behind the present units)
+    }
     // one 32-byte record per unit (written by fill_units): a single round trip instead of unit -> tile tables
     const uint4 r0 = g.unit_tile[2 * (size_t)idx], r1 = g.unit_tile[2 * (size_t)idx + 1];
     u.idx = idx;
@@ -411,6 +423,82 @@ __device__ __forceinline__ bool load_unit_at(const BlendGrid &g, Unit &u, uint32
 
 __device__ __forceinline__ bool load_unit(const BlendGrid &g, Unit &u) { return load_unit_at(g, u, blockIdx.x >> 3, blockIdx.x & 7u); }
 
+// ---- The order the micro-tile backward takes the units in.  A block of micro_bwd lasts as long as its longest wave walks, and the
+// forward launch that first touches a unit knows the length of its longest block list (unit_stage: S.ocnt[0]); it leaves that as the
+// unit's cost.  The first UNIT_ORDER_CLASSES blocks of the finalize launch -- every first-touch launch precedes it on the stream -- turn
+// the costs into an order: classes of descending cost, TABLE ORDER inside a class (a stable counting partition: no atomics, so the
+// stretches of neighbouring tiles that load_unit_at deals to one XCD survive inside a class), units of empty tiles left out, sentinels
+// behind.  The order is a permutation of the present units whatever the costs hold: a cost nobody wrote (an overflowed launch) costs
+// time, not results.  Measured on the headline step with the table permuted by hand (tools/unit_order_probe.py): micro_bwd 117.2 ->
+// 110.4 us at 16 classes (8: 112.4, 32: 109.5, sorted by the measured durations themselves: 110.3).
+constexpr uint32_t UNIT_ORDER_CLASSES = 16, UNIT_ORDER_MAX_CLASSES = 32, UNIT_ORDER_NONE = 0xffffffffu;
+constexpr uint32_t UNIT_ORDER_MAX_UNITS = 64 * BLOCK;      // (one count per (pass, wave) and thread; larger frames keep the table's order)
+constexpr uint32_t UNIT_ORDER_ABSENT = 0xffu;
+struct UnitOrderLds {
+    uint8_t cls[UNIT_ORDER_MAX_UNITS];                    // class of every unit, UNIT_ORDER_ABSENT for the units left out
+    uint32_t part[BLOCK];                                 // units of the block's class among the 64 that wave w reads in pass j, at [4 j + w]
+    uint32_t wave_tot[BLOCK / WAVE], wave_less[BLOCK / WAVE];
+};
+__device__ __forceinline__ uint32_t unit_order_class(uint32_t cost, uint32_t K) { return K - 1u - min(K - 1u, cost * K / 257u); }
+
+// One block of BLOCK threads PER CLASS: block `c` of K places the units of class c.  n units, unit i present iff present(i), of cost
+// cost(i) (0 .. 65535; read for every i < n); out[0 .. nfill): the present units in classes of descending cost, table order inside a
+// class, then UNIT_ORDER_NONE (written by the last class's block).  1 <= K <= UNIT_ORDER_MAX_CLASSES; K = 0, or more units than the
+// counts hold: block 0 writes the identity over [0, n) (absent units included: they return at once in the kernels).
+// The blocks ride in a launch that lasts ~9 us and must not outlast it: every block reads all costs in ONE coalesced pass of independent
+// loads, counts what lies in front of its class and ranks its own units with ballots -- no chain of per-thread read-modify-writes.  (One
+// block for all classes, every thread counting its own stretch of the table into LDS: 22-24 us, and its 32 KB of LDS took the launch's
+// other blocks from eight per CU to five.)
+template <class Cost, class Present>
+__device__ __forceinline__ void unit_order_partition(uint32_t c, uint32_t n, uint32_t nfill, uint32_t K, Cost cost, Present present, uint32_t *out,
+                                                     UnitOrderLds &S)
+{
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    if (K == 0 || n > UNIT_ORDER_MAX_UNITS) {
+        if (c == 0) for (uint32_t i = tid; i < nfill; i += BLOCK) out[i] = i < n ? i : UNIT_ORDER_NONE;
+        return;
+    }
+    if (c >= K) return;
+    const uint32_t passes = (n + BLOCK - 1u) / BLOCK;          // <= 64: pass j, wave w -> part[4 j + w]
+    if (tid >= 4u * passes) S.part[tid] = 0;
+    uint32_t less = 0;                                         // units of this wave's lanes in the classes in front of c
+    // eight passes' loads in flight at once (index clamped, not branched; plain loops left them one round trip after the other: 18 us)
+    for (uint32_t j0 = 0; j0 < passes; j0 += 8u) {
+        uint32_t k[8]; bool p[8];
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; u++) {
+            const uint32_t ic = min((j0 + u) * BLOCK + tid, n - 1u);
+            k[u] = cost(ic); p[u] = present(ic);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 8u; u++) {
+            const uint32_t j = j0 + u, i = j * BLOCK + tid;
+            const uint32_t cl = (i < n && p[u]) ? unit_order_class(k[u], K) : UNIT_ORDER_ABSENT;
+            if (i < n) S.cls[i] = (uint8_t)cl;                  // (read back by this thread alone)
+            const uint64_t mine = __ballot(cl == c), front = __ballot(cl < c);
+            less += (uint32_t)__builtin_popcountll(front);
+            if (lane == 0 && j < passes) S.part[4u * j + wave] = (uint32_t)__builtin_popcountll(mine);
+        }
+    }
+    if (lane == 0) S.wave_less[wave] = less;
+    __syncthreads();
+    const uint32_t v = S.part[tid];
+    const uint32_t incl = wave_incl_scan_u32(v, (int)lane);
+    if (lane == WAVE - 1) S.wave_tot[wave] = incl;
+    __syncthreads();
+    uint32_t pre = incl - v, count = 0, base = 0;
+    for (uint32_t w = 0; w < BLOCK / WAVE; w++) { const uint32_t t = S.wave_tot[w]; if (w < wave) pre += t; count += t; base += S.wave_less[w]; }
+    S.part[tid] = pre;
+    __syncthreads();
+    for (uint32_t j = 0; j < passes; j++) {
+        const uint32_t i = j * BLOCK + tid;
+        const bool is = i < n && S.cls[i] == c;
+        const uint64_t m = __ballot(is);
+        if (is) out[base + S.part[4u * j + wave] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = i;
+    }
+    if (c == K - 1u) for (uint32_t i = base + count + tid; i < nfill; i += BLOCK) out[i] = UNIT_ORDER_NONE;
+}
+
 // Experiment switches (env GMS_DBG) exist only in builds made with `make EXPERIMENTS=1`;
 // in the default build every `dbg_on()` is a compile-time false and the branches disappear from the kernels.
 #ifndef GMS_EXPERIMENTS
@@ -427,7 +515,7 @@ struct Stamp {
 };
 
 // units covered by the grid the blend launches use for `max_units` (the XCD run mapping pads to 8 * UNIT_RUN_MAX blocks)
-inline uint32_t blend_grid_units(uint32_t max_units) { return 8u * UNIT_RUN_MAX * ((max_units + 8u * UNIT_RUN_MAX - 1u) / (8u * UNIT_RUN_MAX)); }
+__host__ __device__ inline uint32_t blend_grid_units(uint32_t max_units) { return 8u * UNIT_RUN_MAX * ((max_units + 8u * UNIT_RUN_MAX - 1u) / (8u * UNIT_RUN_MAX)); }
 
 void experiment_switches(BlendGrid &g, uint32_t buf_bits, hipStream_t stream);     // blend.hip; a no-op outside make EXPERIMENTS=1
 // The compositing launches of a frame (blend.hip): the one place that knows there are two kernel families and picks one

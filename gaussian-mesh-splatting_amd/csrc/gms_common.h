@@ -122,10 +122,20 @@ struct BinningState {
     // blocks its {alpha >= 1/255} ellipse touches -- written by the launch that first touches the instance's unit, read by the later
     // ones, so that every launch builds identical per-block lists.  (Until round 5: 16 bytes of list area per instance + counts.)
     uint16_t *mmask;       // [N]
+    // ... and the order the micro-tile backward takes the units in (gms_blend.h, unit_order_partition): per unit the length of its longest
+    // block list, left by the forward launch that first touches the unit, and the units by rank, built inside the finalize launch.  The two
+    // arrays lie BEHIND the tables `bytes` counts (order_bytes; the forward asks its allocator for both): the tables' layout is unchanged.
+    uint16_t *unit_cost;   // [T + N/L + 1]
+    uint32_t *bwd_order;   // [n_order]
     static __host__ __device__ size_t n_units(size_t N, size_t T, size_t L) { return T + N / L + 1; }
     static __host__ __device__ size_t n_slots(size_t N, size_t L) { return 2 * (N / L) + 2; }
     static __host__ __device__ size_t n_deep(size_t N, size_t T) { return N / 1024 + T + 2; }
     static __host__ __device__ size_t n_multi(size_t N) { return N / 1024 + 2; }
+    static __host__ __device__ size_t n_order(size_t N, size_t T, size_t L) { return (n_units(N, T, L) + 511) / 512 * 512; }      // (the blend launches' grid: gms_blend.h, blend_grid_units)
+    static __host__ __device__ size_t order_bytes(size_t N, size_t T, size_t L, bool micro)
+    {
+        return micro ? align_up(n_units(N, T, L) * 2, 256) + align_up(n_order(N, T, L) * 4, 256) : 0;
+    }
     static __host__ __device__ size_t bytes(size_t N, size_t T, size_t L, bool micro)
     {
         return align_up((N > 0 ? N : 1) * 8, 256) + align_up(n_units(N, T, L) * 32, 256) +
@@ -141,10 +151,23 @@ struct BinningState {
         b.seg_state = (float *)p;    p += align_up(n_slots(N, L) * 7 * TILE_PIX * 4, 256);
         b.deep_tab = (uint2 *)p;     p += align_up(n_deep(N, T) * 8, 256);
         b.multi_tab = (uint32_t *)p; p += align_up(n_multi(N) * 4, 256);
-        b.mmask = (uint16_t *)p;      // (present only in micro mode)
+        b.mmask = (uint16_t *)p;     p += align_up((N > 0 ? N : 1) * 2, 256);      // (this and what follows: present only in micro mode)
+        b.unit_cost = (uint16_t *)p; p += align_up(n_units(N, T, L) * 2, 256);
+        b.bwd_order = (uint32_t *)p;
         return b;
     }
 };
+
+// inclusive scan over the first WIDTH lanes of a wave (shuffles; binning.hip's tile scans and the unit order of gms_blend.h)
+template <int WIDTH = WAVE>
+__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, int lane)
+{
+    for (int d = 1; d < WIDTH; d <<= 1) {
+        const uint32_t x = (uint32_t)__shfl_up((int)v, d);
+        if (lane >= d) v += x;
+    }
+    return v;
+}
 
 // ---- wave64 reductions with DPP (row ops + row broadcasts; result valid in lane 63)
 template <int CTRL, int ROW_MASK = 0xf>

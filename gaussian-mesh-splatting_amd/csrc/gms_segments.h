@@ -104,9 +104,8 @@ __device__ __forceinline__ void tile_dead_check(const BlendGrid &g)
 // U segments per step, every load issued before the first use: a 27-segment tile is otherwise 27 dependent memory round
 // trips, and the kernel's duration is its deepest tile.
 template <int U, class P>
-__device__ __forceinline__ void finalize_tile(const BlendGrid &g, const BlendFwdOut &o)
+__device__ __forceinline__ void finalize_tile(const BlendGrid &g, const BlendFwdOut &o, const int tile)
 {
-    const int tile = blockIdx.x;
     const int nseg = (int)(g.unit_first[tile + 1] - g.unit_first[tile]);
     if (nseg <= 1) return;
     if ((uint64_t)g.tile_offset[tile + 1] > g.capacity) return;

@@ -416,7 +416,8 @@ struct ForwardTail {
 
 static void *alloc_binning(const GmsRasterForwardArgs *A, uint64_t capacity, int T, uint32_t L)
 {
-    void *mem = A->binning_alloc(A->binning_ctx, BinningState::bytes((size_t)capacity, (size_t)T, L, micro_mode()));
+    void *mem = A->binning_alloc(A->binning_ctx, BinningState::bytes((size_t)capacity, (size_t)T, L, micro_mode()) +
+                                                     BinningState::order_bytes((size_t)capacity, (size_t)T, L, micro_mode()));
     if (!mem) set_error("binning allocation callback returned NULL");
     return mem;
 }

@@ -1,6 +1,7 @@
 // test_hooks.hip -- libgmsplat_testhooks.so: device functions of the production kernels exposed for tests.  NOT part of the
 // product library (libgmsplat.so exports none of this); loaded only by tests/ through ctypes.
 //
+// gms_test_unit_order: the unit order of the micro-tile backward (gms_blend.h: unit_order_partition), tests/test_gpu_bwd_unit_order.py.
 // gms_test_cull: the conservative culls (gms_blend.h: cull_extents, rect_hit, block_mask) against the per-pixel accept test
 // (pair_power + the alpha >= 1/255 rule of the compositing kernels), all evaluated ON THE GPU by the very device functions the
 // kernels inline, on caller-supplied (splat, tile) pairs.  tests/test_gpu_cull.py feeds it the adversarial generators of
@@ -80,7 +81,40 @@ __global__ void __launch_bounds__(256) test_sh_dir_jacobian_kernel(int n, int de
     for (int j = 0; j < 9; j++) out[9 * (size_t)i + j] = D[j];
 }
 
+// gms_test_unit_order: the stable counting partition that orders the micro-tile backward's units (gms_blend.h: unit_order_partition), a
+// block per class as in the finalize launch, on caller-supplied costs and presence flags
+__global__ void __launch_bounds__(BLOCK) test_unit_order_kernel(uint32_t n, uint32_t nfill, uint32_t K, const uint16_t *cost, const uint8_t *present,
+                                                                uint32_t *out)
+{
+    __shared__ UnitOrderLds S;
+    unit_order_partition(blockIdx.x, n, nfill, K, [&](uint32_t i) { return (uint32_t)cost[i]; }, [&](uint32_t i) { return present[i] != 0; }, out, S);
+}
+
 }  // namespace gms
+
+// n units with cost[n] (uint16) and present[n] (bytes), K classes (0: the identity) -> out[nfill], nfill = n rounded up to the blend
+// launches' grid (gms_test_unit_order_fill); host buffers in and out; returns 0, -1 (K beyond the routine's limit) or a negative hipError
+extern "C" int32_t gms_test_unit_order_fill(int32_t n) { return (int32_t)gms::blend_grid_units((uint32_t)(n > 0 ? n : 1)); }
+extern "C" int32_t gms_test_unit_order(int32_t n, const uint16_t *cost_host, const uint8_t *present_host, int32_t K, uint32_t *out_host)
+{
+    if (n < 0 || K < 0 || K > (int32_t)gms::UNIT_ORDER_MAX_CLASSES) return -1;
+    const size_t nfill = (size_t)gms_test_unit_order_fill(n), na = (size_t)(n > 0 ? n : 1);
+    uint16_t *dc = nullptr; uint8_t *dp = nullptr; uint32_t *dout = nullptr;
+    hipError_t e = hipMalloc(&dc, na * 2);
+    if (e == hipSuccess) e = hipMalloc(&dp, na);
+    if (e == hipSuccess) e = hipMalloc(&dout, nfill * 4);
+    if (e == hipSuccess && n > 0) e = hipMemcpy(dc, cost_host, (size_t)n * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess && n > 0) e = hipMemcpy(dp, present_host, (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(dout, 0x5a, nfill * 4);
+    if (e == hipSuccess) {
+        gms::test_unit_order_kernel<<<(unsigned)(K > 0 ? K : 1), gms::BLOCK>>>((uint32_t)n, (uint32_t)nfill, (uint32_t)K, dc, dp, dout);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out_host, dout, nfill * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(dc); (void)hipFree(dp); (void)hipFree(dout);
+    return e == hipSuccess ? 0 : -(int32_t)e;
+}
 
 // host buffers in, host buffers out; returns 0 or a negative hipError (-1: deg outside 0..3)
 extern "C" int32_t gms_test_sh_dir_jacobian(int32_t n, int32_t deg, const float *rows_host, const float *dirs_host, float *out_host)

@@ -185,7 +185,7 @@ EXPORTS = (
     "gms_binning_bytes", "gms_profile_enable", "gms_profile_reset", "gms_profile_read", "gms_profile_kernel_name",
     "gms_knn_workspace_bytes", "gms_knn_mean_dist2", "gms_l1_ssim_partials", "gms_l1_ssim_forward",
     "gms_l1_ssim_backward", "gms_adam_step", "gms_wait_stats", "gms_last_deepest_tile", "gms_image_n_contrib_offset",
-    "gms_sh_grad_expand", "gms_set_fault", "gms_get_fault", "gms_set_deterministic", "gms_get_deterministic",
+    "gms_sh_grad_expand", "gms_set_fault", "gms_get_fault", "gms_set_bwd_unit_order", "gms_set_deterministic", "gms_get_deterministic",
     "gms_image_counts_offset", "gms_last_launched_units", "gms_last_used_micro",
     "gms_set_upstream_scale_mod_grad", "gms_get_upstream_scale_mod_grad", "gms_profile_event_overhead_us",
     "gms_points_prepare_vertices", "gms_points_to_gaussians_forward", "gms_points_to_gaussians_backward",
@@ -309,6 +309,8 @@ def load():
         lib.gms_set_fault.argtypes = [C.c_int32]
         lib.gms_set_fault.restype = None
         lib.gms_get_fault.restype = C.c_int32
+        lib.gms_set_bwd_unit_order.argtypes = [C.c_int32]
+        lib.gms_set_bwd_unit_order.restype = None
         lib.gms_profile_event_overhead_us.argtypes = [C.c_void_p, C.c_int32]
         lib.gms_profile_event_overhead_us.restype = C.c_double
         lib.gms_set_upstream_scale_mod_grad.argtypes = [C.c_int32]

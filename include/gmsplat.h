@@ -702,6 +702,12 @@ int32_t gms_get_deterministic(void);
 void gms_set_fault(int32_t fault);
 int32_t gms_get_fault(void);
 
+/* ---- test switch: the order of the micro-tile backward's units ------------------------------------
+ * The forward leaves every unit's longest block list and an order of the units by it (longest first, in classes); the backward follows
+ * it.  0: the frames enqueued from now on get the identity order instead (the table's own); anything else: the default.  Results in
+ * deterministic mode do not depend on it bit for bit; it exists so that a test can show that. */
+void gms_set_bwd_unit_order(int32_t on);
+
 /* ---- upstream-quirk switch (parity hygiene; DESIGN.md section 2 "unverifiable") --------------------
  * cov3D = R diag(mod s)^2 R^T, so the derivative with respect to the scale carries the factor mod = scale_modifier, and that is
  * what this library returns by default.  The public upstream CUDA backward (computeCov3D: `dL_dscale = dot(Rt[k], dL_dMt[k])` with

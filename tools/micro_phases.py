@@ -25,6 +25,9 @@ scene = syn.mesh_scene(wl, state="trained")
 size = scene.meta["image"]
 model = HipGaussianMeshModel.from_scene(scene, "cuda")
 cam = syn.orbit_camera(0, width=size, height=size).to("cuda"); bg = torch.ones(3, device="cuda")
+if os.environ.get("GMS_PHASES_DUMP"):
+    import diff_gaussian_rasterization as dgr
+    dgr.keep_buffers(True)          # the dump adds every unit's longest block list, recomputed from the frame's own masks
 for it in range(4):
     model.update_alpha(); model.prepare_scaling_rot()
     img = render(cam, model, PipelineParams(), bg)["render"]
@@ -61,9 +64,12 @@ print(f"trips per wave: mean {tr.mean():.1f} p50 {np.percentile(tr, 50):.0f} p90
 blk = np.nonzero(live.all(axis=0))[0]
 if os.environ.get("GMS_PHASES_DUMP"):          # per-block records for offline scheduling studies (tools/unit_order_study.py)
     w7 = b[0, blk, 7]
+    from unit_order_probe import unit_costs          # (tools/: the longest block list of every unit, from the kept masks)
+    cost, present, _ = unit_costs(dgr, lib, torch, size, size)
     np.savez_compressed(os.environ["GMS_PHASES_DUMP"], block=blk, kind=np.full(len(blk), 5), start=t[:, blk, 0].min(axis=0), staged=t[:, blk, 2].max(axis=0),
                         end=t[:, blk, 5].max(axis=0), unit=(w7 >> 40) & 0xffffff, entries=(w7 >> 28) & 0xfff, nseg=(w7 >> 14) & 0x3fff, seg=w7 & 0x3fff,
-                        tile_entries=np.zeros(len(blk)), trips=trips[:, blk].max(axis=0), trips_sum=trips[:, blk].sum(axis=0))
+                        tile_entries=np.zeros(len(blk)), trips=trips[:, blk].max(axis=0), trips_sum=trips[:, blk].sum(axis=0),
+                        unit_cost=cost, unit_present=present, unit_run=int(os.environ.get("GMS_UNIT_RUN", 4)))
 bt = t[:, blk, :]
 bdur = bt[:, :, 5].max(axis=0) - bt[:, :, 0].min(axis=0)
 wmax = (bt[:, :, 3] - bt[:, :, 2]).max(axis=0)
