@@ -997,6 +997,54 @@ std::tuple<Tensor, Tensor> image_metrics(const Tensor &img, const Tensor &gt, in
     return {xu, yu};
 }
 
+// ---------------------------------------------------------------------------------------------- LPIPS (csrc/lpips.hip)
+// img / gt [3,H,W] or [B,3,H,W]; weights / biases: the 13 packed convolutions, lins: the 5 lin vectors (games_hip/lpips.py packs them),
+// all float32, contiguous, on the images' device; rows: the caller's float64 [n,6] table, rows first_row .. first_row + B - 1 are
+// written.  Launches only.  -> the five tapped maps [2,B,C_s,H>>s,W>>s] with `want_features`, or an empty list.
+std::vector<Tensor> lpips(const Tensor &img, const Tensor &gt, const std::vector<Tensor> &weights, const std::vector<Tensor> &biases,
+                          const std::vector<Tensor> &lins, const std::vector<double> &mean, const std::vector<double> &std_, int64_t mode, Tensor rows,
+                          int64_t first_row, bool want_features)
+{
+    require_gpu(img); require_gpu(gt); require_gpu(rows);
+    TORCH_CHECK(img.sizes() == gt.sizes(), "image shapes differ");
+    TORCH_CHECK((img.dim() == 3 || img.dim() == 4) && img.size(img.dim() - 3) == 3, "lpips: images must be [3,H,W] or [B,3,H,W]");
+    TORCH_CHECK(rows.scalar_type() == torch::kDouble && rows.is_contiguous() && rows.dim() == 2 && rows.size(1) == GMS_LPIPS_ROW &&
+                rows.device() == img.device(), "lpips: rows must be a contiguous float64 [n,6] tensor on the images' device");
+    TORCH_CHECK(weights.size() == GMS_LPIPS_CONVS && biases.size() == GMS_LPIPS_CONVS && lins.size() == GMS_LPIPS_STAGES && mean.size() == 3 &&
+                std_.size() == 3, "lpips: 13 weights, 13 biases, 5 lin vectors, 3 means and 3 stds expected");
+    static const int64_t cin[GMS_LPIPS_CONVS] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512};
+    static const int64_t cout[GMS_LPIPS_CONVS] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
+    static const int64_t tapc[GMS_LPIPS_STAGES] = {64, 128, 256, 512, 512};
+    GmsLpipsWeights w{};
+    auto packed = [&](const Tensor &t, int64_t n, const char *what) {
+        TORCH_CHECK(t.scalar_type() == torch::kFloat && t.is_contiguous() && t.numel() == n && t.device() == img.device(), "lpips: ", what,
+                    " must be a contiguous float32 tensor of ", n, " elements on the images' device");
+        return t.data_ptr<float>();
+    };
+    for (int l = 0; l < GMS_LPIPS_CONVS; l++) {
+        w.weight[l] = packed(weights[l], 9 * cin[l] * cout[l], "a packed convolution weight");
+        w.bias[l] = packed(biases[l], cout[l], "a bias");
+    }
+    for (int k = 0; k < GMS_LPIPS_STAGES; k++) w.lin[k] = packed(lins[k], tapc[k], "a lin vector");
+    for (int c = 0; c < 3; c++) { w.mean[c] = (float)mean[c]; w.std[c] = (float)std_[c]; }
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(img.device());
+    Tensor x = f32c(img.detach()), y = f32c(gt.detach());
+    const int64_t d = x.dim(), B = d == 4 ? x.size(0) : 1, h = x.size(d - 2), wd = x.size(d - 1);
+    TORCH_CHECK(B <= INT32_MAX && h <= INT32_MAX && wd <= INT32_MAX, "lpips: sizes exceed int32");
+    GmsLpipsArgs a{(int32_t)B, (int32_t)h, (int32_t)wd, cf(x), cf(y), (int32_t)mode, rows.numel() ? rows.data_ptr<double>() : nullptr, rows.size(0),
+                   first_row, {nullptr, nullptr, nullptr, nullptr, nullptr}};
+    std::vector<Tensor> feats;
+    if (want_features && B > 0 && h >= 16 && wd >= 16)
+        for (int k = 0; k < GMS_LPIPS_STAGES; k++) {
+            feats.push_back(torch::empty({2, B, tapc[k], h >> k, wd >> k}, x.options()));
+            a.features[k] = feats.back().data_ptr<float>();
+        }
+    const size_t bytes = gms_lpips_workspace_bytes((int32_t)B, (int32_t)h, (int32_t)wd);
+    Tensor work = torch::empty({(int64_t)bytes}, torch::TensorOptions().dtype(torch::kUInt8).device(x.device()));
+    check_rc(gms_lpips(&w, &a, work.data_ptr(), bytes, stream_of(x)), "gms_lpips");
+    return feats;
+}
+
 // ---------------------------------------------------------------------------------------------- ground truth from bytes (csrc/images.hip)
 // src uint8 [B,H,W,C] (C 3 or 4) on the device -> (float32 [B,3,out_h,out_w], launches made).  The int32 tables of an axis that
 // changes size come from the caller (games_hip.dataset.resample_tables), on src's device; empty tensors otherwise.  Launches only.
@@ -1469,6 +1517,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("H"), py::arg("W"), py::arg("tanx"), py::arg("tany"), py::arg("mod"), py::arg("aa"), py::arg("debug"), py::arg("sh_degree"),
           py::arg("face_splat_offset") = py::none(), nogil());
     m.def("l1_ssim", &l1_ssim, "differentiable w_l1 * L1 + w_ssim * SSIM + bias; returns (value [0-dim], [l1, ssim])", nogil());
+    m.def("lpips", &lpips, "LPIPS (VGG-16) stage terms of image pairs into rows of a device table: the five tapped maps or an empty list; launches only", nogil());
     m.def("image_metrics", &image_metrics, "evaluation sums of image pairs into rows of a device table: (img_u8, gt_u8) or two empty tensors; launches only", nogil());
     m.def("ground_truth_u8", &ground_truth_u8, "decoded bytes [B,H,W,C] -> (ground truth float32 [B,3,out_h,out_w], launches made): composite, Pillow's "
           "8-bit bicubic resize, byte / 255; launches only", nogil());

@@ -100,6 +100,25 @@ class MetricsArgs(C.Structure):
     ]
 
 
+GMS_LPIPS_ROW, GMS_LPIPS_CONVS, GMS_LPIPS_STAGES = 6, 13, 5
+
+
+class LpipsWeights(C.Structure):
+    """GmsLpipsWeights (include/gmsplat.h): the packed network."""
+    _fields_ = [
+        ("weight", C.c_void_p * GMS_LPIPS_CONVS), ("bias", C.c_void_p * GMS_LPIPS_CONVS), ("lin", C.c_void_p * GMS_LPIPS_STAGES),
+        ("mean", C.c_float * 3), ("std", C.c_float * 3),
+    ]
+
+
+class LpipsArgs(C.Structure):
+    """GmsLpipsArgs (include/gmsplat.h)."""
+    _fields_ = [
+        ("pairs", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("img", C.c_void_p), ("gt", C.c_void_p), ("mode", C.c_int32),
+        ("rows", C.c_void_p), ("table_rows", C.c_int64), ("first_row", C.c_int64), ("features", C.c_void_p * GMS_LPIPS_STAGES),
+    ]
+
+
 class GroundTruthArgs(C.Structure):
     """GmsGroundTruthArgs (include/gmsplat.h)."""
     _fields_ = [
@@ -193,6 +212,7 @@ EXPORTS = (
     "gms_flame_workspace_bytes", "gms_flame_forward", "gms_flame_backward",
     "gms_densify_stats", "gms_densify_plan_workspace_bytes", "gms_densify_plan", "gms_densify_apply",
     "gms_image_metrics_workspace_bytes", "gms_image_metrics",
+    "gms_lpips_workspace_bytes", "gms_lpips",
     "gms_ground_truth_workspace_bytes", "gms_ground_truth_u8",
     "gms_resize_workspace_bytes", "gms_resize_tile_columns", "gms_resize_u8",
 )
@@ -276,6 +296,10 @@ def load():
         lib.gms_image_metrics_workspace_bytes.argtypes = [C.c_int32] * 4
         lib.gms_image_metrics.restype = C.c_int32
         lib.gms_image_metrics.argtypes = [C.POINTER(MetricsArgs), C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.gms_lpips_workspace_bytes.restype = C.c_size_t
+        lib.gms_lpips_workspace_bytes.argtypes = [C.c_int32] * 3
+        lib.gms_lpips.restype = C.c_int32
+        lib.gms_lpips.argtypes = [C.POINTER(LpipsWeights), C.POINTER(LpipsArgs), C.c_void_p, C.c_size_t, C.c_void_p]
         lib.gms_ground_truth_workspace_bytes.restype = C.c_size_t
         lib.gms_ground_truth_workspace_bytes.argtypes = [C.c_int32] * 5
         lib.gms_ground_truth_u8.restype = C.c_int32

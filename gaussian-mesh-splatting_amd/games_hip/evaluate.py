@@ -10,7 +10,12 @@ The reference says how good a model is in two places, and the two do not compute
 
 Both are quotients of a few sums over the pixels.  `MetricTable.add` enqueues one kernel pass per image pair that leaves those sums in
 a row of a device table; nothing waits for the device until `MetricTable.rows()`, the one read-back of a whole view set, and
-`metrics_from_rows` turns rows into either report on the CPU.  LPIPS is absent (it needs network weights).
+`metrics_from_rows` turns rows into either report on the CPU.
+
+LPIPS (VGG), the third number of metrics.py, is computed when the caller passes a network (`lpips=games_hip.lpips.LpipsVgg.load(...)`:
+the weight files are the caller's, nothing is fetched): `MetricTable.add(..., lpips=net)` also enqueues gms_lpips (csrc/lpips.hip,
+DESIGN.md section 19) on the same pair in the same value mode into a parallel device table, and the two tables still come back in one
+copy.  Without the keyword nothing changes and the JSON files say "LPIPS": null.
 
 GPU tensors only; there is no CPU path in the product (tests/_metrics_ref.py restates the sums in float64)."""
 from __future__ import annotations
@@ -31,6 +36,7 @@ from diff_gaussian_rasterization import _lib
 MODES = {"raw": _lib.GMS_METRIC_RAW, "clamp": _lib.GMS_METRIC_CLAMP, "quant8": _lib.GMS_METRIC_QUANT8}
 PROTOCOL_MODE = {"report": "clamp", "metrics": "quant8"}
 ROW = _lib.GMS_METRIC_ROW       # { sum |x-y|, sum ssim_map, sum (x-y)^2 of channel 0..3, H*W, channels }
+LPIPS_ROW = _lib.GMS_LPIPS_ROW  # { d_1 .. d_5, their sum }
 
 
 def _image_metrics(img, gt, mode, rows, first_row, want_u8):
@@ -69,6 +75,8 @@ class MetricTable:
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._table = torch.empty((max(int(capacity), 1), ROW), dtype=torch.float64, device=self.device)
+        self._lpips_table = None    # the parallel table of LPIPS rows: allocated by the first add(..., lpips=net)
+        self._host = None           # (rows, lpips rows) of the last read-back while nothing has been added since
         self._n = 0
         self.readbacks = 0          # device-to-host copies of metric data made so far
 
@@ -79,29 +87,56 @@ class MetricTable:
     def capacity(self) -> int:
         return int(self._table.shape[0])
 
-    def add(self, image, gt, mode: str = "clamp", want_u8: bool = False):
+    def add(self, image, gt, mode: str = "clamp", want_u8: bool = False, lpips=None):
         """image / gt: [C,H,W] or [B,C,H,W] (C 1..4) on the table's device -> the index of the first row written, or
-        (index, img_u8, gt_u8) with `want_u8` (mode "quant8": the bytes `save_image` would write)."""
+        (index, img_u8, gt_u8) with `want_u8` (mode "quant8": the bytes `save_image` would write).  `lpips`: a
+        games_hip.lpips.LpipsVgg; the pair's LPIPS row (same value mode) is enqueued as well (C = 3, H and W at least 16)."""
         images = int(image.shape[0]) if image.dim() == 4 else 1
         if self._n + images > self.capacity:            # grow: a new table and a device copy, still no wait
             grown = torch.empty((max(2 * self.capacity, self._n + images), ROW), dtype=torch.float64, device=self.device)
             grown[:self._n].copy_(self._table[:self._n])
             self._table = grown
         first = self._n
+        self._host = None
         xu, yu = _image_metrics(image, gt, MODES[mode], self._table, first, want_u8)
+        if lpips is not None:
+            from .lpips import _lpips
+            if self._lpips_table is None or int(self._lpips_table.shape[0]) < self.capacity:    # rows added without a network stay NaN
+                grown = torch.full((self.capacity, LPIPS_ROW), float("nan"), dtype=torch.float64, device=self.device)
+                if self._lpips_table is not None:
+                    grown[:self._n].copy_(self._lpips_table[:self._n])
+                self._lpips_table = grown
+            _lpips(image, gt, lpips, MODES[mode], self._lpips_table, first)
         self._n += images
         return (first, xu, yu) if want_u8 else first
 
     def _read_back(self) -> torch.Tensor:
+        """The one copy: the metric rows and, where LPIPS rows exist, those beside them (packed on the device first)."""
         self.readbacks += 1
-        return self._table[:self._n].cpu()
+        if self._lpips_table is None:
+            return self._table[:self._n].cpu()
+        both = torch.cat([self._table[:self._n], self._lpips_table[:self._n]], dim=1).cpu()
+        self._host = (both[:, :ROW].contiguous(), both[:, ROW:].contiguous())
+        return self._host[0]
 
     def rows(self) -> np.ndarray:
-        """float64 [n,8]: the ONE device-to-host copy (it waits for everything enqueued before it)."""
+        """float64 [n,8]: the ONE device-to-host copy (it waits for everything enqueued before it).  With LPIPS rows in the table
+        the copy brings both along, and `rows()` / `lpips_rows()` share it until the next `add`."""
+        if self._host is not None:
+            return self._host[0].numpy().copy()
         return self._read_back().numpy().copy()
+
+    def lpips_rows(self) -> np.ndarray:
+        """float64 [n,6] = { d_1 .. d_5, LPIPS } per pair (NaN for pairs added without a network); [0,6] if none was ever given."""
+        if self._lpips_table is None:
+            return np.zeros((0, LPIPS_ROW), np.float64)
+        if self._host is None:
+            self._read_back()
+        return self._host[1].numpy().copy()
 
     def reset(self):
         self._n = 0
+        self._host = None
 
 
 def metrics_from_rows(rows, protocol: str) -> dict:
@@ -133,7 +168,7 @@ def _default_render():
     return render
 
 
-def _evaluate(table, gaussians, cameras, pipe, background, protocol, render, want_u8=False):
+def _evaluate(table, gaussians, cameras, pipe, background, protocol, render, want_u8=False, lpips=None):
     """One render() and one add per camera -> the byte pairs (with `want_u8`).  Launches only, apart from what render() itself does."""
     render = render or _default_render()
     mode = PROTOCOL_MODE[protocol]
@@ -142,27 +177,31 @@ def _evaluate(table, gaussians, cameras, pipe, background, protocol, render, wan
         for camera in cameras:
             image = render(camera, gaussians, pipe, background)["render"]
             gt = camera.original_image[0:3].to(image.device)
-            res = table.add(image, gt, mode, want_u8)
+            res = table.add(image, gt, mode, want_u8, lpips=lpips)
             if want_u8:
                 out.append(res[1:])
     return out
 
 
-def _summary(rows, protocol):
+def _summary(rows, protocol, lpips_rows=None):
     per_view = metrics_from_rows(rows, protocol)
+    if lpips_rows is not None:
+        per_view["lpips"] = np.asarray(lpips_rows, np.float64).reshape(-1, LPIPS_ROW)[:, LPIPS_ROW - 1].copy()
     with np.errstate(invalid="ignore"):
         return {"per_view": per_view, "mean": {k: v.mean(axis=0) for k, v in per_view.items()}}
 
 
-def evaluate_views(gaussians, cameras: Sequence, pipe, background, *, protocol: str = "report", render: Optional[Callable] = None) -> dict:
+def evaluate_views(gaussians, cameras: Sequence, pipe, background, *, protocol: str = "report", render: Optional[Callable] = None,
+                   lpips=None) -> dict:
     """-> {"per_view": metrics_from_rows(...), "mean": the float64 mean of each over the views}.  Runs under no_grad; one render() and
-    one `MetricTable.add` per camera (mode clamp for "report", quant8 for "metrics"), one read-back at the end."""
+    one `MetricTable.add` per camera (mode clamp for "report", quant8 for "metrics"), one read-back at the end.  `lpips`: a
+    games_hip.lpips.LpipsVgg adds "lpips" [n] to `per_view` and its mean to `mean` (same value mode, same single read-back)."""
     cameras = list(cameras)
     if not cameras:
         raise ValueError("evaluate_views: no cameras")
     table = MetricTable(len(cameras), background.device)
-    _evaluate(table, gaussians, cameras, pipe, background, protocol, render)
-    return _summary(table.rows(), protocol)
+    _evaluate(table, gaussians, cameras, pipe, background, protocol, render, lpips=lpips)
+    return _summary(table.rows(), protocol, table.lpips_rows() if lpips is not None else None)
 
 
 def training_report(iteration, gaussians, test_cameras: Sequence, train_cameras: Sequence, pipe, background,
@@ -211,11 +250,12 @@ def write_png(path, u8_chw) -> None:
 
 
 def render_set(out_dir, name, iteration, cameras: Sequence, gaussians, pipe, background, gs_type, *, write_images: bool = True,
-               render: Optional[Callable] = None) -> dict:
+               render: Optional[Callable] = None, lpips=None) -> dict:
     """scripts/render.py::render_set and metrics.py::evaluate in one pass: every frame is evaluated in mode quant8, and the very
     bytes that were evaluated are written to <out_dir>/<name>/ours_<iteration>/renders_<gs_type>/00000.png and .../gt/00000.png.
     `results_<gs_type>.json` / `per_view_<gs_type>.json` in <out_dir> follow metrics.py's layout ({method: {"SSIM", "PSNR", "LPIPS"}})
-    with "LPIPS": null.  -> {"SSIM", "PSNR", "LPIPS": None, "per_view": {...}}."""
+    with "LPIPS": null -- or, with `lpips` (a games_hip.lpips.LpipsVgg), the mean and the per-view dict where metrics.py:81-86 puts
+    them.  -> {"SSIM", "PSNR", "LPIPS": None or the mean, "per_view": {...}}."""
     cameras = list(cameras)
     method = "ours_{}".format(iteration)
     render_path = os.path.join(out_dir, name, method, "renders_{}".format(gs_type))
@@ -223,18 +263,20 @@ def render_set(out_dir, name, iteration, cameras: Sequence, gaussians, pipe, bac
     os.makedirs(render_path, exist_ok=True)
     os.makedirs(gts_path, exist_ok=True)
     table = MetricTable(max(len(cameras), 1), background.device)
-    frames = _evaluate(table, gaussians, cameras, pipe, background, "metrics", render, want_u8=write_images)
-    res = _summary(table.rows(), "metrics")
+    frames = _evaluate(table, gaussians, cameras, pipe, background, "metrics", render, want_u8=write_images, lpips=lpips)
+    res = _summary(table.rows(), "metrics", table.lpips_rows() if lpips is not None else None)
     names = ["{0:05d}.png".format(idx) for idx in range(len(cameras))]
     if write_images:
         for fname, (img_u8, gt_u8) in zip(names, frames):
             write_png(os.path.join(render_path, fname), img_u8)
             write_png(os.path.join(gts_path, fname), gt_u8)
     ssims, psnrs = res["per_view"]["ssim"], res["per_view"]["psnr"]
-    full = {method: {"SSIM": float(res["mean"]["ssim"]), "PSNR": float(res["mean"]["psnr"]), "LPIPS": None}}
-    per_view = {method: {"SSIM": dict(zip(names, ssims.tolist())), "PSNR": dict(zip(names, psnrs.tolist())), "LPIPS": None}}
+    lpips_mean = float(res["mean"]["lpips"]) if lpips is not None else None
+    lpips_views = dict(zip(names, res["per_view"]["lpips"].tolist())) if lpips is not None else None
+    full = {method: {"SSIM": float(res["mean"]["ssim"]), "PSNR": float(res["mean"]["psnr"]), "LPIPS": lpips_mean}}
+    per_view = {method: {"SSIM": dict(zip(names, ssims.tolist())), "PSNR": dict(zip(names, psnrs.tolist())), "LPIPS": lpips_views}}
     with open(os.path.join(out_dir, "results_{}.json".format(gs_type)), "w") as fp:
         json.dump(full, fp, indent=True)
     with open(os.path.join(out_dir, "per_view_{}.json".format(gs_type)), "w") as fp:
         json.dump(per_view, fp, indent=True)
-    return {"SSIM": full[method]["SSIM"], "PSNR": full[method]["PSNR"], "LPIPS": None, "per_view": res["per_view"]}
+    return {"SSIM": full[method]["SSIM"], "PSNR": full[method]["PSNR"], "LPIPS": lpips_mean, "per_view": res["per_view"]}

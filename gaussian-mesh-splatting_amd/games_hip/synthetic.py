@@ -306,3 +306,25 @@ def flame_like_model(V: int = 5023, n_shape_full: int = 300, n_expr_full: int = 
     shapedirs = 0.01 * rng.normal(size=(V, 3, n_shape_full + n_expr_full))
     posedirs = 0.01 * rng.normal(size=((J - 1) * 9, V * 3))
     return FlameData.from_arrays(vt, shapedirs, posedirs, jr, np.asarray(parents), w, faces, n_shape_full=n_shape_full)
+
+
+# --------------------------------------------------------------------------- a VGG-16-shaped LPIPS network (no weights are shipped)
+VGG_FEATURE_INDICES = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)      # the Conv2d modules of torchvision's vgg16().features
+VGG_CHANNELS = ((3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512), (512, 512), (512, 512),
+                (512, 512), (512, 512), (512, 512))
+VGG_TAP_CHANNELS = (64, 128, 256, 512, 512)
+
+
+def vgg_like_weights(seed: int = 0):
+    """-> (features, lin): two state dicts with the architecture of LPIPS (VGG) and seeded synthetic values, in the key form of
+    torchvision's vgg16 checkpoint (`features.{i}.weight` / `.bias`) and of the original `vgg.pth` (`lin{k}.model.1.weight`
+    [1,C,1,1]).  He-scaled convolution weights (activations keep their scale through the thirteen layers), small biases,
+    non-negative lin weights of order 1/C.  A CPU generator: the same values on every machine.  What `flame_like_model` is to FLAME."""
+    g = torch.Generator().manual_seed(int(seed))
+    features, lin = {}, {}
+    for i, (cin, cout) in zip(VGG_FEATURE_INDICES, VGG_CHANNELS):
+        features[f"features.{i}.weight"] = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (9 * cin)) ** 0.5
+        features[f"features.{i}.bias"] = 0.05 * torch.randn(cout, generator=g)
+    for k, c in enumerate(VGG_TAP_CHANNELS):
+        lin[f"lin{k}.model.1.weight"] = (torch.rand(1, c, 1, 1, generator=g) * (2.0 / c)).contiguous()
+    return features, lin

@@ -548,6 +548,47 @@ typedef struct GmsMetricsArgs {
 size_t gms_image_metrics_workspace_bytes(int32_t images, int32_t channels, int32_t height, int32_t width);
 int32_t gms_image_metrics(const GmsMetricsArgs *args, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- LPIPS (VGG-16) of image pairs (csrc/lpips.hip) ---------------------------------------------
+ * The reference's third metric, metrics.py:74 `lpips(render, gt, net_type='vgg')` -> lpipsPyTorch/modules/lpips.py:30-36,
+ * networks.py:86-99 and :124-132, utils.py:6-8, at float32 precision on the exact-f32 matrix instruction (no reduced-precision path):
+ *   1. the value mode (GMS_METRIC_*, above, the same formulas) on both images, then z = (x - mean[c]) / std[c] (networks.py:86-87);
+ *   2. torchvision vgg16().features: thirteen 3x3 convolutions (padding 1, bias) each followed by ReLU, widths 64,64 | 128,128 |
+ *      256,256,256 | 512,512,512 | 512,512,512, a 2x2/2 max-pool (floor) between the groups; the zero padding of the first
+ *      convolution is applied to z (a padded tap adds 0).  Taps: the last ReLU of each group (networks.py:129);
+ *   3. every tapped map divided per pixel by sqrt(sum_c f_c^2) + 1e-10, the eps outside the root (utils.py:6-8);
+ *   4. d_s = mean over the pixels of sum_c lin_s[c] (fx_c - fy_c)^2 (lpips.py:33-34).
+ * Pair i of the call fills row first_row + i of `rows`, GMS_LPIPS_ROW doubles: { d_1, d_2, d_3, d_4, d_5, d_1 + ... + d_5 }.  The
+ * reference's forward also sums over the batch (lpips.py:36); that sum is the caller's (games_hip.lpips.lpips).
+ * Weights, in the kernel's layout -- packed ONCE by the caller with tensor operations (games_hip/lpips.py::pack_conv_weight; there is
+ * no packing entry point): convolution 0 as [27][64], k = (cin * 3 + ky) * 3 + kx; convolution l > 0 of torch shape [Cout,Cin,3,3]
+ * as [Cin / 8][ky][kx][8][Cout] (cin = 8 * slice + the index of the fourth axis).  bias[l]: [Cout].  lin[s]: [C_s], the 1x1 "lin"
+ * layer of stage s.  mean / std are the network's buffers (networks.py:77-80).
+ * features[s], each optional: receives tapped map s of both images, UN-normalised, float32 [2][pairs][C_s][H >> s][W >> s]
+ * (0: img, 1: gt; C_s = 64, 128, 256, 512, 512).
+ * Block partials are float32, added in a fixed order in double; no float atomics: the same bits run to run, stream to stream, and
+ * for a pair alone or inside a batch.  23 launches, no allocation, no host wait, no profile id.  `workspace`: caller-owned device
+ * scratch of at least gms_lpips_workspace_bytes(...) bytes (two activation buffers of 2 * pairs * 64 * H * W floats and the partials).
+ * GMS_ERR_INVALID_ARGUMENT: null pointers, negative sizes, first_row + pairs > table_rows, an unknown mode, a zero std, H or W below
+ * 16 (the fifth stage would be empty: the reference returns NaN there); GMS_ERR_CAPACITY: workspace too small.  pairs == 0: GMS_OK. */
+#define GMS_LPIPS_ROW 6
+#define GMS_LPIPS_CONVS 13
+#define GMS_LPIPS_STAGES 5
+typedef struct GmsLpipsWeights {
+    const float *weight[GMS_LPIPS_CONVS];   /* packed (above) */
+    const float *bias[GMS_LPIPS_CONVS];
+    const float *lin[GMS_LPIPS_STAGES];
+    float mean[3], std[3];
+} GmsLpipsWeights;
+typedef struct GmsLpipsArgs {
+    int32_t pairs, height, width;
+    const float *img, *gt;          /* [pairs,3,H,W] */
+    int32_t mode;                   /* GMS_METRIC_* */
+    double *rows; int64_t table_rows, first_row;   /* rows [table_rows][6] on the device */
+    float *features[GMS_LPIPS_STAGES];             /* optional outputs */
+} GmsLpipsArgs;
+size_t gms_lpips_workspace_bytes(int32_t pairs, int32_t height, int32_t width);
+int32_t gms_lpips(const GmsLpipsWeights *weights, const GmsLpipsArgs *args, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- ground-truth images from decoded bytes (csrc/images.hip) -------------------------------------
  * What the reference does to a view's image on the CPU before training sees it, on the device and with its exact results:
  *   composite  scene/dataset_readers.py:204-210: RGBA bytes over a black or white background,
