@@ -1,10 +1,24 @@
 """Device- and dtype-agnostic torch restatement of the reference's PointsGaussianModel arithmetic
 (games/flat_splatting/scene/points_gaussian_model.py:28-109, utils/general_utils.py:43-96 and :158-179), for the tests:
-evaluated in float64 it is the autograd yardstick of the HIP backward, in float32 it is checked against the committed fixture."""
+evaluated in float64 it is the autograd yardstick of the HIP backward, in float32 it is checked against the committed fixture.
+`drop=` (negative controls only, tests/test_points_cases_cpu.py) names ONE defect of the evaluation; DROPS lists them."""
 import torch
 
+DROPS = ("s2_in_r2",            # r2 = e2 / s2 with s2 detached
+         "eps_in_bwd",          # the values of the caller's eps, the derivative of the default-eps expression
+         "sign_detached",       # the quaternion's sign flip applied to the value, not carried into the gradient
+         "max_norm",            # |w|.clamp_min(eps) in place of |w| + eps under r3
+         "s3_r3_detached")      # s3 = <e3, r3> with r3 detached
 
-def rot_to_quat(M):
+
+def quat_abs(M):
+    """q_abs [P,4] of rot_to_quat_batch: the four candidates' moduli; the largest selects the candidate."""
+    m00, m01, m02, m10, m11, m12, m20, m21, m22 = torch.unbind(M.reshape(-1, 9), dim=-1)
+    x = torch.stack([1.0 + m00 + m11 + m22, 1.0 + m00 - m11 - m22, 1.0 - m00 + m11 - m22, 1.0 - m00 - m11 + m22], dim=-1)
+    return torch.where(x > 0, torch.sqrt(torch.where(x > 0, x, torch.ones_like(x))), torch.zeros_like(x))
+
+
+def rot_to_quat(M, drop=None):
     """rot_to_quat_batch on [P,3,3] (columns = frame vectors): the 0.1 floor, first-maximum argmax, standardize_quaternion."""
     m00, m01, m02, m10, m11, m12, m20, m21, m22 = torch.unbind(M.reshape(-1, 9), dim=-1)
     x = torch.stack([1.0 + m00 + m11 + m22, 1.0 + m00 - m11 - m22, 1.0 - m00 + m11 - m22, 1.0 - m00 - m11 + m22], dim=-1)
@@ -17,11 +31,12 @@ def rot_to_quat(M):
     cand = cand / (2.0 * q_abs[..., None].clamp_min(0.1))
     sel = q_abs.argmax(dim=-1)
     out = cand[torch.arange(cand.shape[0]), sel]
-    return torch.where(out[..., 0:1] < 0, -out, out)
+    flipped = torch.where(out[..., 0:1] < 0, -out, out)
+    return out + (flipped - out).detach() if drop == "sign_detached" else flipped
 
 
-def prepare_scaling_rot(triangles, eps=1e-8, drop=None):
-    """-> (_scaling [P,2], _rotation [P,4]).  `drop` (negative controls only) names one term of the frame to leave out."""
+def frame(triangles, eps=1e-8, drop=None):
+    """-> (s2 [P,1], s3 [P,1], M [P,3,3] with columns r1, r2, r3) of prepare_scaling_rot."""
     v1, v2, v3 = triangles[:, 0], triangles[:, 1], triangles[:, 2]
     _s2, _s3 = v2 - v1, v3 - v1
     r1 = torch.linalg.cross(_s2, _s3)
@@ -30,11 +45,21 @@ def prepare_scaling_rot(triangles, eps=1e-8, drop=None):
     r2 = _s2 / (s2.detach() if drop == "s2_in_r2" else s2)
     dot = lambda a, b: (a * b).sum(dim=-1, keepdim=True)
     r3 = _s3 - dot(_s3, r1) * r1 - dot(_s3, r2) * r2
-    r3 = r3 / (torch.linalg.vector_norm(r3, dim=-1, keepdim=True) + eps)
-    s3 = dot(_s3, r3)
+    n3 = torch.linalg.vector_norm(r3, dim=-1, keepdim=True)
+    r3 = r3 / (n3.clamp_min(eps) if drop == "max_norm" else n3 + eps)
+    s3 = dot(_s3, r3.detach() if drop == "s3_r3_detached" else r3)
+    return s2, s3, torch.stack([r1, r2, r3], dim=1).transpose(-2, -1)
+
+
+def prepare_scaling_rot(triangles, eps=1e-8, drop=None):
+    """-> (_scaling [P,2], _rotation [P,4]).  `drop` (negative controls only) names one defect (DROPS)."""
+    assert drop is None or drop in DROPS, drop
+    if drop == "eps_in_bwd":
+        value, graph = prepare_scaling_rot(triangles, eps), prepare_scaling_rot(triangles, 1e-8)
+        return tuple(g + (v - g).detach() for v, g in zip(value, graph))
+    s2, s3, M = frame(triangles, eps, drop)
     _scaling = torch.log(torch.cat([s2, s3], dim=1).abs())
-    M = torch.stack([r1, r2, r3], dim=1).transpose(-2, -1)
-    return _scaling, rot_to_quat(M)
+    return _scaling, rot_to_quat(M, drop)
 
 
 def getters(triangles, _opacity, eps=1e-8, eps_s0=1e-8, drop=None):
@@ -63,7 +88,7 @@ def prepare_vertices(xyz, _scaling, _rotation):
     return torch.stack([xyz, torch.where(mask, _v2, _v3), torch.where(mask, _v3, _v2)], dim=1)
 
 
-def linear_functional(triangles, _opacity, w, eps=1e-8, drop=None):
+def linear_functional(triangles, _opacity, w, eps=1e-8, drop=None, eps_s0=1e-8):
     """The fixture's L = sum(w_xyz * centre) + sum(w_scaling * get_scaling) + sum(w_rotation * get_rotation) + sum(w_opacity * get_opacity)."""
-    c, s, r, o = getters(triangles, _opacity, eps, drop=drop)
+    c, s, r, o = getters(triangles, _opacity, eps, eps_s0, drop=drop)
     return (w["w_xyz"] * c).sum() + (w["w_scaling"] * s).sum() + (w["w_rotation"] * r).sum() + (w["w_opacity"] * o).sum()
