@@ -1045,71 +1045,69 @@ std::vector<Tensor> lpips(const Tensor &img, const Tensor &gt, const std::vector
     return feats;
 }
 
-// ---------------------------------------------------------------------------------------------- ground truth from bytes (csrc/images.hip)
-// src uint8 [B,H,W,C] (C 3 or 4) on the device -> (float32 [B,3,out_h,out_w], launches made).  The int32 tables of an axis that
-// changes size come from the caller (games_hip.dataset.resample_tables), on src's device; empty tensors otherwise.  Launches only.
+// ---------------------------------------------------------------------------------------------- ground truth from bytes (csrc/images.hip, csrc/resize.hip)
+// What ground_truth_u8 and resize_u8 share: src uint8 [B,H,W,C] on the device and the int32 tables of an axis that changes size,
+// checked; the output and the workspace (`composited`: the one gms_ground_truth_u8 asks for), allocated.  The tables come from the caller (games_hip.dataset.resample_tables), on src's
+// device; empty tensors otherwise.
+struct BytesToGroundTruth {
+    int32_t B, h, w, C, out_h, out_w, hk, vk;
+    const int32_t *h_bounds, *h_coeffs, *v_bounds, *v_coeffs;
+    Tensor out, work;
+    size_t work_bytes;
+};
+BytesToGroundTruth bytes_to_ground_truth(const char *name, bool composited, const Tensor &src, int64_t out_h, int64_t out_w, const Tensor &h_bounds,
+                                         const Tensor &h_coeffs, const Tensor &v_bounds, const Tensor &v_coeffs)
+{
+    require_gpu(src);
+    TORCH_CHECK(src.dim() == 4 && src.scalar_type() == torch::kUInt8 && src.is_contiguous() && src.is_cuda(), name,
+                ": src must be a contiguous uint8 [B,H,W,C] device tensor");
+    const int64_t B = src.size(0), h = src.size(1), w = src.size(2), Cn = src.size(3);
+    TORCH_CHECK(B <= INT32_MAX && h <= INT32_MAX && w <= INT32_MAX && out_h <= INT32_MAX && out_w <= INT32_MAX && out_h > 0 && out_w > 0, name,
+                ": sizes out of range");
+    auto table = [&](const Tensor &bounds, const Tensor &coeffs, int64_t n_out, const char *axis) -> int32_t {
+        TORCH_CHECK(bounds.scalar_type() == torch::kInt && coeffs.scalar_type() == torch::kInt && bounds.is_contiguous() && coeffs.is_contiguous() &&
+                    bounds.device() == src.device() && coeffs.device() == src.device() && bounds.dim() == 2 && coeffs.dim() == 2 &&
+                    bounds.size(0) == n_out && bounds.size(1) == 2 && coeffs.size(0) == n_out && coeffs.size(1) >= 1 && coeffs.size(1) <= INT32_MAX,
+                    name, ": the ", axis, " tables must be contiguous int32 [n_out,2] and [n_out,kmax] on src's device");
+        return (int32_t)coeffs.size(1);
+    };
+    BytesToGroundTruth g{(int32_t)B, (int32_t)h, (int32_t)w, (int32_t)Cn, (int32_t)out_h, (int32_t)out_w};
+    g.hk = out_w != w ? table(h_bounds, h_coeffs, out_w, "horizontal") : 0;
+    g.vk = out_h != h ? table(v_bounds, v_coeffs, out_h, "vertical") : 0;
+    g.h_bounds = g.hk ? h_bounds.data_ptr<int32_t>() : nullptr; g.h_coeffs = g.hk ? h_coeffs.data_ptr<int32_t>() : nullptr;
+    g.v_bounds = g.vk ? v_bounds.data_ptr<int32_t>() : nullptr; g.v_coeffs = g.vk ? v_coeffs.data_ptr<int32_t>() : nullptr;
+    TORCH_CHECK(src.numel() > 0, name, ": empty batch or image");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(src.device());
+    g.out = torch::empty({B, 3, out_h, out_w}, torch::TensorOptions().dtype(torch::kFloat).device(src.device()));
+    g.work_bytes = composited ? gms_ground_truth_workspace_bytes(g.B, g.h, g.w, g.out_h, g.out_w) : gms_resize_workspace_bytes(g.B, g.h, g.w, g.C, g.out_h, g.out_w);
+    g.work = torch::empty({(int64_t)g.work_bytes}, torch::TensorOptions().dtype(torch::kUInt8).device(src.device()));
+    return g;
+}
+
+// src uint8 [B,H,W,C] (C 3 or 4) on the device -> (float32 [B,3,out_h,out_w], launches made).  Launches only.
 std::tuple<Tensor, int64_t> ground_truth_u8(const Tensor &src, bool white_background, int64_t out_h, int64_t out_w, const Tensor &h_bounds,
                                             const Tensor &h_coeffs, const Tensor &v_bounds, const Tensor &v_coeffs)
 {
-    require_gpu(src);
-    TORCH_CHECK(src.dim() == 4 && src.scalar_type() == torch::kUInt8 && src.is_contiguous() && src.is_cuda(),
-                "ground_truth_u8: src must be a contiguous uint8 [B,H,W,C] device tensor");
-    const int64_t B = src.size(0), h = src.size(1), w = src.size(2), Cn = src.size(3);
-    TORCH_CHECK(B <= INT32_MAX && h <= INT32_MAX && w <= INT32_MAX && out_h <= INT32_MAX && out_w <= INT32_MAX && out_h > 0 && out_w > 0,
-                "ground_truth_u8: sizes out of range");
-    auto table = [&](const Tensor &bounds, const Tensor &coeffs, int64_t n_out, const char *axis) -> int32_t {
-        TORCH_CHECK(bounds.scalar_type() == torch::kInt && coeffs.scalar_type() == torch::kInt && bounds.is_contiguous() && coeffs.is_contiguous() &&
-                    bounds.device() == src.device() && coeffs.device() == src.device() && bounds.dim() == 2 && coeffs.dim() == 2 &&
-                    bounds.size(0) == n_out && bounds.size(1) == 2 && coeffs.size(0) == n_out && coeffs.size(1) >= 1 && coeffs.size(1) <= INT32_MAX,
-                    "ground_truth_u8: the ", axis, " tables must be contiguous int32 [n_out,2] and [n_out,kmax] on src's device");
-        return (int32_t)coeffs.size(1);
-    };
-    const int32_t hk = out_w != w ? table(h_bounds, h_coeffs, out_w, "horizontal") : 0;
-    const int32_t vk = out_h != h ? table(v_bounds, v_coeffs, out_h, "vertical") : 0;
+    BytesToGroundTruth g = bytes_to_ground_truth("ground_truth_u8", true, src, out_h, out_w, h_bounds, h_coeffs, v_bounds, v_coeffs);
     c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(src.device());
-    Tensor out = torch::empty({B, 3, out_h, out_w}, torch::TensorOptions().dtype(torch::kFloat).device(src.device()));
-    TORCH_CHECK(src.numel() > 0, "ground_truth_u8: empty batch or image");
-    const size_t bytes = gms_ground_truth_workspace_bytes((int32_t)B, (int32_t)h, (int32_t)w, (int32_t)out_h, (int32_t)out_w);
-    Tensor work = torch::empty({(int64_t)bytes}, torch::TensorOptions().dtype(torch::kUInt8).device(src.device()));
-    GmsGroundTruthArgs a{(int32_t)B, (int32_t)h, (int32_t)w, (int32_t)Cn, src.data_ptr<uint8_t>(), white_background ? 1 : 0, (int32_t)out_h, (int32_t)out_w,
-                         hk ? h_bounds.data_ptr<int32_t>() : nullptr, hk ? h_coeffs.data_ptr<int32_t>() : nullptr, hk,
-                         vk ? v_bounds.data_ptr<int32_t>() : nullptr, vk ? v_coeffs.data_ptr<int32_t>() : nullptr, vk, out.data_ptr<float>()};
-    const int32_t launches = gms_ground_truth_u8(&a, work.data_ptr(), bytes, stream_of(src));
+    GmsGroundTruthArgs a{g.B, g.h, g.w, g.C, src.data_ptr<uint8_t>(), white_background ? 1 : 0, g.out_h, g.out_w, g.h_bounds, g.h_coeffs, g.hk,
+                         g.v_bounds, g.v_coeffs, g.vk, g.out.data_ptr<float>()};
+    const int32_t launches = gms_ground_truth_u8(&a, g.work.data_ptr(), g.work_bytes, stream_of(src));
     check_rc(launches, "gms_ground_truth_u8");
-    return {out, (int64_t)launches};
+    return {g.out, (int64_t)launches};
 }
 
-// ---------------------------------------------------------------------------------------------- Pillow's resize to the ground truth (csrc/resize.hip)
-// src uint8 [B,H,W,C] (C 3 or 4) on the device -> (float32 [B,3,out_h,out_w], launches made); the tables as for ground_truth_u8.
+// The same without the composite (csrc/resize.hip): Pillow's resize of the source bytes themselves.
 std::tuple<Tensor, int64_t> resize_u8(const Tensor &src, int64_t out_h, int64_t out_w, const Tensor &h_bounds, const Tensor &h_coeffs,
                                       const Tensor &v_bounds, const Tensor &v_coeffs)
 {
-    require_gpu(src);
-    TORCH_CHECK(src.dim() == 4 && src.scalar_type() == torch::kUInt8 && src.is_contiguous() && src.is_cuda(),
-                "resize_u8: src must be a contiguous uint8 [B,H,W,C] device tensor");
-    const int64_t B = src.size(0), h = src.size(1), w = src.size(2), Cn = src.size(3);
-    TORCH_CHECK(B <= INT32_MAX && h <= INT32_MAX && w <= INT32_MAX && out_h <= INT32_MAX && out_w <= INT32_MAX && out_h > 0 && out_w > 0,
-                "resize_u8: sizes out of range");
-    auto table = [&](const Tensor &bounds, const Tensor &coeffs, int64_t n_out, const char *axis) -> int32_t {
-        TORCH_CHECK(bounds.scalar_type() == torch::kInt && coeffs.scalar_type() == torch::kInt && bounds.is_contiguous() && coeffs.is_contiguous() &&
-                    bounds.device() == src.device() && coeffs.device() == src.device() && bounds.dim() == 2 && coeffs.dim() == 2 &&
-                    bounds.size(0) == n_out && bounds.size(1) == 2 && coeffs.size(0) == n_out && coeffs.size(1) >= 1 && coeffs.size(1) <= INT32_MAX,
-                    "resize_u8: the ", axis, " tables must be contiguous int32 [n_out,2] and [n_out,kmax] on src's device");
-        return (int32_t)coeffs.size(1);
-    };
-    const int32_t hk = out_w != w ? table(h_bounds, h_coeffs, out_w, "horizontal") : 0;
-    const int32_t vk = out_h != h ? table(v_bounds, v_coeffs, out_h, "vertical") : 0;
+    BytesToGroundTruth g = bytes_to_ground_truth("resize_u8", false, src, out_h, out_w, h_bounds, h_coeffs, v_bounds, v_coeffs);
     c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(src.device());
-    TORCH_CHECK(src.numel() > 0, "resize_u8: empty batch or image");
-    Tensor out = torch::empty({B, 3, out_h, out_w}, torch::TensorOptions().dtype(torch::kFloat).device(src.device()));
-    const size_t bytes = gms_resize_workspace_bytes((int32_t)B, (int32_t)h, (int32_t)w, (int32_t)Cn, (int32_t)out_h, (int32_t)out_w);
-    Tensor work = torch::empty({(int64_t)bytes}, torch::TensorOptions().dtype(torch::kUInt8).device(src.device()));
-    GmsResizeArgs a{(int32_t)B, (int32_t)h, (int32_t)w, (int32_t)Cn, src.data_ptr<uint8_t>(), (int32_t)out_h, (int32_t)out_w,
-                    hk ? h_bounds.data_ptr<int32_t>() : nullptr, hk ? h_coeffs.data_ptr<int32_t>() : nullptr, hk,
-                    vk ? v_bounds.data_ptr<int32_t>() : nullptr, vk ? v_coeffs.data_ptr<int32_t>() : nullptr, vk, out.data_ptr<float>()};
-    const int32_t launches = gms_resize_u8(&a, work.data_ptr(), bytes, stream_of(src));
+    GmsResizeArgs a{g.B, g.h, g.w, g.C, src.data_ptr<uint8_t>(), g.out_h, g.out_w, g.h_bounds, g.h_coeffs, g.hk, g.v_bounds, g.v_coeffs, g.vk,
+                    g.out.data_ptr<float>()};
+    const int32_t launches = gms_resize_u8(&a, g.work.data_ptr(), g.work_bytes, stream_of(src));
     check_rc(launches, "gms_resize_u8");
-    return {out, (int64_t)launches};
+    return {g.out, (int64_t)launches};
 }
 
 // ---------------------------------------------------------------------------------------------- pseudo-mesh bound to a guide mesh

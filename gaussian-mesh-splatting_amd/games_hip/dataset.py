@@ -410,37 +410,50 @@ def _tables_on(device, in_size, out_size, cache: Optional[dict]):
     return pair
 
 
-def ground_truth_u8(src: torch.Tensor, white_background: bool, size: Optional[Tuple[int, int]] = None, tables: Optional[dict] = None) -> torch.Tensor:
-    """uint8 [B,H,W,C] (C 3 or 4) on the GPU -> float32 [B,3,out_h,out_w]: composite over the background, Pillow's bicubic resize to
-    `size` = (width, height) when given, byte / 255.  Launches only; `last_launches` holds how many.  `tables`: a dict in which a caller
-    that resizes many batches keeps the coefficient tables on src's device (load_cameras does); without it they are uploaded per call."""
+def _bytes_to_ground_truth(name: str, src: torch.Tensor, white_background: Optional[bool], size, tables) -> torch.Tensor:
+    """What ground_truth_u8 and resize_u8 share; `white_background` None: nothing is composited (resize_u8)."""
     global last_launches
     import diff_gaussian_rasterization as _dgr
     from diff_gaussian_rasterization import _lib
     if not src.is_cuda:
-        raise RuntimeError("ground_truth_u8: the images must live on a GPU (there is no CPU path in the product)")
+        raise RuntimeError(name + ": the images must live on a GPU (there is no CPU path in the product)")
     if src.dim() != 4 or src.dtype != torch.uint8:
-        raise ValueError("ground_truth_u8: src must be uint8 [B,H,W,C]")
+        raise ValueError(name + ": src must be uint8 [B,H,W,C]")
     src = src.contiguous()
     b, h, w, c = (int(v) for v in src.shape)
     ow, oh = (int(size[0]), int(size[1])) if size is not None else (w, h)
     empty = torch.empty((0, 2), dtype=torch.int32, device=src.device)
     hb, hc = _tables_on(src.device, w, ow, tables) if ow != w else (empty, empty)
     vb, vc = _tables_on(src.device, h, oh, tables) if oh != h else (empty, empty)
+    composite = white_background is not None
     if _dgr._C is not None:
-        out, last_launches = _dgr._C.ground_truth_u8(src, bool(white_background), oh, ow, hb, hc, vb, vc)
+        if composite:
+            out, last_launches = _dgr._C.ground_truth_u8(src, bool(white_background), oh, ow, hb, hc, vb, vc)
+        else:
+            out, last_launches = _dgr._C.resize_u8(src, oh, ow, hb, hc, vb, vc)
         return out
     lib = _lib.load()
     with _lib.on_device(src.device):
         out = torch.empty((b, 3, oh, ow), dtype=torch.float32, device=src.device)
-        nbytes = lib.gms_ground_truth_workspace_bytes(b, h, w, oh, ow)
+        nbytes = lib.gms_ground_truth_workspace_bytes(b, h, w, oh, ow) if composite else lib.gms_resize_workspace_bytes(b, h, w, c, oh, ow)
         work = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
-        args = _lib.GroundTruthArgs(images=b, height=h, width=w, channels=c, src=_lib.ptr(src), white_background=int(bool(white_background)),
-                                    out_height=oh, out_width=ow, h_bounds=_lib.ptr(hb), h_coeffs=_lib.ptr(hc), h_kmax=int(hc.shape[1]) if ow != w else 0,
-                                    v_bounds=_lib.ptr(vb), v_coeffs=_lib.ptr(vc), v_kmax=int(vc.shape[1]) if oh != h else 0, out=_lib.ptr(out))
-        rc = lib.gms_ground_truth_u8(C.byref(args), work.data_ptr(), nbytes, C.c_void_p(_lib.stream_ptr(src.device)))
-    last_launches = _lib.check(rc, "gms_ground_truth_u8")
+        shared = dict(images=b, height=h, width=w, channels=c, src=_lib.ptr(src), out_height=oh, out_width=ow,
+                      h_bounds=_lib.ptr(hb), h_coeffs=_lib.ptr(hc), h_kmax=int(hc.shape[1]) if ow != w else 0,
+                      v_bounds=_lib.ptr(vb), v_coeffs=_lib.ptr(vc), v_kmax=int(vc.shape[1]) if oh != h else 0, out=_lib.ptr(out))
+        if composite:
+            args, call = _lib.GroundTruthArgs(white_background=int(bool(white_background)), **shared), lib.gms_ground_truth_u8
+        else:
+            args, call = _lib.ResizeArgs(**shared), lib.gms_resize_u8
+        rc = call(C.byref(args), work.data_ptr(), nbytes, C.c_void_p(_lib.stream_ptr(src.device)))
+    last_launches = _lib.check(rc, "gms_" + name)
     return out
+
+
+def ground_truth_u8(src: torch.Tensor, white_background: bool, size: Optional[Tuple[int, int]] = None, tables: Optional[dict] = None) -> torch.Tensor:
+    """uint8 [B,H,W,C] (C 3 or 4) on the GPU -> float32 [B,3,out_h,out_w]: composite over the background, Pillow's bicubic resize to
+    `size` = (width, height) when given, byte / 255.  Launches only; `last_launches` holds how many.  `tables`: a dict in which a caller
+    that resizes many batches keeps the coefficient tables on src's device (load_cameras does); without it they are uploaded per call."""
+    return _bytes_to_ground_truth("ground_truth_u8", src, bool(white_background), size, tables)
 
 
 def resize_u8(src: torch.Tensor, size: Optional[Tuple[int, int]] = None, tables: Optional[dict] = None) -> torch.Tensor:
@@ -448,33 +461,7 @@ def resize_u8(src: torch.Tensor, size: Optional[Tuple[int, int]] = None, tables:
     byte / 255, nothing composited (csrc/resize.hip): the ground truth of COLMAP images.  RGBA takes the premultiplied route and
     loses its alpha.  One launch per axis that changes, one at an unchanged size; `last_launches` holds how many.  `tables` as for
     ground_truth_u8."""
-    global last_launches
-    import diff_gaussian_rasterization as _dgr
-    from diff_gaussian_rasterization import _lib
-    if not src.is_cuda:
-        raise RuntimeError("resize_u8: the images must live on a GPU (there is no CPU path in the product)")
-    if src.dim() != 4 or src.dtype != torch.uint8:
-        raise ValueError("resize_u8: src must be uint8 [B,H,W,C]")
-    src = src.contiguous()
-    b, h, w, c = (int(v) for v in src.shape)
-    ow, oh = (int(size[0]), int(size[1])) if size is not None else (w, h)
-    empty = torch.empty((0, 2), dtype=torch.int32, device=src.device)
-    hb, hc = _tables_on(src.device, w, ow, tables) if ow != w else (empty, empty)
-    vb, vc = _tables_on(src.device, h, oh, tables) if oh != h else (empty, empty)
-    if _dgr._C is not None:
-        out, last_launches = _dgr._C.resize_u8(src, oh, ow, hb, hc, vb, vc)
-        return out
-    lib = _lib.load()
-    with _lib.on_device(src.device):
-        out = torch.empty((b, 3, oh, ow), dtype=torch.float32, device=src.device)
-        nbytes = lib.gms_resize_workspace_bytes(b, h, w, c, oh, ow)
-        work = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
-        args = _lib.ResizeArgs(images=b, height=h, width=w, channels=c, src=_lib.ptr(src), out_height=oh, out_width=ow,
-                               h_bounds=_lib.ptr(hb), h_coeffs=_lib.ptr(hc), h_kmax=int(hc.shape[1]) if ow != w else 0,
-                               v_bounds=_lib.ptr(vb), v_coeffs=_lib.ptr(vc), v_kmax=int(vc.shape[1]) if oh != h else 0, out=_lib.ptr(out))
-        rc = lib.gms_resize_u8(C.byref(args), work.data_ptr(), nbytes, C.c_void_p(_lib.stream_ptr(src.device)))
-    last_launches = _lib.check(rc, "gms_resize_u8")
-    return out
+    return _bytes_to_ground_truth("resize_u8", src, None, size, tables)
 
 
 # ------------------------------------------------------------------------------------------------ cameras

@@ -589,7 +589,7 @@ typedef struct GmsLpipsArgs {
 size_t gms_lpips_workspace_bytes(int32_t pairs, int32_t height, int32_t width);
 int32_t gms_lpips(const GmsLpipsWeights *weights, const GmsLpipsArgs *args, void *workspace, size_t workspace_bytes, void *stream);
 
-/* ---- ground-truth images from decoded bytes (csrc/images.hip) -------------------------------------
+/* ---- ground-truth images from decoded bytes (csrc/images.hip, the resize by csrc/resize.hip) ------
  * What the reference does to a view's image on the CPU before training sees it, on the device and with its exact results:
  *   composite  scene/dataset_readers.py:204-210: RGBA bytes over a black or white background,
  *              byte = trunc((c/255.0 * (a/255.0) + bg * (1 - a/255.0)) * 255.0) in float64, in that operation order (the integer
@@ -600,14 +600,17 @@ int32_t gms_lpips(const GmsLpipsWeights *weights, const GmsLpipsArgs *args, void
  *              (games_hip.dataset.resample_tables restates Pillow's precompute_coeffs): bounds [n_out][2] = (first tap, tap count),
  *              coeffs [n_out][kmax] int32 with 22 fractional bits, both on the device;
  *              out = clip8(((1 << 21) + sum_i coeffs[i] * pixel[first + i]) >> 22).  Taps that would leave the axis are cut.
+ *              The kernels are those of gms_resize_u8 (below), run on the composited pixels.
  *   to float   scene/cameras.py:39 / utils/general_utils.py:103: (float) byte / 255.0f, the IEEE quotient.
  * src: uint8 [images,height,width,channels] interleaved; out: float32 [images,3,out_height,out_width] planar.  Every result is exact
  * (bytes equal, floats bit-equal to the reference's).  One launch at native size, one more per resized axis; no allocation, no host
- * wait, no atomics, no profile id.  `workspace`: caller-owned device scratch of at least gms_ground_truth_workspace_bytes(...) bytes,
- * read only when a size changes (NULL allowed otherwise).
+ * wait, no atomics, no profile id.  `workspace`: caller-owned device scratch, read only when a size changes (NULL allowed otherwise) and
+ * then 16-byte aligned, of at least gms_ground_truth_workspace_bytes(...) bytes: with align16(n) = (n + 15) & ~15, the composited
+ * pixels at four bytes each, align16(images*height*width*4), plus, when both axes change, the horizontal pass's
+ * align16(images*height*out_width*4); 16 at native size.
  * Returns the number of kernel launches made (1..3), or GMS_ERR_INVALID_ARGUMENT: null pointers (args, src, out, the tables of an axis
- * that changes, the workspace of a resize), sizes <= 0, more than 65 535 images, channels outside {3, 4}, white_background outside
- * {0, 1}; GMS_ERR_CAPACITY: workspace too small. */
+ * that changes, the workspace of a resize), a misaligned workspace of a resize, sizes <= 0, more than 65 535 images, channels outside
+ * {3, 4}, white_background outside {0, 1}; GMS_ERR_CAPACITY: workspace too small. */
 typedef struct GmsGroundTruthArgs {
     int32_t images, height, width, channels;
     const uint8_t *src;                             /* [images,height,width,channels] */
@@ -626,7 +629,8 @@ int32_t gms_ground_truth_u8(const GmsGroundTruthArgs *args, void *workspace, siz
  * resampled, RGBa -> RGBA) and the colours are kept, alpha dropped; at an unchanged size Pillow returns a copy and no premultiply
  * round trip happens.  src: uint8 [images,height,width,channels] interleaved (4-byte aligned for channels == 4 when a size changes);
  * out: float32 [images,3,out_height,out_width] planar, bit-equal to Pillow's bytes / 255.  The tables are those of
- * gms_ground_truth_u8.  Launches: 1 at an unchanged size, 1 when one axis changes, 2 when both do (pixels [images,height,out_width]
+ * gms_ground_truth_u8, which runs these same kernels after its composite and shares this entry point's argument checks: the library
+ * has one resampler.  Launches: 1 at an unchanged size, 1 when one axis changes, 2 when both do (pixels [images,height,out_width]
  * of four bytes each, for RGB too, pass through `workspace`, 16-byte aligned, at least gms_resize_workspace_bytes(...) bytes,
  * read only then; NULL allowed otherwise).  No allocation, no host wait, no atomics, no profile id.
  * The horizontal pass stages each tile's input span in LDS; gms_resize_tile_columns gives the output columns of a tile (64 or 32)

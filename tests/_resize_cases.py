@@ -1,5 +1,6 @@
 """Shapes and inputs of the resize tests (tests/test_resize_ref_cpu.py against Pillow on the host, tests/test_gpu_resize.py on the
-kernels of csrc/resize.hip): the smallest sizes at which each path of the kernels runs.
+kernels of csrc/resize.hip, tests/test_gpu_ground_truth.py on the same kernels after the composite): the smallest sizes at which each
+path of the kernels runs.
 
 A horizontal tile is 64 (or 32) output columns x 16 rows; a staged row holds 1056 bytes, four per pixel for RGB as for RGBA.
 `tile_columns` restates the budget rule of csrc/resize.hip (gms_resize_tile_columns; tests/test_resize_abi_cpu.py compares the two)."""

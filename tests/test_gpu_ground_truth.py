@@ -1,4 +1,4 @@
-"""GPU: the ground-truth kernels (csrc/images.hip) against the reference's own results (tests/golden/gt_images.npz, written by
+"""GPU: the ground-truth kernels (csrc/images.hip, and csrc/resize.hip for a resize) against the reference's own results (tests/golden/gt_images.npz, written by
 tests/golden/make_gt_golden.py from `readCamerasFromTransforms`, `Image.resize` and `loadCam`).  Everything is exact: the bytes are
 equal and the floats are bit-equal.  Needs neither Pillow nor the reference tree.
 
@@ -10,7 +10,10 @@ import numpy as np
 import pytest
 import torch
 
+import functools
+
 import _gt_cases as G
+import _resize_cases as RC
 from games_hip import dataset as D
 
 pytestmark = pytest.mark.gpu
@@ -148,6 +151,40 @@ def test_composite_resize_and_float_in_one_call_is_the_references_original_image
     native, launches = _run(G.pattern_rgba(37, 29)[None], white, D.target_resolution(37, 29, 1))
     assert launches == 1          # native resolution: RGBA bytes to float ground truth in ONE launch
     assert np.array_equal(native[0].view(np.uint32), golden["gt_pattern_37x29_%s_r1" % tag].view(np.uint32))
+
+
+# every shape at which a path of the tiled resize (csrc/resize.hip) runs, through the composite; the batch of three where the head
+# and the tail chunks of a batch differ from an image's own
+TILED_CASES = [(name, 1) for name in sorted(RC.cases())] + [("odd_53x37_to_16x11", 3), ("tiles_of_32_three_wide_420_to_70", 3)]
+SOURCES = {"rgba_on_black": (4, False), "rgba_on_white": (4, True), "rgb": (3, False)}
+
+
+@functools.lru_cache(maxsize=None)
+def _host_ground_truth(name, source, k):
+    """float32 [3,oh,ow] from host functions the CPU tests hold to the reference and to Pillow: composite_table (test_dataset_ref_cpu),
+    resample_numpy on these shapes (test_resize_ref_cpu), float32(byte) / float32(255)."""
+    channels, white = SOURCES[source]
+    img = RC.image(name, channels, k)
+    if channels == 4:
+        img = D.composite_table(white)[img[:, :, :3], img[:, :, 3:4]]
+    _, _, ow, oh = RC.cases()[name]
+    out = np.ascontiguousarray(D.resample_numpy(img, ow, oh).transpose(2, 0, 1)).astype(np.float32) / np.float32(255)
+    out.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("source", sorted(SOURCES))
+@pytest.mark.parametrize("case", TILED_CASES, ids=["%s_batch%d" % c for c in TILED_CASES])
+def test_every_path_of_the_tiled_resize_after_the_composite(case, source):
+    name, batch = case
+    w, h, ow, oh = RC.cases()[name]
+    channels, white = SOURCES[source]
+    out, launches = _run(np.stack([RC.image(name, channels, k) for k in range(batch)]), white, (ow, oh))
+    assert out.shape == (batch, 3, oh, ow) and out.dtype == np.float32
+    for k in range(batch):
+        want = _host_ground_truth(name, source, k)
+        assert np.array_equal(out[k].view(np.uint32), want.view(np.uint32)), f"{name} {source} image {k}: floats differ in bits"
+    assert launches == 1 + (ow != w) + (oh != h)
 
 
 def test_both_bindings_give_the_same_bits(golden, monkeypatch):

@@ -47,8 +47,8 @@ def test_ctypes_table_resolves_the_symbols_and_the_abi_stays():
     assert lib.gms_ground_truth_workspace_bytes.restype is C.c_size_t
     ws = lib.gms_ground_truth_workspace_bytes
     assert ws(1, 800, 800, 800, 800) == 16                                  # native size: nothing is staged
-    assert ws(2, 29, 37, 14, 37) == 2 * 3 * 29 * 37 + 10                    # one axis: the composite's byte planes (padded to 16)
-    assert ws(2, 29, 37, 14, 18) == (2 * 3 * 29 * 37 + 10) + (2 * 3 * 29 * 18 + 4)      # both: + the horizontal pass's
+    assert ws(2, 29, 37, 14, 37) == 8592                                    # one axis: the composite's four-byte pixels, 2*29*37*4 = 8584 padded to 16
+    assert ws(2, 29, 37, 14, 18) == 8592 + 4176                             # both: + the horizontal pass's, 2*29*18*4
     assert ws(0, 10, 10, 10, 10) > 0 and ws(1, 0, 10, 5, 5) > 0
 
 
@@ -86,4 +86,6 @@ def test_null_args_and_a_missing_or_small_workspace():
     assert lib.gms_ground_truth_u8(None, None, 0, None) == INVALID
     resize = dict(out_width=2, h_bounds=0x3000, h_coeffs=0x4000, h_kmax=5)
     assert lib.gms_ground_truth_u8(C.byref(_args(_lib, **resize)), None, 0, None) == INVALID          # a resize stages bytes
+    assert lib.gms_ground_truth_u8(C.byref(_args(_lib, **resize)), 0x5008, 1 << 20, None) == INVALID  # and reads them as 16-byte words
+    assert b"16-byte aligned" in lib.gms_last_error()
     assert lib.gms_ground_truth_u8(C.byref(_args(_lib, **resize)), 0x5000, 8, None) == CAPACITY

@@ -1,18 +1,21 @@
 #!/usr/bin/env python3
-"""Device time of the two resize routes on images of a COLMAP photograph's size, and one end-to-end load.
+"""Device time of the resize on images of a COLMAP photograph's size and of the composited ground truth
+(section 15), and one end-to-end load.
 
-  routes      B same-sized images already on the device, default 4946x3286 -> 1600x1063 (what `--resolution -1` gives): the tiled
-              route (games_hip.dataset.resize_u8, csrc/resize.hip) against the planar one (ground_truth_u8, csrc/images.hip) on the
-              same bytes.  The routes alternate in one process after a warm-up; 7 rounds of `--calls` calls between device events;
-              median and spread (max - min) of the rounds.  The outputs of the two must be equal (RGB; for RGBA the planar route
-              composites, which is another image: only the tiled route is timed).
+  resize      B same-sized images already on the device, default 4946x3286 -> 1600x1063 (what `--resolution -1` gives), through
+              games_hip.dataset.resize_u8 (csrc/resize.hip).  After a warm-up, 7 rounds of `--calls` calls between device events;
+              median and spread (max - min) of the rounds.
+  ground_truth  the same protocol on games_hip.dataset.ground_truth_u8 (composite, the same resize, / 255): 8 RGBA images of 800x800
+              over white to 400x400, 200x200 and 100x100 (a Blender scene at resolutions 2, 4 and 8), and one RGB photograph of
+              `--width` x `--height` at resolution -1.  It calls nothing but that function, so a copy of this file in another
+              checkout's tools/ times that checkout.
   load        a directory of `--images` RGB photographs of that size read with resolution -1: ours (read_colmap_scene + load_cameras, to
               the last camera resident), the 8-thread decode alone, and a numpy + Pillow restatement of the reference's steps on the same
               files, one image at a time as it does them (scene/dataset_readers.py:97-99, utils/camera_utils.py:19-52,
               utils/general_utils.py:101-107, scene/cameras.py:39-46).  The restatement lives here because a machine with a GPU need
               not hold a reference tree; it is the yardstick, not the code under test.
 
-Prints one JSON line per part.    python tools/resize_time.py [--part routes|load|all] [--batch 1 4] [--width 4946 --height 3286]"""
+Prints one JSON line per measurement.    python tools/resize_time.py [--part resize|ground_truth|load|all] [--batch 1 4] [--width 4946 --height 3286]"""
 import argparse
 import json
 import os
@@ -41,37 +44,48 @@ def photograph(width, height, channels, k):
     return (img.clip(0, 1) * 255 + 0.5).astype(np.uint8)
 
 
-def time_routes(width, height, batch, channels, calls):
+def time_calls(fn, calls):
+    """-> {"median", "spread", "rounds"} in us per call: a warm-up (tables uploaded, allocator primed), then ROUNDS rounds of `calls` calls."""
+    import torch
+    fn()
+    fn()
+    torch.cuda.synchronize()
+    t = []
+    for _ in range(ROUNDS):
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        for _ in range(calls):
+            fn()
+        stop.record()
+        stop.synchronize()
+        t.append(start.elapsed_time(stop) * 1000.0 / calls)
+    return {"median": round(float(np.median(t)), 1), "spread": round(max(t) - min(t), 1), "rounds": [round(v, 1) for v in t]}
+
+
+def time_resize(width, height, batch, channels, calls):
     import torch
     from games_hip import dataset as D
     size = D.target_resolution(width, height, -1)
     src = torch.from_numpy(np.stack([photograph(width, height, channels, k) for k in range(batch)])).cuda()
     tables = {}
-    routes = {"tiled": lambda: D.resize_u8(src, size, tables)}
-    if channels == 3:
-        routes["planar"] = lambda: D.ground_truth_u8(src, False, size, tables)
-    outs = {name: fn() for name, fn in routes.items()}          # warm-up: tables uploaded, allocator primed
-    launches = {}
-    for name, fn in routes.items():
-        fn()
-        launches[name] = D.last_launches
-    torch.cuda.synchronize()
-    equal = torch.equal(outs["tiled"], outs["planar"]) if "planar" in outs else None
-    times = {name: [] for name in routes}
-    for _ in range(ROUNDS):
-        for name, fn in routes.items():
-            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            start.record()
-            for _ in range(calls):
-                fn()
-            stop.record()
-            stop.synchronize()
-            times[name].append(start.elapsed_time(stop) * 1000.0 / calls)
-    row = {"part": "routes", "in": [width, height], "out": list(size), "batch": batch, "channels": channels, "calls_per_round": calls,
-           "rounds": ROUNDS, "outputs_equal": equal, "launches": launches}
-    for name, t in times.items():
-        row[name + "_us"] = {"median": round(float(np.median(t)), 1), "spread": round(max(t) - min(t), 1), "rounds": [round(v, 1) for v in t]}
-    return row
+    us = time_calls(lambda: D.resize_u8(src, size, tables), calls)
+    return {"part": "resize", "in": [width, height], "out": list(size), "batch": batch, "channels": channels, "calls_per_round": calls,
+            "rounds": ROUNDS, "launches": D.last_launches, "us": us}
+
+
+def time_ground_truth(width, height, calls):
+    import torch
+    from games_hip import dataset as D
+    rows = []
+    blender = torch.from_numpy(np.stack([photograph(800, 800, 4, k) for k in range(8)])).cuda()
+    photo = torch.from_numpy(photograph(width, height, 3, 0)[None]).cuda()
+    for src, size in ((blender, (400, 400)), (blender, (200, 200)), (blender, (100, 100)), (photo, D.target_resolution(width, height, -1))):
+        tables = {}
+        us = time_calls(lambda: D.ground_truth_u8(src, True, size, tables), calls)
+        b, h, w, c = src.shape
+        rows.append({"part": "ground_truth", "in": [w, h], "out": list(size), "batch": b, "channels": c, "white_background": True,
+                     "calls_per_round": calls, "rounds": ROUNDS, "launches": D.last_launches, "us": us})
+    return rows
 
 
 def reference_restatement(records, resolution, device):
@@ -139,7 +153,7 @@ def time_load(width, height, images, distinct, skip_reference):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("routes", "load", "all"), default="all")
+    ap.add_argument("--part", choices=("resize", "ground_truth", "load", "all"), default="all")
     ap.add_argument("--width", type=int, default=4946)
     ap.add_argument("--height", type=int, default=3286)
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 4])
@@ -148,10 +162,13 @@ def main():
     ap.add_argument("--distinct", type=int, default=8, help="PNG files encoded; the rest of --images are copies of them")
     ap.add_argument("--skip-reference", action="store_true")
     a = ap.parse_args()
-    if a.part in ("routes", "all"):
+    if a.part in ("resize", "all"):
         for batch in a.batch:
             for channels in (3, 4):
-                print(json.dumps(time_routes(a.width, a.height, batch, channels, a.calls)), flush=True)
+                print(json.dumps(time_resize(a.width, a.height, batch, channels, a.calls)), flush=True)
+    if a.part in ("ground_truth", "all"):
+        for row in time_ground_truth(a.width, a.height, a.calls):
+            print(json.dumps(row), flush=True)
     if a.part in ("load", "all"):
         print(json.dumps(time_load(a.width, a.height, a.images, a.distinct, a.skip_reference)), flush=True)
 
