@@ -24,9 +24,11 @@ struct PreArgs {
     float *k0_xyz, *k0_scale, *k0_rot, *k0_opac;   // ... and stored here for the backward (training frames; NULL: forward-only frame)
 };
 
-// K1.  Picks the instantiation: the frame straight from pseudo-triangles (`points`), straight from the mesh (`fused_mesh`, a.mesh), or
-// from tensors -- at the active degree a.D when `fast_layout` (M = 16, 16-byte aligned rows), else the generic-width kernel.
-int32_t launch_preprocess_forward(const PreArgs &a, const GmsPointsArgs *points, bool fused_mesh, bool fast_layout, bool debug, hipStream_t stream);
+// K1.  Picks the instantiation: the frame straight from a free model's raw parameters (`free_args`), from pseudo-triangles (`points`),
+// straight from the mesh (`fused_mesh`, a.mesh), or from tensors -- at the active degree a.D when `fast_layout` (M = 16, 16-byte aligned
+// rows), else the generic-width kernel.
+int32_t launch_preprocess_forward(const PreArgs &a, const GmsPointsArgs *points, const GmsFreeArgs *free_args, bool fused_mesh, bool fast_layout,
+                                  bool debug, hipStream_t stream);
 
 // What the binning launches of one frame share.  `pub_slot`: the pinned words the frame's counts are published to (NULL: nobody
 // reads them); `planned_np`: the merge-path passes the frame was planned with (a run whose scratch is too short sorts with 0).

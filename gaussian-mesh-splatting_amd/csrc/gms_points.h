@@ -5,6 +5,7 @@
 // both users produce the same bits.
 #pragma once
 #include "gms_common.h"
+#include "gms_free.h"
 #include "gms_mesh.h"
 
 namespace gms {
@@ -50,15 +51,13 @@ struct PointsOut { float log_s[2], q_raw[4]; };
 __device__ __forceinline__ void points_params(const PointsFrame &f, float eps_s0, float op_raw, SplatParams &o, PointsOut *raw)
 {
 #pragma clang fp contract(off)
-    o.opacity = 1.f / (1.f + expf(-op_raw));
+    o.opacity = sigmoid_act(op_raw);          // (the getters' statements are gms_free.h's: one source for the points and the free frames)
     o.xyz[0] = f.t0.x; o.xyz[1] = f.t0.y; o.xyz[2] = f.t0.z;
     const float l2 = logf(fabsf(f.s2)), l3 = logf(fabsf(f.s3));
     o.scale[0] = eps_s0; o.scale[1] = expf(l2); o.scale[2] = expf(l3);
     float q[4];
     rot_to_quat(f.r1, f.r2, f.r3, q, nullptr);
-    // torch.nn.functional.normalize: q / max(|q|, 1e-12)
-    const float n = fmaxf(sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]), 1e-12f);
-    o.q[0] = q[0] / n; o.q[1] = q[1] / n; o.q[2] = q[2] / n; o.q[3] = q[3] / n;
+    normalize_quat(q, o.q);
     if (raw) {
         raw->log_s[0] = l2; raw->log_s[1] = l3;
 #pragma unroll

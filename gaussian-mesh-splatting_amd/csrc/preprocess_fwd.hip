@@ -11,6 +11,7 @@
 #include "gms_blend.h"
 #include "gms_mesh.h"
 #include "gms_points.h"
+#include "gms_free.h"
 #include "gms_common.h"
 #include "gms_project.h"
 #include "gms_forward.h"
@@ -77,13 +78,17 @@ __device__ __forceinline__ void store_sh_ddir(float *sh_ddir, int i, const float
 // PTS (ABI 9; forward-only frames of the gs_points drivers, scripts/render_points_time_animated.py): the same from the Gaussian's own
 // pseudo-triangle -- 36 bytes of triangle and 4 of raw opacity in, the statements of points_fwd_kernel (gms_points.h) -- `pts` is only
 // read by that instantiation.
-template <int SHDEG, bool SPLIT, bool DMA = false, bool K0 = false, bool PTS = false>
-__device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsPointsArgs &pts = GmsPointsArgs{})
+// FREE (gms_rasterize_forward_free; training frames of gs / gs_flat models): the centre is loaded as ever, scale / rotation / opacity are
+// the getters of the raw rows -- 4 S + 16 + 4 bytes in, the statements of free_fwd_kernel (gms_free.h) -- `fr` is only read by that
+// instantiation.
+template <int SHDEG, bool SPLIT, bool DMA = false, bool K0 = false, bool PTS = false, bool FREE = false>
+__device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsPointsArgs &pts = GmsPointsArgs{}, const GmsFreeArgs &fr = GmsFreeArgs{})
 {
 #pragma clang fp contract(off)
     static_assert(!DMA || (SHDEG >= 0 && SHDEG <= 3 && SPLIT), "the LDS-DMA staging exists for split degree-3 STORAGE (any active degree: the rows come in whole)");
     static_assert(!K0 || DMA, "the fused mesh input rides on the LDS-DMA instantiation");
     static_assert(!PTS || (DMA && !K0), "the fused points input rides on the LDS-DMA instantiation, without the mesh input");
+    static_assert(!FREE || (DMA && !K0 && !PTS), "the raw-parameter input rides on the LDS-DMA instantiation, without the mesh / points input");
     static_assert(DMA || !SPLIT || SHDEG != 3, "split degree-3 storage is staged by LDS-DMA (the register-staged rows were measured and removed)");
     // Round 6: the REST rows come in as TWO halves of 32 rows through the same 6 KB of LDS per wave (6 x 1 KiB DMA instructions each,
     // 1 440 of the 1 536 floats used), the 64 x 3 DC floats behind them: 27 KB per block instead of 49.
@@ -115,6 +120,8 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsP
     if (K0 && valid) splat_inputs_load(a.mesh, (int64_t)i, k0in);          // (in front of the SH rows' DMA: see gms_mesh.h)
     PointsInputs ptin = {};
     if (PTS && valid) points_inputs_load(pts, (int64_t)i, ptin);           // (likewise)
+    FreeRaw frin = {};
+    if (FREE && valid) free_inputs_load(fr, (int64_t)i, frin);             // (likewise)
     if (SHDEG >= 0) {
         const int g0 = blockIdx.x * BLOCK + wave * WAVE;
         const int rows = min(WAVE, a.P - g0);
@@ -151,7 +158,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsP
                 dcv[j] = e < rows * 3 ? a.shs[(size_t)g0 * 3 + e] : 0.f;
             }
         }
-        if (valid && !K0 && !PTS) {
+        if (valid && !K0 && !PTS && !FREE) {
             op_in = a.opac[i];
             if (!a.cov3Dp) {
                 s_in[0] = a.scales[3 * (size_t)i]; s_in[1] = a.scales[3 * (size_t)i + 1]; s_in[2] = a.scales[3 * (size_t)i + 2];
@@ -188,6 +195,14 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsP
             s_in[0] = sp.scale[0]; s_in[1] = sp.scale[1]; s_in[2] = sp.scale[2];
             q_in = make_float4(sp.q[0], sp.q[1], sp.q[2], sp.q[3]);
             op_in = sp.opacity;
+            view_transform(a.view, px, py, pz, vx, vy, vz); vis = vz > NEAR_Z;
+        }
+    } else if (FREE) {
+        if (valid) {
+            float q[4];
+            free_activate(fr, frin, s_in, q, op_in);
+            q_in = make_float4(q[0], q[1], q[2], q[3]);
+            px = a.means3D[3 * (size_t)i]; py = a.means3D[3 * (size_t)i + 1]; pz = a.means3D[3 * (size_t)i + 2];
             view_transform(a.view, px, py, pz, vx, vy, vz); vis = vz > NEAR_Z;
         }
     } else if (valid) {
@@ -434,6 +449,13 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5
     preprocess_fwd_body<DEG, true, true, false, true>(a, pts);
 }
 
+// ... the frame straight from a free model's raw parameters (gms_rasterize_forward_free): likewise
+template <int DEG>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5))) preprocess_fwd_free_kernel(PreArgs a, GmsFreeArgs fr)
+{
+    preprocess_fwd_body<DEG, true, true, false, false, true>(a, GmsPointsArgs{}, fr);
+}
+
 // The fused inputs hold split degree-3 storage (validate_forward): the active degree alone picks the preprocess instantiation
 template <typename Launch> static void dispatch_degree(int D, Launch &&launch)
 {
@@ -445,10 +467,13 @@ template <typename Launch> static void dispatch_degree(int D, Launch &&launch)
     }
 }
 
-int32_t launch_preprocess_forward(const PreArgs &pa, const GmsPointsArgs *points, bool fused_mesh, bool fast_layout, bool debug, hipStream_t stream)
+int32_t launch_preprocess_forward(const PreArgs &pa, const GmsPointsArgs *points, const GmsFreeArgs *free_args, bool fused_mesh, bool fast_layout,
+                                  bool debug, hipStream_t stream)
 {
     const unsigned pblocks = (unsigned)((pa.P + BLOCK - 1) / BLOCK);
-    if (points) {
+    if (free_args) {
+        dispatch_degree(pa.D, [&](auto d) { GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_free_kernel<d.value><<<pblocks, BLOCK, 0, stream>>>(pa, *free_args))); });
+    } else if (points) {
         dispatch_degree(pa.D, [&](auto d) { GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_points_kernel<d.value><<<pblocks, BLOCK, 0, stream>>>(pa, *points))); });
     } else if (fused_mesh) {
         dispatch_degree(pa.D, [&](auto d) { GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_dma_kernel<true, d.value><<<pblocks, BLOCK, 0, stream>>>(pa))); });

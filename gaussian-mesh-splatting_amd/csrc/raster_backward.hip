@@ -17,7 +17,10 @@
 // sqrt(det0/det)) and dL/dscale carrying the scale_modifier factor; both are inert in GaMeS training (antialiasing off,
 // modifier 1.0).  DESIGN.md section 2 lists them.
 #include "gms_blend.h"
+#include <type_traits>
+
 #include "gms_mesh.h"
+#include "gms_free.h"
 #include "gms_common.h"
 #include "gms_project.h"
 
@@ -43,6 +46,8 @@ struct PreBwdArgs {
     int campos_row;         // factorised mode: also write the camera centre into row P of dL_dcolor_sh
     GmsMeshArgs mesh;       // MESH instantiation: the frame was rendered straight from this mesh; the thread carries its gradients on through K0
     float *mesh_dvertices, *mesh_dalpha, *mesh_dscale, *mesh_dopacity;
+    GmsFreeArgs free;       // FreeTail instantiation: the frame was rendered straight from these raw rows; the thread carries its gradients on through the getters
+    float *free_dscaling, *free_drotation, *free_dopacity;
 };
 
 // SH basis values at the unit direction (x, y, z), the `basis_k` of the colour sum (gms_project.h::sh_eval_with_dir_jacobian)
@@ -97,7 +102,12 @@ static_assert(BWD_WAVE_FLOATS >= WAVE * BWD_RESTF + WAVE * 3, "the split image f
 // stay in the __global__ function itself: called through a __device__ template (forced inline) the two instantiations that
 // tests/test_kernel_resources_cpu.py pins by name came out with other registers (<false>: 92 -> 96 VGPRs, 58 -> 54 SGPRs), and an
 // empty pack leaves their names -- preprocess_bwd_kernel<false>, preprocess_bwd_kernel<true> -- and their code as they were.
+// <false, FreeTail> (gms_rasterize_backward_free): the frame came from a free model's raw parameters.  The thread forms scale / quaternion /
+// opacity from the raw rows -- the forward's statements (gms_free.h), so its bits -- and its tail carries dscale / drot / d opacity on
+// through the getters' backward to plain stores of the raw gradients; dL_dscales / dL_drots / dL_dopacity are not written.  A tag as
+// well, for the same reason.
 struct MeshRuns;
+struct FreeTail;
 template <bool MESH, typename... Runs>
 __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int dst_vec)
 {
@@ -107,8 +117,10 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
     // (tests/test_gpu_fused_training.py::test_mesh_backward_inside_preprocess_bwd_equals_the_mesh_backward_launch[203-2] fails under `fast`).
 #pragma clang fp contract(on)
     __shared__ __attribute__((aligned(16))) float sh_lds[4 * BWD_WAVE_FLOATS];
-    constexpr bool RUNS = sizeof...(Runs) > 0;
+    constexpr bool FREE = (std::is_same<Runs, FreeTail>::value || ...);
+    constexpr bool RUNS = sizeof...(Runs) > 0 && !FREE;
     static_assert(MESH || !RUNS, "the runs tail is a mesh tail");
+    static_assert(!FREE || !MESH, "the raw tail is not a mesh tail");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i = blockIdx.x * BLOCK + tid;
     const bool valid = i < a.P;
@@ -160,7 +172,13 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
         view_transform(V, px, py, pz, vx, vy, vz);
         Cov3 cv;
         float s_in[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f};
-        if (a.cov3Dp) {
+        float op_act = 0.f;          // FREE: the sigmoid opacity, formed here
+        if (FREE) {
+            FreeRaw fr;
+            free_inputs_load(a.free, (int64_t)i, fr);
+            free_activate(a.free, fr, s_in, q, op_act);
+            cov3d_from_scale_rot(s_in, a.mod, q, cv);
+        } else if (a.cov3Dp) {
 #pragma unroll
             for (int k = 0; k < 6; k++) cv.c[k] = a.cov3Dp[6 * (size_t)i + k];
         } else {
@@ -181,7 +199,7 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
             const float cA = cD * dinv, cB = -b * dinv, cC = aD * dinv;
             acc_mx = -(0.5f * (float)a.W) * (cA * mom_x + cB * mom_y);
             acc_my = -(0.5f * (float)a.H) * (cC * mom_y + cB * mom_x);
-            float opp = a.opac[i];
+            float opp = FREE ? op_act : a.opac[i];
             if (a.aa) opp *= sqrtf(fmaxf(0.000025f, (e.a0 * e.c0 - b * b) / det));
             dop = opp > 0.f ? mom_0 / opp : 0.f;
         }
@@ -194,7 +212,7 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
             const float det0 = e.a0 * e.c0 - b * b;
             const float ratio = det0 / det;
             const float h = sqrtf(fmaxf(0.000025f, ratio));
-            const float dL_dh = dop * a.opac[i];
+            const float dL_dh = dop * (FREE ? op_act : a.opac[i]);
             dop = dop * h;
             const float dL_dr = ratio <= 0.000025f ? 0.f : dL_dh / (2.f * h);
             dL_da += dL_dr * (e.c0 / det - det0 * cD / (det * det));
@@ -249,7 +267,7 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
         }
 
         // cov3D -> scale / quaternion
-        if (!a.cov3Dp) {
+        if (FREE || !a.cov3Dp) {
             const float mod = a.mod;
             const float s[3] = {mod * s_in[0], mod * s_in[1], mod * s_in[2]};
             const float r = q[0], x = q[1], y = q[2], z = q[3];
@@ -294,6 +312,17 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
         // the frame came straight from the mesh (gmsplat.h, ABI 8): on through the face -> Gaussian parameterization from registers
         const float gs[3] = {dscale[0], dscale[1], dscale[2]}, gq[4] = {drot[0], drot[1], drot[2], drot[3]};
         splat_backward_from_registers(a.mesh, (int64_t)i, dmean, gs, gq, dop, a.mesh_dvertices, a.mesh_dalpha, a.mesh_dscale, a.mesh_dopacity);
+    } else if (FREE) {
+        // the raw rows again (from cache for a visible Gaussian), the getters' backward on the registers, three plain stores
+        FreeRaw fr;
+        free_inputs_load(a.free, (int64_t)i, fr);
+        float ds[3], dq[4], d_op;
+        free_backward(a.free, fr, dscale, drot, dop, ds, dq, d_op);
+        const int S = a.free.scaling_cols;
+        a.free_dscaling[S * (size_t)i] = ds[0]; a.free_dscaling[S * (size_t)i + 1] = ds[1];
+        if (S == 3) a.free_dscaling[S * (size_t)i + 2] = ds[2];
+        *reinterpret_cast<float4 *>(a.free_drotation + 4 * (size_t)i) = make_float4(dq[0], dq[1], dq[2], dq[3]);
+        a.free_dopacity[i] = d_op;
     } else if (!MESH) {
         a.dL_dopacity[i] = dop;
     }
@@ -305,7 +334,9 @@ __global__ void __launch_bounds__(BLOCK) preprocess_bwd_kernel(PreBwdArgs a, int
     if (a.dL_dcolor_sh) { a.dL_dcolor_sh[3 * (size_t)i] = dcol_sh[0]; a.dL_dcolor_sh[3 * (size_t)i + 1] = dcol_sh[1]; a.dL_dcolor_sh[3 * (size_t)i + 2] = dcol_sh[2]; }
     if (!MESH) {
     a.dL_dmeans3D[3 * (size_t)i] = dmean[0]; a.dL_dmeans3D[3 * (size_t)i + 1] = dmean[1]; a.dL_dmeans3D[3 * (size_t)i + 2] = dmean[2];
-    if (a.cov3Dp) {
+    if (FREE) {
+        // (written above, as the raw gradients)
+    } else if (a.cov3Dp) {
         if (a.dL_dcov3D)
 #pragma unroll
             for (int k = 0; k < 6; k++) a.dL_dcov3D[6 * (size_t)i + k] = dcov[k];
@@ -486,10 +517,11 @@ __global__ void __launch_bounds__(BLOCK) sh_grad_expand_kernel(ShExpandArgs a)
 
 using namespace gms;
 
-extern "C" int32_t gms_rasterize_backward(const GmsRasterBackwardArgs *A, void *stream_)
+// gms_rasterize_backward and gms_rasterize_backward_free (`free_args` and the three raw gradients set): one driver, the per-Gaussian
+// instantiation differs
+static int32_t rasterize_backward(const GmsRasterBackwardArgs *A, const GmsFreeArgs *free_args, float *dL_d_scaling, float *dL_d_rotation,
+                                  float *dL_d_opacity, hipStream_t stream)
 {
-    gms::TraceRange trace_range("gms_rasterize_backward");
-    hipStream_t stream = (hipStream_t)stream_;
     set_error("%s", "");
     if (!A || A->P < 0 || A->width <= 0 || A->height <= 0) {
         set_error("gms_rasterize_backward: invalid sizes");
@@ -497,8 +529,18 @@ extern "C" int32_t gms_rasterize_backward(const GmsRasterBackwardArgs *A, void *
     }
     const int P = A->P, W = A->width, H = A->height;
     if (P == 0) return GMS_OK;
-    const bool sr = A->scales && A->rotations;
+    const bool sr = free_args || (A->scales && A->rotations);          // (the raw frame is on the scales + rotations path)
     const GmsMeshArgs *mesh = A->mesh;
+    if (free_args) {
+        const int32_t frc = check_free_args(free_args);
+        if (frc != GMS_OK) return frc;
+        if (free_args->P != (int64_t)P || mesh || A->cov3D_precomp || !dL_d_scaling || !dL_d_rotation || !dL_d_opacity ||
+            (((uintptr_t)dL_d_rotation) & 15u) != 0) {
+            set_error("gms_rasterize_backward_free: needs a complete GmsFreeArgs (P equal), no mesh, no cov3D_precomp and all three raw "
+                      "gradient outputs (dL_d_rotation 16-byte aligned)");
+            return GMS_ERR_INVALID_ARGUMENT;
+        }
+    }
     if (mesh) {
         const int32_t mrc = check_mesh_args(mesh, false);
         if (mrc != GMS_OK) return mrc;
@@ -510,13 +552,13 @@ extern "C" int32_t gms_rasterize_backward(const GmsRasterBackwardArgs *A, void *
             return GMS_ERR_INVALID_ARGUMENT;
         }
     }
-    if (!A->means3D || !A->opacities || !A->radii || !A->geom_buffer || !A->binning_buffer || !A->image_buffer ||
-        !A->dL_dout_color || !A->dL_dmeans2D || !A->grad_accum || (!mesh && !A->dL_dopacity) || (A->colors_precomp && !A->dL_dcolors) ||
+    if (!A->means3D || (!free_args && !A->opacities) || !A->radii || !A->geom_buffer || !A->binning_buffer || !A->image_buffer ||
+        !A->dL_dout_color || !A->dL_dmeans2D || !A->grad_accum || (!mesh && !free_args && !A->dL_dopacity) || (A->colors_precomp && !A->dL_dcolors) ||
         (!mesh && !A->dL_dmeans3D) || (A->sh_factor_mode != 0 && A->sh_factor_mode != 1) || (A->sh_factor_mode && (!A->shs || !A->dL_dcolors)) ||
         (A->factor_campos_row && !A->sh_factor_mode) ||
         (A->shs && !A->sh_factor_mode && !A->dL_dsh) || (A->shs_rest && ((!A->sh_factor_mode && !A->dL_dsh_rest) || A->M != 16)) ||
         ((A->shs == nullptr) == (A->colors_precomp == nullptr)) ||
-        (sr == (A->cov3D_precomp != nullptr)) || (sr && !mesh && (!A->dL_dscales || !A->dL_drotations)) ||
+        (sr == (A->cov3D_precomp != nullptr)) || (sr && !mesh && !free_args && (!A->dL_dscales || !A->dL_drotations)) ||
         (A->cov3D_precomp && !A->dL_dcov3D)) {
         set_error("gms_rasterize_backward: null or inconsistent pointer arguments");
         return GMS_ERR_INVALID_ARGUMENT;
@@ -575,16 +617,34 @@ extern "C" int32_t gms_rasterize_backward(const GmsRasterBackwardArgs *A, void *
             GMS_LAUNCH(GMS_K_PREPROCESS_BWD, stream, preprocess_bwd_kernel<true><<<(unsigned)((P + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(p, dst_vec));
         else      // longer runs, CSR tables: the segmented reduction
             GMS_LAUNCH(GMS_K_PREPROCESS_BWD, stream, preprocess_bwd_kernel<true, MeshRuns><<<(unsigned)((P + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(p, dst_vec));
+    } else if (free_args) {
+        p.free = *free_args; p.free_dscaling = dL_d_scaling; p.free_drotation = dL_d_rotation; p.free_dopacity = dL_d_opacity;
+        p.opac = p.scales = p.rots = nullptr; p.dL_dopacity = p.dL_dscales = p.dL_drots = nullptr;          // (ignored / not written)
+        GMS_LAUNCH(GMS_K_PREPROCESS_BWD, stream, (preprocess_bwd_kernel<false, FreeTail><<<(unsigned)((P + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(p, dst_vec)));
     } else {
         GMS_LAUNCH(GMS_K_PREPROCESS_BWD, stream, preprocess_bwd_kernel<false><<<(unsigned)((P + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(p, dst_vec));
     }
     GMS_KERNEL_CHECK(A->debug, stream, "preprocess_bwd");
-    if (fault_mode() == 4 && A->dL_dscales)      // negative control: dL/dscale.x of every 1000th Gaussian off by 2e-3
+    if (fault_mode() == 4 && A->dL_dscales && !free_args)      // negative control: dL/dscale.x of every 1000th Gaussian off by 2e-3
         fault_scale_kernel<<<(unsigned)((P / 1000 + 256) / 256), 256, 0, stream>>>(A->dL_dscales, P, 3, 0, 1000, 1.002f);
-    if (fault_mode() == 5 && A->dL_dscales)      // negative control: dL/dscale of every 100th Gaussian off by 1.3e-3 (between 1e-3 and 2e-3)
+    if (fault_mode() == 5 && A->dL_dscales && !free_args)      // negative control: dL/dscale of every 100th Gaussian off by 1.3e-3 (between 1e-3 and 2e-3)
         for (int f = 0; f < 3; f++)
             fault_scale_kernel<<<(unsigned)((P / 100 + 256) / 256), 256, 0, stream>>>(A->dL_dscales, P, 3, f, 100, 1.0013f);
     return GMS_OK;
+}
+
+extern "C" int32_t gms_rasterize_backward(const GmsRasterBackwardArgs *A, void *stream_)
+{
+    gms::TraceRange trace_range("gms_rasterize_backward");
+    return rasterize_backward(A, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream_);
+}
+
+extern "C" int32_t gms_rasterize_backward_free(const GmsRasterBackwardArgs *A, const GmsFreeArgs *free_args, float *dL_d_scaling,
+                                               float *dL_d_rotation, float *dL_d_opacity, void *stream_)
+{
+    gms::TraceRange trace_range("gms_rasterize_backward_free");
+    if (!free_args) { set_error("gms_rasterize_backward_free: NULL GmsFreeArgs"); return GMS_ERR_INVALID_ARGUMENT; }
+    return rasterize_backward(A, free_args, dL_d_scaling, dL_d_rotation, dL_d_opacity, (hipStream_t)stream_);
 }
 
 extern "C" int32_t gms_sh_grad_expand(const GmsShGradExpandArgs *A, void *stream_)

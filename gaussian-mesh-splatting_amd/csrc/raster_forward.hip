@@ -21,6 +21,7 @@
 #include "gms_blend.h"
 #include "gms_mesh.h"
 #include "gms_points.h"
+#include "gms_free.h"
 #include <atomic>
 #include <vector>
 #include <chrono>
@@ -268,14 +269,14 @@ extern "C" size_t gms_binning_bytes(int64_t n, int32_t w, int32_t h)
 
 static bool aligned16(const void *p) { return (((uintptr_t)p) & 15u) == 0; }
 // SH rows the DMA / split instantiations can read (the fused inputs always qualify: validate_forward)
-static bool sh_fast_layout(const GmsRasterForwardArgs *A)
+static bool sh_fast_layout(const GmsRasterForwardArgs *A, const GmsFreeArgs *free_args)
 {
     return A->shs && A->M == 16 && aligned16(A->shs) && aligned16(A->shs_rest) &&
-           (A->mesh || A->points || A->cov3D_precomp || aligned16(A->rotations));
+           (A->mesh || A->points || free_args || A->cov3D_precomp || aligned16(A->rotations));
 }
 
-// Every argument check of gms_rasterize_forward, before anything is allocated or launched
-static int32_t validate_forward(const GmsRasterForwardArgs *A)
+// Every argument check of gms_rasterize_forward (`free_args`: of gms_rasterize_forward_free), before anything is allocated or launched
+static int32_t validate_forward(const GmsRasterForwardArgs *A, const GmsFreeArgs *free_args)
 {
     if (!A || A->P < 0 || A->width <= 0 || A->height <= 0 || !A->out_color || !A->out_invdepth || !A->background) {
         set_error("gms_rasterize_forward: invalid sizes or null output/background pointer");
@@ -284,9 +285,20 @@ static int32_t validate_forward(const GmsRasterForwardArgs *A)
     const GmsMeshArgs *mesh = A->mesh;
     const GmsPointsArgs *points = A->points;
     if (mesh && points) { set_error("gms_rasterize_forward: set at most one of mesh / points"); return GMS_ERR_INVALID_ARGUMENT; }
+    if (free_args && (mesh || points)) { set_error("gms_rasterize_forward_free: mesh and points must be NULL"); return GMS_ERR_INVALID_ARGUMENT; }
     if (A->P == 0) return GMS_OK;
     const bool fused = mesh || points;
-    if (fused) {
+    if (free_args) {
+        // the thread of a Gaussian reads the raw rows as the stand-alone launch does: same checks first
+        const int32_t rc = check_free_args(free_args);
+        if (rc != GMS_OK) return rc;
+        if (free_args->P != (int64_t)A->P || !A->means3D || !A->shs || !A->shs_rest || A->M != 16 || A->D < 0 || A->D > 3 || A->colors_precomp ||
+            A->cov3D_precomp || !aligned16(A->shs) || !aligned16(A->shs_rest)) {
+            set_error("gms_rasterize_forward_free: needs a complete GmsFreeArgs (P equal), means3D, split degree-3 SH storage (shs + shs_rest, "
+                      "M = 16, active degree 0 .. 3, 16-byte aligned) and no precomputed colours / covariances");
+            return GMS_ERR_INVALID_ARGUMENT;
+        }
+    } else if (fused) {
         // the thread of a Gaussian reads the mesh / triangles through the same tables as the standalone launches: same checks first
         const int32_t rc = mesh ? check_mesh_args(mesh, false) : check_points_args(points);
         if (rc != GMS_OK) return rc;
@@ -316,7 +328,7 @@ static int32_t validate_forward(const GmsRasterForwardArgs *A)
             return GMS_ERR_INVALID_ARGUMENT;
         }
     }
-    if ((!fused && (!A->means3D || !A->opacities)) || !A->viewmatrix || !A->projmatrix || !A->campos || !A->radii || !A->geom_alloc ||
+    if ((!fused && (!A->means3D || (!free_args && !A->opacities))) || !A->viewmatrix || !A->projmatrix || !A->campos || !A->radii || !A->geom_alloc ||
         !A->binning_alloc || !A->image_alloc) {
         set_error("gms_rasterize_forward: null input pointer or callback");
         return GMS_ERR_INVALID_ARGUMENT;
@@ -325,7 +337,7 @@ static int32_t validate_forward(const GmsRasterForwardArgs *A)
         set_error("SH degree %d needs %d coefficients but M = %d (degrees 0..3 supported)", A->D, (A->D + 1) * (A->D + 1), A->M);
         return GMS_ERR_INVALID_ARGUMENT;
     }
-    if (A->shs_rest && !sh_fast_layout(A)) { set_error("split SH storage (shs_rest) needs M == 16 and 16-byte aligned pointers"); return GMS_ERR_INVALID_ARGUMENT; }
+    if (A->shs_rest && !sh_fast_layout(A, free_args)) { set_error("split SH storage (shs_rest) needs M == 16 and 16-byte aligned pointers"); return GMS_ERR_INVALID_ARGUMENT; }
     if (A->no_host_wait && A->binning_capacity_hint <= 0) { set_error("no_host_wait needs a binning capacity hint (render the shape once without it first)"); return GMS_ERR_INVALID_ARGUMENT; }
     return GMS_OK;
 }
@@ -352,14 +364,16 @@ static int32_t claim_tile_counters(int device, hipStream_t stream, int T, Counte
     return GMS_OK;
 }
 
-static PreArgs pre_args(const GmsRasterForwardArgs *A, const GeomState &geom, const ImageState &img, int gx, int gy, bool inline_scan)
+static PreArgs pre_args(const GmsRasterForwardArgs *A, bool raw_free, const GeomState &geom, const ImageState &img, int gx, int gy, bool inline_scan)
 {
     PreArgs pa{};          // (zero-initialised: the fused inputs leave the tensor inputs NULL, only K0 fills `mesh` and k0_*)
     pa.P = A->P; pa.D = A->D; pa.M = A->M; pa.W = A->width; pa.H = A->height; pa.gx = gx; pa.gy = gy;
     pa.shs = A->shs; pa.shs_rest = A->shs_rest; pa.colors = A->colors_precomp; pa.view = A->viewmatrix;
     pa.proj = A->projmatrix; pa.campos = A->campos; pa.mod = A->scale_modifier; pa.tanx = A->tan_fovx;
     pa.tany = A->tan_fovy; pa.aa = A->antialiasing; pa.radii = A->radii; pa.visible = A->visible; pa.geom = geom; pa.tile_count = img.tile_count;
-    if (!A->mesh && !A->points) {
+    if (raw_free) {
+        pa.means3D = A->means3D;          // (scale / rotation / opacity come from the raw rows in the thread)
+    } else if (!A->mesh && !A->points) {
         pa.means3D = A->means3D; pa.opac = A->opacities; pa.scales = A->scales; pa.rots = A->rotations; pa.cov3Dp = A->cov3D_precomp;
     }
     if (A->mesh) {
@@ -422,12 +436,11 @@ static void *alloc_binning(const GmsRasterForwardArgs *A, uint64_t capacity, int
     return mem;
 }
 
-extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *stream_)
+// gms_rasterize_forward and gms_rasterize_forward_free (`free_args` set): one driver, the preprocess instantiation differs
+static int64_t rasterize_forward(const GmsRasterForwardArgs *A, const GmsFreeArgs *free_args, hipStream_t stream)
 {
-    gms::TraceRange trace_range("gms_rasterize_forward");
-    hipStream_t stream = (hipStream_t)stream_;
     g_err[0] = 0;
-    if (const int32_t rc = validate_forward(A)) return rc;
+    if (const int32_t rc = validate_forward(A, free_args)) return rc;
     const int P = A->P, W = A->width, H = A->height;
     const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE, T = gx * gy;
     const size_t HW = (size_t)W * H;
@@ -460,8 +473,8 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
     // tile table fits the emit blocks' LDS.
     const bool inline_scan = inline_scan_setting() && hint > 0 && frame_L != 0 && inline_scan_fits(T, P);
     // K1: the frame straight from a mesh or from pseudo-triangles (gmsplat.h) runs K0 inside the preprocess thread
-    const PreArgs pa = pre_args(A, geom, img, gx, gy, inline_scan);
-    if (const int32_t rc = launch_preprocess_forward(pa, A->points, A->mesh != nullptr, sh_fast_layout(A), debug, stream)) return rc;
+    const PreArgs pa = pre_args(A, free_args != nullptr, geom, img, gx, gy, inline_scan);
+    if (const int32_t rc = launch_preprocess_forward(pa, A->points, free_args, A->mesh != nullptr, sh_fast_layout(A, free_args), debug, stream)) return rc;
     const uint32_t L = seg_len_min();
     // deferred read-back (gmsplat.h, count_ticket_out): this frame's counts go to the next slot of the thread's ring and nobody waits here
     const bool defer = A->count_ticket_out != nullptr && hint > 0 && !A->no_host_wait;
@@ -525,6 +538,19 @@ extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *st
     }
     if (A->num_units_out) *A->num_units_out = (int64_t)units_seen;
     return N;
+}
+
+extern "C" int64_t gms_rasterize_forward(const GmsRasterForwardArgs *A, void *stream_)
+{
+    gms::TraceRange trace_range("gms_rasterize_forward");
+    return rasterize_forward(A, nullptr, (hipStream_t)stream_);
+}
+
+extern "C" int64_t gms_rasterize_forward_free(const GmsRasterForwardArgs *A, const GmsFreeArgs *free_args, void *stream_)
+{
+    gms::TraceRange trace_range("gms_rasterize_forward_free");
+    if (!free_args) { set_error("gms_rasterize_forward_free: NULL GmsFreeArgs"); return GMS_ERR_INVALID_ARGUMENT; }
+    return rasterize_forward(A, free_args, (hipStream_t)stream_);
 }
 
 extern "C" int64_t gms_rasterize_forward_counts(const int64_t *ticket, int32_t width, int32_t height, int32_t P, int64_t *num_units_out,

@@ -159,9 +159,11 @@ Gaussians tensor_gaussians(const Tensor &means3D, const Tensor &sh, const Tensor
     return {f32c(sh), f32c(sh_rest), f32c(means3D), f32c(colors), f32c(opac), f32c(scales), f32c(rots), f32c(cov)};
 }
 
-// `mesh` / `points`: the forward-only frame straight from a mesh or pseudo-triangles (gmsplat.h); `g` then holds only the SH tensors
+// `mesh` / `points`: the forward-only frame straight from a mesh or pseudo-triangles (gmsplat.h); `g` then holds only the SH tensors.
+// `free_args`: the frame straight from a free model's raw parameters (gms_rasterize_forward_free); `g` holds the SH tensors and means3D
 Forward forward_core(const FrameSettings &s, int64_t P, c10::Device dev, const Gaussians &g, const Tensor &visible, bool use_hint,
-                     const GmsMeshArgs *mesh = nullptr, const MeshOut *mesh_out = nullptr, bool may_defer = false, const GmsPointsArgs *points = nullptr)
+                     const GmsMeshArgs *mesh = nullptr, const MeshOut *mesh_out = nullptr, bool may_defer = false, const GmsPointsArgs *points = nullptr,
+                     const GmsFreeArgs *free_args = nullptr)
 {
     c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
     const bool has_sh = g.sh.defined() && g.sh.numel() > 0;
@@ -218,9 +220,9 @@ Forward forward_core(const FrameSettings &s, int64_t P, c10::Device dev, const G
     int64_t ticket[2] = {0, 0};
     const bool defer = may_defer && hint > 0 && !capturing && P > 0 && deferred_counts();
     if (defer) a.count_ticket_out = ticket;
-    const int64_t n = gms_rasterize_forward(&a, stream);
+    const int64_t n = free_args ? gms_rasterize_forward_free(&a, free_args, stream) : gms_rasterize_forward(&a, stream);
     TORCH_CHECK(!(geom.failed || binning.failed || image.failed), "scratch allocation failed (out of device memory?)");
-    check_rc(n, "gms_rasterize_forward");
+    check_rc(n, free_args ? "gms_rasterize_forward_free" : "gms_rasterize_forward");
     f.num_rendered = n; f.num_units = num_units;
     f.capacity = (hint > 0 && n <= hint) ? hint : (n > 0 ? n : 1);
     f.geom = geom.t; f.binning = binning.t; f.image = image.t;
@@ -238,6 +240,8 @@ Forward forward_core(const FrameSettings &s, int64_t P, c10::Device dev, const G
 struct Backward { Tensor dmeans2D, dcolors, dopacity, dmeans3D, dcov3D, dsh, dsh_rest, dscales, drots; };
 // outputs of the mesh backward when it runs inside preprocess_bwd (GmsRasterBackwardArgs.mesh, ABI 8)
 struct MeshGrads { Tensor d_vertices, d_alpha, d_scale, d_opacity; };
+// outputs of the getters' backward when it runs in the tail of preprocess_bwd (gms_rasterize_backward_free)
+struct FreeGrads { Tensor d_scaling, d_rotation, d_opacity; };
 
 // The gradient outputs of a backward call.  The autograd fast path allocates them in FORWARD, before the C call (there the
 // host runs ahead of the GPU and then waits for the instance count anyway), so that between "N has arrived" and "blend_bwd is
@@ -251,7 +255,8 @@ static std::atomic<bool> g_sh_factor{false};
 static std::map<int, std::vector<Tensor>> g_factors;
 constexpr size_t MAX_QUEUED_FACTORS = 256;
 
-Backward alloc_backward(const Gaussians &g)
+// `raw`: a frame straight from raw parameters writes no dL/d(opacity, scales, rotations)
+Backward alloc_backward(const Gaussians &g, bool raw = false)
 {
     const int64_t P = g.means3D.size(0);
     auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(g.means3D.device());
@@ -259,7 +264,7 @@ Backward alloc_backward(const Gaussians &g)
     const bool has_cov = g.cov.defined() && g.cov.numel() > 0;
     Backward b;
     b.dmeans2D = torch::empty({P, 3}, fopt);
-    b.dopacity = torch::empty(g.opac.sizes(), fopt);
+    if (!raw) b.dopacity = torch::empty(g.opac.sizes(), fopt);
     b.dmeans3D = torch::empty({P, 3}, fopt);
     const bool factor = has_sh && g_sh_factor.load();
     if (!has_sh) b.dcolors = torch::empty({P, 3}, fopt);
@@ -267,13 +272,14 @@ Backward alloc_backward(const Gaussians &g)
     if (has_sh && !factor) b.dsh = torch::empty(g.sh.sizes(), fopt);
     if (split && !factor) b.dsh_rest = torch::empty(g.sh_rest.sizes(), fopt);
     if (has_cov) b.dcov3D = torch::empty({P, 6}, fopt);
-    else { b.dscales = torch::empty({P, 3}, fopt); b.drots = torch::empty({P, 4}, fopt); }
+    else if (!raw) { b.dscales = torch::empty({P, 3}, fopt); b.drots = torch::empty({P, 4}, fopt); }
     return b;
 }
 
 // `f`: the forward's radii, scratch tensors and counts
 Backward backward_core(const FrameSettings &s, const Gaussians &g, const Forward &f, const Tensor &dL_dcolor_, const Tensor &dL_dinvd_,
-                       const Backward *prealloc = nullptr, const GmsMeshArgs *mesh = nullptr, const MeshGrads *mesh_grads = nullptr)
+                       const Backward *prealloc = nullptr, const GmsMeshArgs *mesh = nullptr, const MeshGrads *mesh_grads = nullptr,
+                       const GmsFreeArgs *free_args = nullptr, const FreeGrads *free_grads = nullptr)
 {
     const auto dev = g.means3D.device();
     c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
@@ -292,7 +298,7 @@ Backward backward_core(const FrameSettings &s, const Gaussians &g, const Forward
         if (it != g_accum.end()) { accum = it->second; g_accum.erase(it); }
     }
     if (!accum.defined()) accum = torch::zeros({std::max<int64_t>(P, 1), 16}, fopt);
-    Backward b = prealloc ? *prealloc : alloc_backward(g);
+    Backward b = prealloc ? *prealloc : alloc_backward(g, free_args != nullptr);
     GmsRasterBackwardArgs a{};
     a.P = (int32_t)P; a.D = (int32_t)s.D; a.M = (int32_t)M; a.width = (int32_t)s.W; a.height = (int32_t)s.H;
     a.num_rendered = f.num_rendered; a.binning_capacity = f.capacity;
@@ -320,7 +326,10 @@ Backward backward_core(const FrameSettings &s, const Gaussians &g, const Forward
         TORCH_CHECK(g_factors[(int)dev.index()].size() < MAX_QUEUED_FACTORS, "factorised SH mode: ", MAX_QUEUED_FACTORS,
                     " factors queued on this device and never taken (call take_sh_factors() every step, or set_sh_factor_mode(False))");
     }
-    if (P > 0) check_rc(gms_rasterize_backward(&a, stream), "gms_rasterize_backward");
+    if (P > 0 && free_args)
+        check_rc(gms_rasterize_backward_free(&a, free_args, mf(free_grads->d_scaling), mf(free_grads->d_rotation), mf(free_grads->d_opacity), stream),
+                 "gms_rasterize_backward_free");
+    else if (P > 0) check_rc(gms_rasterize_backward(&a, stream), "gms_rasterize_backward");
     if (a.sh_factor_mode) {          // factorised mode: queue the factor (rows 0..P-1 + camera centre) for the exchange
         std::lock_guard<std::mutex> lk(g_mu);
         g_factors[(int)dev.index()].push_back(b.dcolors);
@@ -914,6 +923,136 @@ std::vector<Tensor> render_mesh(const Tensor &vertices, const Tensor &faces, con
     return RenderMeshFn::apply(vertices, faces, _alpha, _scale, _opacity, sh_dc, sh_rest, means2D, mode, spf, splat_face, bg, view, proj, campos, H, W,
                                tanx, tany, mod, aa, debug, vertices.requires_grad(), will_backward, sh_degree,
                                face_splat_offset ? *face_splat_offset : torch::empty({0}, faces.options().dtype(torch::kInt)));      // (a defined tensor: autograd asks every tensor argument for its device)
+}
+
+// ---------------------------------------------------------------------------------------------- free-Gaussian models (gs / gs_flat)
+// The getters of a free model as one launch and one autograd node (gms_free_to_gaussians_*), and the training frame straight from its
+// raw parameters (gms_rasterize_forward_free / _backward_free): ONE node from (_xyz, _scaling, _rotation, _opacity, SH) to the image.
+struct FreeIn { Tensor scaling, rotation, opacity; };
+FreeIn free_inputs(const char *what, const Tensor &scaling_, const Tensor &rotation_, const Tensor &opacity_)
+{
+    require_gpu(scaling_); require_gpu(rotation_); require_gpu(opacity_);
+    TORCH_CHECK(scaling_.dim() == 2 && (scaling_.size(1) == 2 || scaling_.size(1) == 3), what, ": _scaling must have dimensions (P, 2) or (P, 3)");
+    const int64_t P = scaling_.size(0);
+    TORCH_CHECK(rotation_.dim() == 2 && rotation_.size(0) == P && rotation_.size(1) == 4 && opacity_.numel() == P, what,
+                ": _rotation must have dimensions (P, 4) and _opacity must hold P values");
+    TORCH_CHECK(rotation_.device() == scaling_.device() && opacity_.device() == scaling_.device(), what, ": the raw parameters live on different devices");
+    return {f32c(scaling_), f32c(rotation_), f32c(opacity_)};
+}
+GmsFreeArgs free_args_of(const FreeIn &in, double eps_s0)
+{
+    GmsFreeArgs a{};
+    a.P = in.scaling.size(0); a.scaling = cf(in.scaling); a.scaling_cols = (int32_t)in.scaling.size(1); a.rotation = cf(in.rotation);
+    a._opacity = cf(in.opacity); a.eps_s0 = (float)eps_s0;
+    return a;
+}
+
+class FreeFn : public torch::autograd::Function<FreeFn> {
+public:
+    // -> get_scaling [P,3], get_rotation [P,4], get_opacity shaped like `_opacity`
+    static variable_list forward(AutogradContext *ctx, Tensor scaling_, Tensor rotation_, Tensor opacity_, double eps_s0)
+    {
+        ctx->set_materialize_grads(false);
+        const FreeIn in = free_inputs("free_to_gaussians", scaling_, rotation_, opacity_);
+        const auto dev = in.scaling.device();
+        c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+        const int64_t P = in.scaling.size(0);
+        auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
+        Tensor sact = torch::empty({P, 3}, fopt), runit = torch::empty({P, 4}, fopt), oact = torch::empty_like(in.opacity);
+        const GmsFreeArgs a = free_args_of(in, eps_s0);
+        check_rc(gms_free_to_gaussians_forward(&a, mf(sact), mf(runit), mf(oact), stream_of(dev)), "gms_free_to_gaussians_forward");
+        ctx->save_for_backward({in.scaling, in.rotation, in.opacity});
+        ctx->saved_data["eps_s0"] = eps_s0;
+        return {sact, runit, oact};
+    }
+
+    static variable_list backward(AutogradContext *ctx, variable_list g)
+    {
+        auto s = ctx->get_saved_variables();
+        const FreeIn in{s[0], s[1], s[2]};
+        const auto dev = in.scaling.device();
+        c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+        Tensor gs = g[0].defined() ? f32c(g[0]) : Tensor(), gq = g[1].defined() ? f32c(g[1]) : Tensor(), gop = g[2].defined() ? f32c(g[2]) : Tensor();
+        Tensor d_scaling = torch::empty_like(in.scaling), d_rotation = torch::empty_like(in.rotation), d_opacity = torch::empty_like(in.opacity);
+        const GmsFreeArgs a = free_args_of(in, ctx->saved_data["eps_s0"].toDouble());
+        check_rc(gms_free_to_gaussians_backward(&a, cf(gs), cf(gq), cf(gop), mf(d_scaling), mf(d_rotation), mf(d_opacity), stream_of(dev)),
+                 "gms_free_to_gaussians_backward");
+        return {d_scaling, d_rotation, d_opacity, Tensor()};
+    }
+};
+
+std::vector<Tensor> free_to_gaussians(const Tensor &_scaling, const Tensor &_rotation, const Tensor &_opacity, double eps_s0)
+{
+    return FreeFn::apply(_scaling, _rotation, _opacity, eps_s0);
+}
+
+class RenderFreeFn : public torch::autograd::Function<RenderFreeFn> {
+public:
+    static variable_list forward(AutogradContext *ctx, Tensor xyz_, Tensor scaling_, Tensor rotation_, Tensor opacity_, Tensor sh_dc, Tensor sh_rest,
+                                 Tensor means2D, Tensor bg, Tensor view, Tensor proj, Tensor campos, int64_t H, int64_t W, double tanx, double tany,
+                                 double mod, bool aa, bool debug, int64_t sh_degree, double eps_s0, bool will_backward)
+    {
+        ctx->set_materialize_grads(false);
+        TORCH_CHECK(sh_degree >= 0 && sh_degree <= 3, "render_free: active SH degree ", sh_degree, " (storage is degree 3: 0 .. 3)");
+        require_gpu(xyz_); require_gpu(sh_dc); require_gpu(sh_rest);
+        TORCH_CHECK(xyz_.dim() == 2 && xyz_.size(1) == 3, "render_free: _xyz must have dimensions (P, 3)");
+        const FreeIn in = free_inputs("render_free", scaling_, rotation_, opacity_);
+        const int64_t P = xyz_.size(0);
+        TORCH_CHECK(in.scaling.size(0) == P && sh_dc.size(0) == P && sh_rest.size(0) == P, "render_free: P mismatch");
+        TORCH_CHECK(in.scaling.device() == xyz_.device() && sh_dc.device() == xyz_.device() && sh_rest.device() == xyz_.device(),
+                    "render_free: the parameters live on different devices");
+        check_split_sh("render_free", sh_dc, sh_rest);
+        const auto dev = xyz_.device();
+        c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+        Tensor xyz = f32c(xyz_), dc = f32c(sh_dc), rest = f32c(sh_rest);
+        auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
+        const Gaussians g{dc, rest, xyz, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        if (will_backward) stash_backward(ctx, alloc_backward(g, true));      // (see Backward)
+        const GmsFreeArgs fa = free_args_of(in, eps_s0);
+        Tensor visible = torch::empty({P}, fopt.dtype(torch::kBool));          // radii > 0, written by the preprocess kernel
+        const FrameSettings s = frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, sh_degree, false, aa, debug);
+        Forward f = forward_core(s, P, dev, g, visible, true, nullptr, nullptr, will_backward, nullptr, &fa);
+        if (will_backward) {
+            save_frame(ctx, {xyz, in.scaling, in.rotation, in.opacity, dc, rest}, s, f);
+            ctx->saved_data["eps_s0"] = eps_s0;
+        }
+        ctx->mark_non_differentiable({f.radii, visible});
+        return {f.color, f.radii, f.invdepth, visible};
+    }
+
+    static variable_list backward(AutogradContext *ctx, variable_list grads)
+    {
+        auto saved = ctx->get_saved_variables();
+        const Tensor &xyz = saved[0];
+        const FreeIn in{saved[1], saved[2], saved[3]};
+        const Gaussians g{saved[4], saved[5], xyz, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
+        auto [s, f] = load_frame(ctx, saved);
+        const auto dev = xyz.device();
+        c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+        Tensor gcol = grads[0].defined() ? grads[0] : torch::zeros({3, s.H, s.W}, xyz.options());
+        std::optional<Backward> pre = take_backward(ctx);
+        redeem_counts(ctx, s, f, xyz);
+        // the getters' backward in the tail of preprocess_bwd (preprocess_bwd_kernel<false, FreeTail>): plain stores, so deterministic mode
+        // and the factorised SH mode take it as well
+        const FreeGrads fg{torch::empty_like(in.scaling), torch::empty_like(in.rotation), torch::empty_like(in.opacity)};
+        const GmsFreeArgs fa = free_args_of(in, ctx->saved_data["eps_s0"].toDouble());
+        Backward b = backward_core(s, g, f, gcol, grads[2], pre ? &*pre : nullptr, nullptr, nullptr, &fa, &fg);
+        Tensor none;
+        return {b.dmeans3D, fg.d_scaling, fg.d_rotation, fg.d_opacity, b.dsh, b.dsh_rest, b.dmeans2D,
+                none, none, none, none, none, none, none, none, none, none, none, none, none, none};
+    }
+};
+
+std::vector<Tensor> render_free(const Tensor &xyz, const Tensor &_scaling, const Tensor &_rotation, const Tensor &_opacity, const Tensor &sh_dc,
+                                const Tensor &sh_rest, const Tensor &means2D, const Tensor &bg, const Tensor &view, const Tensor &proj,
+                                const Tensor &campos, int64_t H, int64_t W, double tanx, double tany, double mod, bool aa, bool debug,
+                                int64_t sh_degree, double eps_s0)
+{
+    const bool will_backward = at::GradMode::is_enabled() &&
+        (xyz.requires_grad() || _scaling.requires_grad() || _rotation.requires_grad() || _opacity.requires_grad() || sh_dc.requires_grad() ||
+         sh_rest.requires_grad() || means2D.requires_grad());
+    return RenderFreeFn::apply(xyz, _scaling, _rotation, _opacity, sh_dc, sh_rest, means2D, bg, view, proj, campos, H, W, tanx, tany, mod, aa,
+                               debug, sh_degree, eps_s0, will_backward);
 }
 
 // ---------------------------------------------------------------------------------------------- fused L1 + SSIM
@@ -1514,6 +1653,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("means2D"), py::arg("mode"), py::arg("spf"), py::arg("splat_face"), py::arg("bg"), py::arg("view"), py::arg("proj"), py::arg("campos"),
           py::arg("H"), py::arg("W"), py::arg("tanx"), py::arg("tany"), py::arg("mod"), py::arg("aa"), py::arg("debug"), py::arg("sh_degree"),
           py::arg("face_splat_offset") = py::none(), nogil());
+    m.def("free_to_gaussians", &free_to_gaussians, "differentiable getters of a free model: (_scaling [P,2|3], _rotation [P,4], _opacity, eps_s0) -> "
+          "[get_scaling [P,3], get_rotation [P,4], get_opacity]; one launch each way", nogil());
+    m.def("render_free", &render_free, "differentiable frame straight from a free model's raw parameters: [image, radii, invdepth, visible]", py::arg("xyz"),
+          py::arg("_scaling"), py::arg("_rotation"), py::arg("_opacity"), py::arg("features_dc"), py::arg("features_rest"), py::arg("screenspace_points"),
+          py::arg("bg"), py::arg("view"), py::arg("proj"), py::arg("campos"), py::arg("H"), py::arg("W"), py::arg("tanfovx"), py::arg("tanfovy"),
+          py::arg("scale_modifier"), py::arg("antialiasing"), py::arg("debug"), py::arg("active_degree"), py::arg("eps_s0"), nogil());
     m.def("l1_ssim", &l1_ssim, "differentiable w_l1 * L1 + w_ssim * SSIM + bias; returns (value [0-dim], [l1, ssim])", nogil());
     m.def("lpips", &lpips, "LPIPS (VGG-16) stage terms of image pairs into rows of a device table: the five tapped maps or an empty list; launches only", nogil());
     m.def("image_metrics", &image_metrics, "evaluation sums of image pairs into rows of a device table: (img_u8, gt_u8) or two empty tensors; launches only", nogil());

@@ -81,6 +81,14 @@ class PointsArgs(C.Structure):
     ]
 
 
+class FreeArgs(C.Structure):
+    """GmsFreeArgs (include/gmsplat.h; additive to ABI 10)."""
+    _fields_ = [
+        ("P", C.c_int64), ("scaling", C.c_void_p), ("scaling_cols", C.c_int32), ("rotation", C.c_void_p), ("_opacity", C.c_void_p),
+        ("eps_s0", C.c_float),
+    ]
+
+
 class LossArgs(C.Structure):
     _fields_ = [
         ("planes", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("img", C.c_void_p), ("gt", C.c_void_p),
@@ -215,6 +223,7 @@ EXPORTS = (
     "gms_lpips_workspace_bytes", "gms_lpips",
     "gms_ground_truth_workspace_bytes", "gms_ground_truth_u8",
     "gms_resize_workspace_bytes", "gms_resize_tile_columns", "gms_resize_u8",
+    "gms_free_to_gaussians_forward", "gms_free_to_gaussians_backward", "gms_rasterize_forward_free", "gms_rasterize_backward_free",
 )
 K_COUNT = 23
 
@@ -252,6 +261,14 @@ def load():
         lib.gms_points_to_gaussians_forward.argtypes = [C.POINTER(PointsArgs)] + [C.c_void_p] * 7
         lib.gms_points_to_gaussians_backward.restype = C.c_int32
         lib.gms_points_to_gaussians_backward.argtypes = [C.POINTER(PointsArgs)] + [C.c_void_p] * 7
+        lib.gms_free_to_gaussians_forward.restype = C.c_int32
+        lib.gms_free_to_gaussians_forward.argtypes = [C.POINTER(FreeArgs)] + [C.c_void_p] * 4
+        lib.gms_free_to_gaussians_backward.restype = C.c_int32
+        lib.gms_free_to_gaussians_backward.argtypes = [C.POINTER(FreeArgs)] + [C.c_void_p] * 7
+        lib.gms_rasterize_forward_free.restype = C.c_int64
+        lib.gms_rasterize_forward_free.argtypes = [C.POINTER(RasterForwardArgs), C.POINTER(FreeArgs), C.c_void_p]
+        lib.gms_rasterize_backward_free.restype = C.c_int32
+        lib.gms_rasterize_backward_free.argtypes = [C.POINTER(RasterBackwardArgs), C.POINTER(FreeArgs)] + [C.c_void_p] * 4
         lib.gms_abi_version.restype = C.c_int32
         lib.gms_last_error.restype = C.c_char_p
         for n in ("gms_geom_bytes", "gms_image_bytes", "gms_binning_bytes", "gms_image_n_contrib_offset"):

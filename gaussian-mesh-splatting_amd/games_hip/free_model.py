@@ -3,8 +3,9 @@
 
 On a machine that holds the reference its own two classes train on the drop-in packages (rasterizer, `simple_knn`, `FusedAdam`) and
 `games_hip.densify.install_density()` puts the kernels under them; these classes exist for where the reference tree is absent: what
-`games_hip.train.training()` needs of a free model and nothing more.  The getters are plain torch (a fused getter for free models is
-not built).  The PLY is the reference's `_save_ply` layout, the `eps_s0` scale column of a flat model included, so
+`games_hip.train.training()` needs of a free model and nothing more.  The getters are plain torch, as the reference's (their bits matter
+to readers of the model); `hip_getters()` returns the three from one launch (games_hip.free_op), and with `hip_raw_frame = True` a
+training frame goes from the raw parameters to the image in one autograd node (games_hip.render).  The PLY is the reference's `_save_ply` layout, the `eps_s0` scale column of a flat model included, so
 `HipPointsGaussianModel.load_ply` and the reference read the file."""
 from __future__ import annotations
 
@@ -13,6 +14,7 @@ import torch
 from torch import nn
 
 from .densify import HipDensifyMixin
+from .free_op import HipRawFrameMixin
 from .model import _StandaloneBase
 from .synthetic import RGB2SH
 
@@ -30,7 +32,7 @@ def get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, ma
     return helper
 
 
-class HipGaussianModel(HipDensifyMixin, _StandaloneBase):
+class HipGaussianModel(HipRawFrameMixin, HipDensifyMixin, _StandaloneBase):
     """gs: three stored scales."""
 
     n_scales = 3

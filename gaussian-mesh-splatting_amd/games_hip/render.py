@@ -150,10 +150,62 @@ def _render_training_frame_from_mesh(viewpoint_camera, pc, pipe, bg_color, scali
     return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": visible, "radii": radii, "depth": invdepth}
 
 
+def _free_frame_inputs(pc, pipe, override_color):
+    """The six raw parameters (+ eps_s0) of this frame if it can be rendered straight from them (`_C.render_free`), else None.  The
+    model opted in (`hip_raw_frame`), the rasterizer's native SH / cov3D stages on split degree-3 SH STORAGE (any active degree; no
+    knob of its own: GMS_TRAIN_FUSED=0 keeps the two-node frame, as for the mesh route), the model's own centres (a `_View` with
+    other centres never qualifies), float32 contiguous GPU tensors of matching sizes.  A flat model (one that has `eps_s0`) stores
+    two scale columns, any other three: the op reads the column count as the model kind."""
+    if not (getattr(pc, "hip_raw_frame", False) and _native_route("render_free", "GMS_TRAIN_FUSED", pc, pipe, override_color)):
+        return None
+    names = ("_xyz", "_scaling", "_rotation", "_opacity", "_features_dc", "_features_rest")
+    t = [getattr(pc, n, None) for n in names]
+    if not all(torch.is_tensor(x) and x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() for x in t):
+        return None
+    xyz, scaling, rotation, opacity, dc, rest = t
+    if pc.get_xyz is not xyz or xyz.dim() != 2 or xyz.shape[1] != 3:
+        return None
+    P = int(xyz.shape[0])
+    flat = hasattr(pc, "eps_s0")
+    if (scaling.dim() != 2 or scaling.shape[0] != P or scaling.shape[1] != (2 if flat else 3) or tuple(rotation.shape) != (P, 4)
+            or opacity.numel() != P or dc.dim() != 3 or tuple(dc.shape) != (P, 1, 3) or rest.shape[0] != P or rest.shape[2] != 3
+            or not 0 <= int(pc.active_sh_degree) <= 3):
+        return None
+    return xyz, scaling, rotation, opacity, dc, rest, float(getattr(pc, "eps_s0", 0.0))
+
+
+def _render_free_frame(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, inputs):
+    """train.py:100 on a free model (gs / gs_flat) that opted in: ONE C++ autograd node from (_xyz, _scaling, _rotation, _opacity, SH) to
+    the image (`_C.render_free`; gms_rasterize_forward_free / _backward_free) -- the getters run inside the preprocess thread, their
+    backward in the tail of preprocess_bwd.  Same image and, in deterministic mode, the same gradients bit for bit as the op node
+    followed by the rasterize node (tests/test_gpu_free_frame.py).  `inputs`: _free_frame_inputs()."""
+    xyz, scaling, rotation, opacity, dc, rest, eps_s0 = inputs
+    screenspace_points = _zero_points(xyz.device, xyz.shape, xyz.dtype)
+    H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
+    args = (xyz, scaling, rotation, opacity, dc, rest, screenspace_points, bg_color, viewpoint_camera.world_view_transform,
+            viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W, math.tan(viewpoint_camera.FoVx * 0.5),
+            math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing), bool(pipe.debug),
+            int(pc.active_sh_degree), eps_s0)
+    if pipe.debug:      # as the two-node route (diff_gaussian_rasterization.rasterize_gaussians): a failing forward leaves its inputs behind
+        snapshot = dgr._cpu_copy(args)
+        try:
+            image, radii, invdepth, visible = dgr._C.render_free(*args)
+        except Exception:
+            torch.save(snapshot, "snapshot_fw.dump")
+            print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+            raise
+    else:
+        image, radii, invdepth, visible = dgr._C.render_free(*args)
+    return {"render": image, "viewspace_points": screenspace_points, "visibility_filter": visible, "radii": radii, "depth": invdepth}
+
+
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None):
     inputs = _fused_training_inputs(pc, pipe, override_color)
     if inputs is not None:
         return _render_training_frame_from_mesh(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, inputs)
+    inputs = _free_frame_inputs(pc, pipe, override_color)
+    if inputs is not None:
+        return _render_free_frame(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, inputs)
     xyz = pc.get_xyz
     # the reference writes `torch.zeros_like(...) + 0` and retain_grad() (renderer/gaussian_renderer/__init__.py:33-37): a
     # 3.6 MB fill + an elementwise kernel per render for a tensor whose VALUES nobody reads (the rasterizer only hands a

@@ -352,6 +352,45 @@ int32_t gms_points_to_gaussians_backward(const GmsPointsArgs *args, const float 
                                          const float *dL_drotation_unit, const float *dL_dopacity_activated /* or NULL */,
                                          float *dL_dtriangles, float *dL_d_opacity /* or NULL */, void *stream);
 
+/* ---- free-Gaussian getters (gs / gs_flat) and the frame straight from raw parameters -------
+ * Additive to ABI 10: no existing struct changes.  Replaces get_scaling / get_rotation / get_opacity of scene/gaussian_model.py:95-115
+ * and games/flat_splatting/scene/flat_gaussian_model.py:29-35:
+ *   scale = exp(scaling) (scaling_cols 3) or [eps_s0, exp(scaling[:, 0]), exp(scaling[:, 1])] (scaling_cols 2),
+ *   q = rotation / max(|rotation|, 1e-12), opacity = sigmoid(_opacity). */
+typedef struct GmsFreeArgs {
+    int64_t P;                    /* Gaussians */
+    const float *scaling;         /* [P,scaling_cols] raw (log) scales */
+    int32_t scaling_cols;         /* 3: gs; 2: gs_flat */
+    const float *rotation;        /* [P,4] raw quaternions, 16-byte aligned */
+    const float *_opacity;        /* [P] raw opacities */
+    float eps_s0;                 /* scaling_cols 2: the constant first column of the activated scale */
+} GmsFreeArgs;
+
+/* One launch.  Every output may be NULL (not written): scaling_activated [P,3], rotation_unit [P,4] (16-byte aligned),
+ * opacity_activated [P]. */
+int32_t gms_free_to_gaussians_forward(const GmsFreeArgs *args, float *scaling_activated, float *rotation_unit, float *opacity_activated,
+                                      void *stream);
+/* One launch.  Gradients w.r.t. the activated values (NULL: zero) -> the raw parameters (NULL: not written): dL_d_scaling
+ * [P,scaling_cols], dL_d_rotation [P,4], dL_d_opacity [P].  torch's own derivative of F.normalize, the branch below the clamp
+ * included.  Plain stores of each Gaussian's own entries: no atomics, bit-identical run to run. */
+int32_t gms_free_to_gaussians_backward(const GmsFreeArgs *args, const float *dL_dscaling_activated, const float *dL_drotation_unit,
+                                       const float *dL_dopacity_activated, float *dL_d_scaling, float *dL_d_rotation, float *dL_d_opacity,
+                                       void *stream);
+
+/* gms_rasterize_forward on a free model's raw parameters: `args->means3D` is the raw `_xyz`; `args->scales`, `rotations`,
+ * `opacities` are ignored (may be NULL) and the preprocess thread derives them from `free_args` with the arithmetic of
+ * gms_free_to_gaussians_forward, bit for bit.  Needs `mesh` and `points` NULL, free_args->P == P, split degree-3 SH storage (shs +
+ * shs_rest, M = 16, active degree 0 .. 3, 16-byte aligned) and no precomputed colours / covariances.  Everything else -- return
+ * value, capacity hint, count ticket, no_host_wait -- as gms_rasterize_forward. */
+int64_t gms_rasterize_forward_free(const GmsRasterForwardArgs *args, const GmsFreeArgs *free_args, void *stream);
+/* ... and its backward: gms_rasterize_backward with the getters' backward in the tail of the per-Gaussian kernel.  `args->scales`,
+ * `rotations`, `opacities` are ignored; `dL_dscales`, `dL_drotations`, `dL_dopacity` are not written (may be NULL).  The raw gradients
+ * dL_d_scaling [P,scaling_cols], dL_d_rotation [P,4] (16-byte aligned), dL_d_opacity [P] are plain stores; dL_dmeans3D (the gradient of
+ * `_xyz`), dL_dmeans2D and the SH gradients are written as usual.  Needs the scales + rotations path (no cov3D_precomp) and no mesh.
+ * Valid in deterministic mode. */
+int32_t gms_rasterize_backward_free(const GmsRasterBackwardArgs *args, const GmsFreeArgs *free_args, float *dL_d_scaling,
+                                    float *dL_d_rotation, float *dL_d_opacity, void *stream);
+
 /* ---- exact 3-NN mean squared distance ---------------------------------
  * Replaces the un-vendored `simple_knn._C.distCUDA2(points)` (.gitmodules:1-3) called at
  * scene/gaussian_model.py:134 and games/flat_splatting/scene/flat_gaussian_model.py:47 to size the initial
