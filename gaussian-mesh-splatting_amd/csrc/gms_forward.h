@@ -26,9 +26,10 @@ struct PreArgs {
 
 // K1.  Picks the instantiation: the frame straight from a free model's raw parameters (`free_args`), from pseudo-triangles (`points`),
 // straight from the mesh (`fused_mesh`, a.mesh), or from tensors -- at the active degree a.D when `fast_layout` (M = 16, 16-byte aligned
-// rows), else the generic-width kernel.
+// rows), else the generic-width kernel.  `rest_rotation` (mesh / points only; else NULL): [P,4] unit quaternions of the pose the SH
+// coefficients were learned in -- the instantiations that evaluate them on the pose-local direction (gms_local_sh.h).
 int32_t launch_preprocess_forward(const PreArgs &a, const GmsPointsArgs *points, const GmsFreeArgs *free_args, bool fused_mesh, bool fast_layout,
-                                  bool debug, hipStream_t stream);
+                                  const float *rest_rotation, bool debug, hipStream_t stream);
 
 // What the binning launches of one frame share.  `pub_slot`: the pinned words the frame's counts are published to (NULL: nobody
 // reads them); `planned_np`: the merge-path passes the frame was planned with (a run whose scratch is too short sorts with 0).

@@ -12,6 +12,7 @@
 #include "gms_mesh.h"
 #include "gms_points.h"
 #include "gms_free.h"
+#include "gms_local_sh.h"
 #include "gms_common.h"
 #include "gms_project.h"
 #include "gms_forward.h"
@@ -81,14 +82,20 @@ __device__ __forceinline__ void store_sh_ddir(float *sh_ddir, int i, const float
 // FREE (gms_rasterize_forward_free; training frames of gs / gs_flat models): the centre is loaded as ever, scale / rotation / opacity are
 // the getters of the raw rows -- 4 S + 16 + 4 bytes in, the statements of free_fwd_kernel (gms_free.h) -- `fr` is only read by that
 // instantiation.
-template <int SHDEG, bool SPLIT, bool DMA = false, bool K0 = false, bool PTS = false, bool FREE = false>
-__device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsPointsArgs &pts = GmsPointsArgs{}, const GmsFreeArgs &fr = GmsFreeArgs{})
+// LOCAL (gms_rasterize_forward_local_sh; forward-only mesh / points frames): the SH rows are evaluated on the view direction taken back
+// into the pose the coefficients were learned in, R(q_0) R(q_t)^T n (gms_local_sh.h) -- q_t is the unit quaternion the thread has just
+// derived, q_0 its row of `rest_rot` (16 bytes, loaded with the other early loads).  Nothing else of the frame changes; `sh_ddir` is not
+// stored (no backward reads a forward-only frame's).  `rest_rot` is only read by that instantiation.
+template <int SHDEG, bool SPLIT, bool DMA = false, bool K0 = false, bool PTS = false, bool FREE = false, bool LOCAL = false>
+__device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsPointsArgs &pts = GmsPointsArgs{}, const GmsFreeArgs &fr = GmsFreeArgs{},
+                                                    const float *rest_rot = nullptr)
 {
 #pragma clang fp contract(off)
     static_assert(!DMA || (SHDEG >= 0 && SHDEG <= 3 && SPLIT), "the LDS-DMA staging exists for split degree-3 STORAGE (any active degree: the rows come in whole)");
     static_assert(!K0 || DMA, "the fused mesh input rides on the LDS-DMA instantiation");
     static_assert(!PTS || (DMA && !K0), "the fused points input rides on the LDS-DMA instantiation, without the mesh input");
     static_assert(!FREE || (DMA && !K0 && !PTS), "the raw-parameter input rides on the LDS-DMA instantiation, without the mesh / points input");
+    static_assert(!LOCAL || K0 || PTS, "the pose-local SH direction exists for the fused mesh / points inputs (the thread holds q_t)");
     static_assert(DMA || !SPLIT || SHDEG != 3, "split degree-3 storage is staged by LDS-DMA (the register-staged rows were measured and removed)");
     // Round 6: the REST rows come in as TWO halves of 32 rows through the same 6 KB of LDS per wave (6 x 1 KiB DMA instructions each,
     // 1 440 of the 1 536 floats used), the 64 x 3 DC floats behind them: 27 KB per block instead of 49.
@@ -122,6 +129,8 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsP
     if (PTS && valid) points_inputs_load(pts, (int64_t)i, ptin);           // (likewise)
     FreeRaw frin = {};
     if (FREE && valid) free_inputs_load(fr, (int64_t)i, frin);             // (likewise)
+    float4 q0_in = make_float4(1.f, 0.f, 0.f, 0.f);
+    if (LOCAL && valid) q0_in = *reinterpret_cast<const float4 *>(rest_rot + 4 * (size_t)i);          // (likewise)
     if (SHDEG >= 0) {
         const int g0 = blockIdx.x * BLOCK + wave * WAVE;
         const int rows = min(WAVE, a.P - g0);
@@ -263,6 +272,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsP
             const float dx = px - a.campos[0], dy = py - a.campos[1], dz = pz - a.campos[2];
             const float inv = 1.f / sqrtf(dx * dx + dy * dy + dz * dz);
             dxc = dx * inv; dyc = dy * inv; dzc = dz * inv;
+            if (LOCAL) local_sh_direction(q0_in, q_in, dxc, dyc, dzc);
         }
 #pragma unroll
         for (int half = 0; half < 2; half++) {
@@ -302,7 +312,7 @@ __device__ __forceinline__ void preprocess_fwd_body(const PreArgs &a, const GmsP
                     if (v < 0.f) { clampbits |= 1u << c; v = 0.f; }
                     rgb[c] = v;
                 }
-                store_sh_ddir(a.geom.sh_ddir, i, ddir);
+                if (!LOCAL) store_sh_ddir(a.geom.sh_ddir, i, ddir);
             }
         }
     } else if (SHDEG >= 0) {
@@ -456,6 +466,19 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5
     preprocess_fwd_body<DEG, true, true, false, false, true>(a, GmsPointsArgs{}, fr);
 }
 
+// ... the forward-only mesh and points frames with pose-local SH (gms_rasterize_forward_local_sh): kernels of their own, so that the ones
+// above keep their code; the same 27 KB of LDS and launch bounds.  `rest`: [P,4] unit quaternions, 16-byte aligned.
+template <int DEG>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5))) preprocess_fwd_local_sh_mesh_kernel(PreArgs a, const float *rest)
+{
+    preprocess_fwd_body<DEG, true, true, true, false, false, true>(a, GmsPointsArgs{}, GmsFreeArgs{}, rest);
+}
+template <int DEG>
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(5, 5))) preprocess_fwd_local_sh_points_kernel(PreArgs a, GmsPointsArgs pts, const float *rest)
+{
+    preprocess_fwd_body<DEG, true, true, false, true, false, true>(a, pts, GmsFreeArgs{}, rest);
+}
+
 // The fused inputs hold split degree-3 storage (validate_forward): the active degree alone picks the preprocess instantiation
 template <typename Launch> static void dispatch_degree(int D, Launch &&launch)
 {
@@ -468,10 +491,17 @@ template <typename Launch> static void dispatch_degree(int D, Launch &&launch)
 }
 
 int32_t launch_preprocess_forward(const PreArgs &pa, const GmsPointsArgs *points, const GmsFreeArgs *free_args, bool fused_mesh, bool fast_layout,
-                                  bool debug, hipStream_t stream)
+                                  const float *rest_rotation, bool debug, hipStream_t stream)
 {
     const unsigned pblocks = (unsigned)((pa.P + BLOCK - 1) / BLOCK);
-    if (free_args) {
+    if (rest_rotation && points) {
+        dispatch_degree(pa.D, [&](auto d) { GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_local_sh_points_kernel<d.value><<<pblocks, BLOCK, 0, stream>>>(pa, *points, rest_rotation))); });
+    } else if (rest_rotation && fused_mesh) {
+        dispatch_degree(pa.D, [&](auto d) { GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_local_sh_mesh_kernel<d.value><<<pblocks, BLOCK, 0, stream>>>(pa, rest_rotation))); });
+    } else if (rest_rotation) {
+        set_error("preprocess_fwd: the pose-local SH direction needs the fused mesh or points input");
+        return GMS_ERR_INVALID_ARGUMENT;
+    } else if (free_args) {
         dispatch_degree(pa.D, [&](auto d) { GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_free_kernel<d.value><<<pblocks, BLOCK, 0, stream>>>(pa, *free_args))); });
     } else if (points) {
         dispatch_degree(pa.D, [&](auto d) { GMS_LAUNCH(GMS_K_PREPROCESS_FWD, stream, (preprocess_fwd_points_kernel<d.value><<<pblocks, BLOCK, 0, stream>>>(pa, *points))); });

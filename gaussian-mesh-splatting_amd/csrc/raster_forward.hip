@@ -436,8 +436,9 @@ static void *alloc_binning(const GmsRasterForwardArgs *A, uint64_t capacity, int
     return mem;
 }
 
-// gms_rasterize_forward and gms_rasterize_forward_free (`free_args` set): one driver, the preprocess instantiation differs
-static int64_t rasterize_forward(const GmsRasterForwardArgs *A, const GmsFreeArgs *free_args, hipStream_t stream)
+// gms_rasterize_forward, gms_rasterize_forward_free (`free_args` set) and gms_rasterize_forward_local_sh (`rest_rotation` set): one driver,
+// the preprocess instantiation differs
+static int64_t rasterize_forward(const GmsRasterForwardArgs *A, const GmsFreeArgs *free_args, hipStream_t stream, const float *rest_rotation = nullptr)
 {
     g_err[0] = 0;
     if (const int32_t rc = validate_forward(A, free_args)) return rc;
@@ -474,7 +475,7 @@ static int64_t rasterize_forward(const GmsRasterForwardArgs *A, const GmsFreeArg
     const bool inline_scan = inline_scan_setting() && hint > 0 && frame_L != 0 && inline_scan_fits(T, P);
     // K1: the frame straight from a mesh or from pseudo-triangles (gmsplat.h) runs K0 inside the preprocess thread
     const PreArgs pa = pre_args(A, free_args != nullptr, geom, img, gx, gy, inline_scan);
-    if (const int32_t rc = launch_preprocess_forward(pa, A->points, free_args, A->mesh != nullptr, sh_fast_layout(A, free_args), debug, stream)) return rc;
+    if (const int32_t rc = launch_preprocess_forward(pa, A->points, free_args, A->mesh != nullptr, sh_fast_layout(A, free_args), rest_rotation, debug, stream)) return rc;
     const uint32_t L = seg_len_min();
     // deferred read-back (gmsplat.h, count_ticket_out): this frame's counts go to the next slot of the thread's ring and nobody waits here
     const bool defer = A->count_ticket_out != nullptr && hint > 0 && !A->no_host_wait;
@@ -551,6 +552,26 @@ extern "C" int64_t gms_rasterize_forward_free(const GmsRasterForwardArgs *A, con
     gms::TraceRange trace_range("gms_rasterize_forward_free");
     if (!free_args) { set_error("gms_rasterize_forward_free: NULL GmsFreeArgs"); return GMS_ERR_INVALID_ARGUMENT; }
     return rasterize_forward(A, free_args, (hipStream_t)stream_);
+}
+
+extern "C" int64_t gms_rasterize_forward_local_sh(const GmsRasterForwardArgs *A, const float *rest_rotation, void *stream_)
+{
+    gms::TraceRange trace_range("gms_rasterize_forward_local_sh");
+    if (!rest_rotation || !aligned16(rest_rotation)) {
+        set_error("gms_rasterize_forward_local_sh: rest_rotation must be a non-NULL, 16-byte aligned [P,4] array of unit quaternions");
+        return GMS_ERR_INVALID_ARGUMENT;
+    }
+    if (!A || (!A->mesh && !A->points)) {
+        set_error("gms_rasterize_forward_local_sh: needs the fused mesh or points input (args->mesh / args->points): the thread that derives the "
+                  "Gaussian's rotation turns its view direction");
+        return GMS_ERR_INVALID_ARGUMENT;
+    }
+    if (A->mesh_out_xyz || A->mesh_out_scaling_act || A->mesh_out_rotation_unit || A->mesh_out_opacity_act) {
+        set_error("gms_rasterize_forward_local_sh: mesh_out_* must be NULL (a forward-only frame: the backward of a training frame would read a "
+                  "direction derivative this frame does not store)");
+        return GMS_ERR_INVALID_ARGUMENT;
+    }
+    return rasterize_forward(A, nullptr, (hipStream_t)stream_, rest_rotation);
 }
 
 extern "C" int64_t gms_rasterize_forward_counts(const int64_t *ticket, int32_t width, int32_t height, int32_t P, int64_t *num_units_out,

@@ -161,9 +161,10 @@ Gaussians tensor_gaussians(const Tensor &means3D, const Tensor &sh, const Tensor
 
 // `mesh` / `points`: the forward-only frame straight from a mesh or pseudo-triangles (gmsplat.h); `g` then holds only the SH tensors.
 // `free_args`: the frame straight from a free model's raw parameters (gms_rasterize_forward_free); `g` holds the SH tensors and means3D
+// `rest_rotation`: a mesh / points frame with pose-local SH (gms_rasterize_forward_local_sh): [P,4] unit quaternions the caller keeps alive
 Forward forward_core(const FrameSettings &s, int64_t P, c10::Device dev, const Gaussians &g, const Tensor &visible, bool use_hint,
                      const GmsMeshArgs *mesh = nullptr, const MeshOut *mesh_out = nullptr, bool may_defer = false, const GmsPointsArgs *points = nullptr,
-                     const GmsFreeArgs *free_args = nullptr)
+                     const GmsFreeArgs *free_args = nullptr, const float *rest_rotation = nullptr)
 {
     c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
     const bool has_sh = g.sh.defined() && g.sh.numel() > 0;
@@ -220,9 +221,11 @@ Forward forward_core(const FrameSettings &s, int64_t P, c10::Device dev, const G
     int64_t ticket[2] = {0, 0};
     const bool defer = may_defer && hint > 0 && !capturing && P > 0 && deferred_counts();
     if (defer) a.count_ticket_out = ticket;
-    const int64_t n = free_args ? gms_rasterize_forward_free(&a, free_args, stream) : gms_rasterize_forward(&a, stream);
+    const int64_t n = rest_rotation ? gms_rasterize_forward_local_sh(&a, rest_rotation, stream)
+                      : free_args   ? gms_rasterize_forward_free(&a, free_args, stream)
+                                    : gms_rasterize_forward(&a, stream);
     TORCH_CHECK(!(geom.failed || binning.failed || image.failed), "scratch allocation failed (out of device memory?)");
-    check_rc(n, free_args ? "gms_rasterize_forward_free" : "gms_rasterize_forward");
+    check_rc(n, rest_rotation ? "gms_rasterize_forward_local_sh" : free_args ? "gms_rasterize_forward_free" : "gms_rasterize_forward");
     f.num_rendered = n; f.num_units = num_units;
     f.capacity = (hint > 0 && n <= hint) ? hint : (n > 0 ? n : 1);
     f.geom = geom.t; f.binning = binning.t; f.image = image.t;
@@ -612,22 +615,55 @@ int64_t check_mesh_frame(const char *what, const Tensor &vertices, const Tensor 
     return P;
 }
 
+// The quaternions of a pose-local frame: [P,4] float32, contiguous, on the frame's device, unit (the python wrapper normalises them once)
+const float *rest_rotation_ptr(const char *what, const Tensor &rest_rotation, int64_t P, c10::Device dev)
+{
+    TORCH_CHECK(rest_rotation.defined() && rest_rotation.dim() == 2 && rest_rotation.size(0) == P && rest_rotation.size(1) == 4, what,
+                ": rest_rotation must have dimensions (", P, ", 4)");
+    TORCH_CHECK(rest_rotation.is_cuda() && rest_rotation.device() == dev && rest_rotation.scalar_type() == torch::kFloat && rest_rotation.is_contiguous(),
+                what, ": rest_rotation must be a contiguous float32 tensor on the frame's device");
+    return rest_rotation.data_ptr<float>();
+}
+
 // Forward-only frame of the animated render drivers (games_hip.animate): mesh -> image in the rasterizer's own launches, K0 inside
 // the preprocess thread (GmsRasterForwardArgs.mesh).  Returns (image, radii, inverse depth, radii > 0).
+// `rest_rotation` (render_mesh_forward_local_sh; undefined: the plain frame): the SH rows are evaluated on the pose-local direction.
+std::tuple<Tensor, Tensor, Tensor, Tensor> mesh_forward_frame(const char *what, const Tensor &vertices, const Tensor &faces, const Tensor &_alpha,
+                                                      const Tensor &_scale, const Tensor &_opacity, int64_t mode, int64_t spf,
+                                                      const Tensor &splat_face, const Tensor &sh_dc, const Tensor &sh_rest, const Tensor &bg,
+                                                      const Tensor &view, const Tensor &proj, const Tensor &campos, int64_t H, int64_t W,
+                                                      double tanx, double tany, double mod, bool aa, bool debug, const Tensor &rest_rotation)
+{
+    const int64_t P = check_mesh_frame(what, vertices, faces, _alpha, _scale, _opacity, spf, splat_face, sh_dc, sh_rest);
+    const float *rest = rest_rotation.defined() ? rest_rotation_ptr(what, rest_rotation, P, sh_dc.device()) : nullptr;
+    Tensor v = f32c(vertices), al = f32c(_alpha), sc = f32c(_scale), op = f32c(_opacity);
+    GmsMeshArgs m = mesh_args(v, faces, al, sc, mode, spf, Tensor(), splat_face, true, op);
+    Tensor visible = torch::empty({P}, sh_dc.options().dtype(torch::kBool));          // radii > 0, written by the preprocess kernel
+    const auto dev = sh_dc.device();
+    Forward f = forward_core(frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, 3, false, aa, debug), P, dev,
+                             {f32c(sh_dc), f32c(sh_rest)}, visible, true, &m, nullptr, false, nullptr, nullptr, rest);
+    return std::make_tuple(f.color, f.radii, f.invdepth, visible);
+}
 std::tuple<Tensor, Tensor, Tensor, Tensor> render_mesh_forward(const Tensor &vertices, const Tensor &faces, const Tensor &_alpha, const Tensor &_scale,
                                                        const Tensor &_opacity, int64_t mode, int64_t spf, const Tensor &splat_face,
                                                        const Tensor &sh_dc, const Tensor &sh_rest, const Tensor &bg, const Tensor &view,
                                                        const Tensor &proj, const Tensor &campos, int64_t H, int64_t W, double tanx, double tany,
                                                        double mod, bool aa, bool debug)
 {
-    const int64_t P = check_mesh_frame("render_mesh_forward", vertices, faces, _alpha, _scale, _opacity, spf, splat_face, sh_dc, sh_rest);
-    Tensor v = f32c(vertices), al = f32c(_alpha), sc = f32c(_scale), op = f32c(_opacity);
-    GmsMeshArgs m = mesh_args(v, faces, al, sc, mode, spf, Tensor(), splat_face, true, op);
-    Tensor visible = torch::empty({P}, sh_dc.options().dtype(torch::kBool));          // radii > 0, written by the preprocess kernel
-    const auto dev = sh_dc.device();
-    Forward f = forward_core(frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, 3, false, aa, debug), P, dev,
-                             {f32c(sh_dc), f32c(sh_rest)}, visible, true, &m);
-    return std::make_tuple(f.color, f.radii, f.invdepth, visible);
+    return mesh_forward_frame("render_mesh_forward", vertices, faces, _alpha, _scale, _opacity, mode, spf, splat_face, sh_dc, sh_rest, bg, view, proj,
+                              campos, H, W, tanx, tany, mod, aa, debug, Tensor());
+}
+// ... with spherical harmonics that turn with the face (gms_rasterize_forward_local_sh): the same arguments, then rest_rotation [P,4]
+std::tuple<Tensor, Tensor, Tensor, Tensor> render_mesh_forward_local_sh(const Tensor &vertices, const Tensor &faces, const Tensor &_alpha,
+                                                                const Tensor &_scale, const Tensor &_opacity, int64_t mode, int64_t spf,
+                                                                const Tensor &splat_face, const Tensor &sh_dc, const Tensor &sh_rest,
+                                                                const Tensor &bg, const Tensor &view, const Tensor &proj, const Tensor &campos,
+                                                                int64_t H, int64_t W, double tanx, double tany, double mod, bool aa, bool debug,
+                                                                const Tensor &rest_rotation)
+{
+    TORCH_CHECK(rest_rotation.defined(), "render_mesh_forward_local_sh: rest_rotation is required");
+    return mesh_forward_frame("render_mesh_forward_local_sh", vertices, faces, _alpha, _scale, _opacity, mode, spf, splat_face, sh_dc, sh_rest, bg,
+                              view, proj, campos, H, W, tanx, tany, mod, aa, debug, rest_rotation);
 }
 
 class MeshFn : public torch::autograd::Function<MeshFn> {
@@ -803,10 +839,12 @@ std::vector<Tensor> points_to_gaussians(const Tensor &triangles, const Tensor &_
 // Forward-only frame of the gs_points render drivers (games_hip.render.render_points_animated): pseudo-triangles -> image in the
 // rasterizer's own launches, the points op inside the preprocess thread (GmsRasterForwardArgs.points).  Returns (image, radii,
 // inverse depth, radii > 0).
-std::tuple<Tensor, Tensor, Tensor, Tensor> render_points_forward(const Tensor &triangles_, const Tensor &_opacity, const Tensor &sh_dc,
-                                                         const Tensor &sh_rest, const Tensor &bg, const Tensor &view, const Tensor &proj,
-                                                         const Tensor &campos, int64_t H, int64_t W, double tanx, double tany, double mod,
-                                                         bool aa, bool debug, int64_t sh_degree, double eps, double eps_s0)
+// `rest_rotation` (render_points_forward_local_sh; undefined: the plain frame): the SH rows are evaluated on the pose-local direction.
+std::tuple<Tensor, Tensor, Tensor, Tensor> points_forward_frame(const Tensor &triangles_, const Tensor &_opacity, const Tensor &sh_dc,
+                                                        const Tensor &sh_rest, const Tensor &bg, const Tensor &view, const Tensor &proj,
+                                                        const Tensor &campos, int64_t H, int64_t W, double tanx, double tany, double mod,
+                                                        bool aa, bool debug, int64_t sh_degree, double eps, double eps_s0,
+                                                        const Tensor &rest_rotation)
 {
     Tensor tri = points_triangles(triangles_, "render_points_forward");
     require_gpu(_opacity); require_gpu(sh_dc); require_gpu(sh_rest);
@@ -816,12 +854,32 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> render_points_forward(const Tensor &t
     TORCH_CHECK(op.numel() == P && sh_dc.size(0) == P && sh_rest.size(0) == P, "render_points_forward: P mismatch");
     TORCH_CHECK(tri.device() == sh_dc.device() && op.device() == sh_dc.device(), "render_points_forward: triangles and SH tensors live on different devices");
     check_split_sh("render_points_forward", sh_dc, sh_rest);
+    const float *rest = rest_rotation.defined() ? rest_rotation_ptr("render_points_forward_local_sh", rest_rotation, P, sh_dc.device()) : nullptr;
     GmsPointsArgs pa = points_args(tri, op, eps, eps_s0);
     Tensor visible = torch::empty({P}, sh_dc.options().dtype(torch::kBool));          // radii > 0, written by the preprocess kernel
     const auto dev = sh_dc.device();
     Forward f = forward_core(frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, sh_degree, false, aa, debug), P, dev,
-                             {f32c(sh_dc), f32c(sh_rest)}, visible, true, nullptr, nullptr, false, &pa);
+                             {f32c(sh_dc), f32c(sh_rest)}, visible, true, nullptr, nullptr, false, &pa, nullptr, rest);
     return std::make_tuple(f.color, f.radii, f.invdepth, visible);
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> render_points_forward(const Tensor &triangles_, const Tensor &_opacity, const Tensor &sh_dc,
+                                                         const Tensor &sh_rest, const Tensor &bg, const Tensor &view, const Tensor &proj,
+                                                         const Tensor &campos, int64_t H, int64_t W, double tanx, double tany, double mod,
+                                                         bool aa, bool debug, int64_t sh_degree, double eps, double eps_s0)
+{
+    return points_forward_frame(triangles_, _opacity, sh_dc, sh_rest, bg, view, proj, campos, H, W, tanx, tany, mod, aa, debug, sh_degree, eps, eps_s0,
+                                Tensor());
+}
+// ... with spherical harmonics that turn with the triangle (gms_rasterize_forward_local_sh): the same arguments, then rest_rotation [P,4]
+std::tuple<Tensor, Tensor, Tensor, Tensor> render_points_forward_local_sh(const Tensor &triangles_, const Tensor &_opacity, const Tensor &sh_dc,
+                                                                  const Tensor &sh_rest, const Tensor &bg, const Tensor &view, const Tensor &proj,
+                                                                  const Tensor &campos, int64_t H, int64_t W, double tanx, double tany,
+                                                                  double mod, bool aa, bool debug, int64_t sh_degree, double eps, double eps_s0,
+                                                                  const Tensor &rest_rotation)
+{
+    TORCH_CHECK(rest_rotation.defined(), "render_points_forward_local_sh: rest_rotation is required");
+    return points_forward_frame(triangles_, _opacity, sh_dc, sh_rest, bg, view, proj, campos, H, W, tanx, tany, mod, aa, debug, sh_degree, eps, eps_s0,
+                                rest_rotation);
 }
 
 // ---------------------------------------------------------------------------------------------- training frame straight from the mesh
@@ -1633,9 +1691,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("rasterize", &rasterize, "differentiable rasterization (autograd node in C++)", nogil());
     m.def("mesh_to_gaussians", &mesh_to_gaussians, "differentiable mesh-face -> Gaussian parameterization", nogil());
     m.def("render_mesh_forward", &render_mesh_forward, "forward-only frame straight from a mesh (K0 inside the preprocess thread)", nogil());
+    m.def("render_mesh_forward_local_sh", &render_mesh_forward_local_sh, "render_mesh_forward with SH evaluated on the pose-local direction: + rest_rotation [P,4]", nogil());
     m.def("points_to_gaussians", &points_to_gaussians, "differentiable pseudo-triangle -> Gaussian: [xyz, scaling_raw, rotation_raw, scaling_act, rotation_unit(, opacity_act)]", nogil());
     m.def("points_prepare_vertices", &points_prepare_vertices, "Gaussian -> pseudo-triangle [P,3,3] (prepare_vertices)", nogil());
     m.def("render_points_forward", &render_points_forward, "forward-only frame straight from pseudo-triangles (the points op inside the preprocess thread)", nogil());
+    m.def("render_points_forward_local_sh", &render_points_forward_local_sh, "render_points_forward with SH evaluated on the pose-local direction: + rest_rotation [P,4]", nogil());
     m.def("bind_pseudomesh", &bind_pseudomesh, "bind pseudo-triangles [P,3,3] to the nearest faces of a guide mesh: (face_idx int32 [P], alpha [P,3,3], n_degenerate)", nogil());
     m.def("bind_apply", &bind_apply, "pseudo-triangles [P,3,3] of a binding on (edited) guide vertices; launches only", py::arg("face_idx"), py::arg("alpha"),
           py::arg("guide_vertices"), py::arg("guide_faces"), py::arg("out") = py::none(), nogil());

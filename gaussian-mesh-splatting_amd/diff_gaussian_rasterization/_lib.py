@@ -224,6 +224,7 @@ EXPORTS = (
     "gms_ground_truth_workspace_bytes", "gms_ground_truth_u8",
     "gms_resize_workspace_bytes", "gms_resize_tile_columns", "gms_resize_u8",
     "gms_free_to_gaussians_forward", "gms_free_to_gaussians_backward", "gms_rasterize_forward_free", "gms_rasterize_backward_free",
+    "gms_rasterize_forward_local_sh",
 )
 K_COUNT = 23
 
@@ -267,6 +268,8 @@ def load():
         lib.gms_free_to_gaussians_backward.argtypes = [C.POINTER(FreeArgs)] + [C.c_void_p] * 7
         lib.gms_rasterize_forward_free.restype = C.c_int64
         lib.gms_rasterize_forward_free.argtypes = [C.POINTER(RasterForwardArgs), C.POINTER(FreeArgs), C.c_void_p]
+        lib.gms_rasterize_forward_local_sh.restype = C.c_int64
+        lib.gms_rasterize_forward_local_sh.argtypes = [C.POINTER(RasterForwardArgs), C.c_void_p, C.c_void_p]
         lib.gms_rasterize_backward_free.restype = C.c_int32
         lib.gms_rasterize_backward_free.argtypes = [C.POINTER(RasterBackwardArgs), C.POINTER(FreeArgs)] + [C.c_void_p] * 4
         lib.gms_abi_version.restype = C.c_int32

@@ -66,44 +66,62 @@ def _save(image: torch.Tensor, path: str) -> None:
     Image.fromarray(a).save(path)
 
 
-def render_frame(vertices: torch.Tensor, faces: torch.Tensor, view, gaussians, pipeline, background: torch.Tensor):
+def _prepared(rest_rotation, P: int, device):
+    """`rest_rotation` checked and normalised once, in front of a driver's loop (games_hip.local_sh); None stays None."""
+    if rest_rotation is None:
+        return None
+    from .local_sh import prepared_rest_rotation
+    return prepared_rest_rotation(rest_rotation, P, device)
+
+
+def _no_flame_local_sh(what: str, rest_rotation) -> None:
+    if rest_rotation is not None:
+        raise NotImplementedError(f"{what}: pose-local SH (rest_rotation) is not defined for gs_flame -- the model has no single training "
+                                  "pose: every training frame carries its own expression and pose")
+
+
+def render_frame(vertices: torch.Tensor, faces: torch.Tensor, view, gaussians, pipeline, background: torch.Tensor, rest_rotation=None):
     """One animated frame from deformed vertices.  Forward-only frames of a model the fused path supports go mesh -> image in the
     rasterizer's own launches (`render_mesh_frame`: no `vertices[faces]` gather, no K0 launch, no xyz / scale / rotation tensors);
-    anything else takes the reference's route, `render_animated(None, vertices[faces], ...)`.  Same image bit for bit."""
+    anything else takes the reference's route, `render_animated(None, vertices[faces], ...)`.  Same image bit for bit.
+    `rest_rotation`: pose-local SH (games_hip.local_sh), on either route."""
     if _fused_frame_ok(gaussians, pipeline, None):
-        return render_mesh_frame(vertices, faces, view, gaussians, pipeline, background)
-    return render_animated(None, vertices[faces].float(), view, gaussians, pipeline, background)
+        return render_mesh_frame(vertices, faces, view, gaussians, pipeline, background, rest_rotation=rest_rotation)
+    return render_animated(None, vertices[faces].float(), view, gaussians, pipeline, background, rest_rotation=rest_rotation)
 
 
 @torch.no_grad()
 def render_time_animated(gaussians, views: Iterable, pipeline, background: torch.Tensor,
                          transform: Callable = transform_hotdog_fly, idxs=None, out_dir: Optional[str] = None,
-                         t_max: float = 10 * math.pi, mesh: int = 0) -> List[torch.Tensor]:
+                         t_max: float = 10 * math.pi, mesh: int = 0, rest_rotation=None) -> List[torch.Tensor]:
     """scripts/render_time_animated.py:68-87.  Returns the rendered frames (device tensors [3,H,W]).  A multi-mesh model
     (`gaussians.vertices` a list): the transform moves mesh number `mesh` against the others, every frame goes mesh -> image
-    (`render_mesh_frame` with per-mesh vertices)."""
+    (`render_mesh_frame` with per-mesh vertices).  `rest_rotation` ([P,4], games_hip.local_sh.rest_rotation_of(gaussians) taken
+    before the loop): the SH colours turn with the faces."""
     views = list(views)
     ts = torch.linspace(0, t_max, max(len(views), 1))
     if isinstance(gaussians.vertices, (list, tuple)):
         per_mesh = [v.detach().clone() for v in gaussians.vertices]      # working copies, as below
+        rest = _prepared(rest_rotation, sum(int(a.shape[0] * a.shape[1]) for a in gaussians._alpha), per_mesh[0].device)
         frames = []
         if out_dir:
             os.makedirs(out_dir, exist_ok=True)
         for k, view in enumerate(views):
             per_mesh[mesh] = transform(per_mesh[mesh], ts[k], idxs)
-            img = render_mesh_frame(per_mesh, None, view, gaussians, pipeline, background)["render"]
+            img = render_mesh_frame(per_mesh, None, view, gaussians, pipeline, background, rest_rotation=rest)["render"]
             frames.append(img)
             if out_dir:
                 _save(img, os.path.join(out_dir, f"{k:05d}.png"))
         return frames
     vertices = gaussians.vertices.detach().clone()      # working copy: the in-place transforms accumulate in it, as in the reference
     faces = gaussians.faces.long()
+    rest = _prepared(rest_rotation, int(gaussians._alpha.shape[0] * gaussians._alpha.shape[1]), vertices.device)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
     frames = []
     for k, view in enumerate(views):
         new_vertices = transform(vertices, ts[k], idxs)
-        img = render_frame(new_vertices, faces, view, gaussians, pipeline, background)["render"]
+        img = render_frame(new_vertices, faces, view, gaussians, pipeline, background, rest_rotation=rest)["render"]
         frames.append(img)
         if out_dir:
             _save(img, os.path.join(out_dir, f"{k:05d}.png"))
@@ -112,9 +130,11 @@ def render_time_animated(gaussians, views: Iterable, pipeline, background: torch
 
 @torch.no_grad()
 def render_flame_animated(gaussians, views: Iterable, pipeline, background: torch.Tensor, drive: Callable,
-                          out_dir: Optional[str] = None) -> List[torch.Tensor]:
+                          out_dir: Optional[str] = None, rest_rotation=None) -> List[torch.Tensor]:
     """scripts/render_flame.py:29-60 shape: per frame `drive(gaussians, k)` edits the FLAME parameters in place
-    (expression / pose / neck / translation), update_alpha() runs the FLAME layer + ONE K0 launch, then the plain render."""
+    (expression / pose / neck / translation), update_alpha() runs the FLAME layer + ONE K0 launch, then the plain render.
+    `rest_rotation` must stay None (pose-local SH is not defined for gs_flame)."""
+    _no_flame_local_sh("render_flame_animated", rest_rotation)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
     frames = []
@@ -146,13 +166,18 @@ class GraphedAnimation:
         anim = GraphedAnimation(gaussians, view, pipeline, background)
         for k in range(n_frames):
             img = anim.render(transform(vertices, t[k])[faces].float(), check=True)
+
+    `rest_rotation` ([P,4], games_hip.local_sh.rest_rotation_of(gaussians)): the SH colours turn with the faces; the quaternions are a
+    static input of the captured graph.
     """
 
-    def __init__(self, gaussians, view, pipeline, background: torch.Tensor, warmup: int = 3):
+    def __init__(self, gaussians, view, pipeline, background: torch.Tensor, warmup: int = 3, rest_rotation=None):
         import diff_gaussian_rasterization as dgr
         if dgr._C is None:
             raise NotImplementedError("GraphedAnimation needs the _C extension module")
         self._dgr = dgr
+        # pose-local SH (games_hip.local_sh): normalised once on the first capture, then a static input of the graph like the model's tensors
+        self._rest_given, self.rest = rest_rotation, None
         self.pc, self.view, self.pipe, self.bg, self.warmup = gaussians, view, pipeline, background, int(warmup)
         self.stream = torch.cuda.Stream(device=background.device)
         self.graph = None
@@ -166,6 +191,8 @@ class GraphedAnimation:
         dgr = self._dgr
         dev = triangles.device
         self.static_tri = triangles.detach().clone()
+        if self._rest_given is not None and self.rest is None:
+            self.rest = _prepared(self._rest_given, self._num_gaussians(), dev)
         W, H = int(self.view.image_width), int(self.view.image_height)
         P = self._num_gaussians()
         self.stream.wait_stream(torch.cuda.current_stream(dev))
@@ -194,7 +221,7 @@ class GraphedAnimation:
 
     # ---- what one frame is (GraphedPointsAnimation renders pseudo-triangles instead)
     def _frame(self, triangles: torch.Tensor) -> dict:
-        return render_animated(None, triangles, self.view, self.pc, self.pipe, self.bg)
+        return render_animated(None, triangles, self.view, self.pc, self.pipe, self.bg, rest_rotation=self.rest)
 
     def _num_gaussians(self) -> int:
         return int(self.pc._alpha.shape[0] * self.pc._alpha.shape[1])
@@ -239,11 +266,13 @@ def transform_hotdog(triangles, t):                        # scripts/render_poin
 
 @torch.no_grad()
 def render_points_time_animated(gaussians, views: Iterable, pipeline, background: torch.Tensor, transform: Callable = transform_hotdog,
-                                out_dir: Optional[str] = None, t_max: float = 10 * math.pi, frame_index: Optional[int] = 43) -> List[torch.Tensor]:
+                                out_dir: Optional[str] = None, t_max: float = 10 * math.pi, frame_index: Optional[int] = 43,
+                                rest_rotation=None) -> List[torch.Tensor]:
     """scripts/render_points_time_animated.py:33-48 (render_set) + :51-57: prepare_vertices / prepare_scaling_rot once, then per view
     the pseudo-triangles are deformed by `transform(triangles, t)` and rendered with `render_points_animated` -- straight from the
     triangles inside the rasterizer where the fused path applies.  `frame_index`: the reference renders every view at t[43] of
-    linspace(0, 10 pi, len(views)); None deforms view k with t[k] instead.  Returns the frames (device tensors [3,H,W])."""
+    linspace(0, 10 pi, len(views)); None deforms view k with t[k] instead.  Returns the frames (device tensors [3,H,W]).
+    `rest_rotation` ([P,4], games_hip.local_sh.rest_rotation_of(gaussians)): the SH colours turn with the triangles."""
     views = list(views)
     if hasattr(gaussians, "prepare_vertices"):
         gaussians.prepare_vertices()
@@ -251,12 +280,13 @@ def render_points_time_animated(gaussians, views: Iterable, pipeline, background
         gaussians.prepare_scaling_rot()
     ts = torch.linspace(0, t_max, max(len(views), 1))
     triangles = torch.stack([gaussians.v1, gaussians.v2, gaussians.v3], dim=1)
+    rest = _prepared(rest_rotation, int(triangles.shape[0]), triangles.device)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
     frames = []
     for k, view in enumerate(views):
         t = ts[frame_index] if frame_index is not None and frame_index < len(ts) else ts[k]
-        img = render_points_animated(transform(triangles, t), view, gaussians, pipeline, background)["render"]
+        img = render_points_animated(transform(triangles, t), view, gaussians, pipeline, background, rest_rotation=rest)["render"]
         frames.append(img)
         if out_dir:
             _save(img, os.path.join(out_dir, f"{k:05d}.png"))
@@ -273,7 +303,7 @@ class GraphedPointsAnimation(GraphedAnimation):
     """
 
     def _frame(self, triangles: torch.Tensor) -> dict:
-        return render_points_animated(triangles, self.view, self.pc, self.pipe, self.bg)
+        return render_points_animated(triangles, self.view, self.pc, self.pipe, self.bg, rest_rotation=self.rest)
 
     def _num_gaussians(self) -> int:
         return int(self.static_tri.shape[0])
@@ -282,19 +312,21 @@ class GraphedPointsAnimation(GraphedAnimation):
 # ---------------------------------------------------------------------------------------------- gs_points driven by a guide mesh
 @torch.no_grad()
 def render_points_mesh_animated(gaussians, views: Iterable, pipeline, background: torch.Tensor, binding, guide_faces: torch.Tensor,
-                                vertices_for_frame: Callable, out_dir: Optional[str] = None) -> List[torch.Tensor]:
+                                vertices_for_frame: Callable, out_dir: Optional[str] = None, rest_rotation=None) -> List[torch.Tensor]:
     """The gs_points loop with the pseudo-mesh bound to a guide mesh (games_hip.pseudomesh.bind_pseudomesh; the reference edits the
     pseudo-mesh with scripts/edit_pseudomesh_based_on_estimated_mesh.py and renders the saved triangles): per view k,
     `vertices_for_frame(k)` -> guide vertices [V,3], `deform_pseudomesh` -> pseudo-triangles, `render_points_animated`.  `guide_faces`:
-    the guide's faces [F,3] (converted to int32 on the device once).  Returns the frames (device tensors [3,H,W])."""
+    the guide's faces [F,3] (converted to int32 on the device once).  Returns the frames (device tensors [3,H,W]).
+    `rest_rotation` ([P,4]): the SH colours turn with the triangles (games_hip.local_sh)."""
     from .pseudomesh import deform_pseudomesh, guide_faces_int32
     faces = guide_faces_int32(guide_faces, binding.face_idx.device)
+    rest = _prepared(rest_rotation, int(binding.P), binding.face_idx.device)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
     frames = []
     for k, view in enumerate(views):
         triangles = deform_pseudomesh(binding, vertices_for_frame(k), faces)
-        img = render_points_animated(triangles, view, gaussians, pipeline, background)["render"]
+        img = render_points_animated(triangles, view, gaussians, pipeline, background, rest_rotation=rest)["render"]
         frames.append(img)
         if out_dir:
             _save(img, os.path.join(out_dir, f"{k:05d}.png"))
@@ -312,8 +344,9 @@ class GraphedBoundAnimation(GraphedPointsAnimation):
             img = anim.render(edited_vertices[k], check=True)
     """
 
-    def __init__(self, gaussians, view, pipeline, background: torch.Tensor, binding, guide_faces: torch.Tensor, warmup: int = 3):
-        super().__init__(gaussians, view, pipeline, background, warmup)
+    def __init__(self, gaussians, view, pipeline, background: torch.Tensor, binding, guide_faces: torch.Tensor, warmup: int = 3,
+                 rest_rotation=None):
+        super().__init__(gaussians, view, pipeline, background, warmup, rest_rotation)
         from .pseudomesh import deform_pseudomesh, guide_faces_int32
         self._deform = deform_pseudomesh
         self.binding = binding
@@ -321,7 +354,8 @@ class GraphedBoundAnimation(GraphedPointsAnimation):
         self.triangles = torch.empty(binding.P, 3, 3, dtype=torch.float32, device=binding.face_idx.device)     # static: rewritten by every frame
 
     def _frame(self, vertices: torch.Tensor) -> dict:
-        return render_points_animated(self._deform(self.binding, vertices, self.faces, out=self.triangles), self.view, self.pc, self.pipe, self.bg)
+        return render_points_animated(self._deform(self.binding, vertices, self.faces, out=self.triangles), self.view, self.pc, self.pipe, self.bg,
+                                      rest_rotation=self.rest)
 
     def _num_gaussians(self) -> int:
         return self.binding.P
@@ -346,7 +380,8 @@ class GraphedFlameAnimation(GraphedAnimation):
             img = anim.render(anim.pack(shape, expression[k], pose[k], neck[k], transl[k]), check=True)
     """
 
-    def __init__(self, gaussians, view, pipeline, background: torch.Tensor, warmup: int = 3):
+    def __init__(self, gaussians, view, pipeline, background: torch.Tensor, warmup: int = 3, rest_rotation=None):
+        _no_flame_local_sh("GraphedFlameAnimation", rest_rotation)
         super().__init__(gaussians, view, pipeline, background, warmup)
         from . import flame as _flame
         from .model import _squeeze_and_enlarge

@@ -254,8 +254,23 @@ def _fused_frame_ok(pc, pipe, override_color) -> bool:
             and _mesh_sizes_ok(pc) and int(pc.active_sh_degree) == 3 and _kernel_opacity_current(pc))
 
 
+def _local_sh_override(pc, viewpoint_camera, xyz, rotation_now, rest_rotation):
+    """The pose-local SH colours of a frame the fused path declined (games_hip.local_sh.local_sh_colors), to be passed as
+    `override_color`: [P,3] float32 at the model's active degree."""
+    from .local_sh import local_sh_colors, model_features, prepared_rest_rotation
+    with torch.no_grad():
+        rest = prepared_rest_rotation(rest_rotation, int(xyz.shape[0]), xyz.device)
+        return local_sh_colors(model_features(pc).detach(), int(pc.active_sh_degree), xyz.detach().float(), viewpoint_camera.camera_center,
+                               rotation_now.detach(), rest.q)
+
+
+def _no_override_with_local_sh(what, override_color):
+    if override_color is not None:
+        raise ValueError(f"{what}: rest_rotation turns the SH colours; it cannot be combined with override_color")
+
+
 def render_mesh_frame(vertices: torch.Tensor, faces: torch.Tensor, viewpoint_camera, pc, pipe, bg_color: torch.Tensor,
-                      scaling_modifier=1.0):
+                      scaling_modifier=1.0, rest_rotation=None):
     """One forward-only frame straight from a (deformed) mesh: vertices [V,3] + faces [F,3] -> image, with the face -> Gaussian
     parameterization computed inside the rasterizer's preprocess thread (no K0 launch, no xyz / scale / rotation tensors; SURVEY.md
     section 7 step 9).  Same image, bit for bit, as `render_animated(None, vertices[faces], ...)`; callers check `_fused_frame_ok`.
@@ -264,7 +279,9 @@ def render_mesh_frame(vertices: torch.Tensor, faces: torch.Tensor, viewpoint_cam
     forward-only frame has no screen-space gradient to receive.  Code that saves or inspects the DEFORMED Gaussians after a frame
     calls `render_animated` with `GMS_ANIMATE_FUSED=0` (or assigns `pc.triangles` and calls `prepare_scaling_rot()`).
     A multi-mesh model (games_hip.model.HipMultiMeshMixin) takes a LIST of per-mesh vertices, in the model's order -- one mesh moved
-    against the others, say; `faces` is then ignored (the model's concatenated faces and splat table are used)."""
+    against the others, say; `faces` is then ignored (the model's concatenated faces and splat table are used).
+    `rest_rotation` ([P,4], games_hip.local_sh.rest_rotation_of): the SH rows are evaluated on the direction taken back into the pose
+    the coefficients were learned in (gms_rasterize_forward_local_sh); None: the frame as ever."""
     H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
     if isinstance(vertices, (list, tuple)):
         with torch.no_grad():
@@ -274,6 +291,16 @@ def render_mesh_frame(vertices: torch.Tensor, faces: torch.Tensor, viewpoint_cam
             raise RuntimeError("render_mesh_frame: the per-mesh vertices do not have the model's vertex counts")
     else:
         _alpha, _scale, spf, splat_face = pc._alpha, getattr(pc, getattr(pc, "_hip_scale_attr", "_scale")), int(pc._alpha.shape[1]), None
+    if rest_rotation is not None:
+        from .local_sh import prepared_rest_rotation
+        rest = prepared_rest_rotation(rest_rotation, int(_scale.numel()), vertices.device)
+        color, radii, invdepth, visible = dgr._C.render_mesh_forward_local_sh(
+            vertices.float(), faces, _alpha, _scale, pc._opacity, ALPHA_MODES[getattr(pc, "alpha_mode", "relu")], spf,
+            dgr._empty(vertices.device) if splat_face is None else splat_face, pc._features_dc, pc._features_rest, bg_color,
+            viewpoint_camera.world_view_transform, viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W,
+            math.tan(viewpoint_camera.FoVx * 0.5), math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing),
+            bool(pipe.debug), rest.q)
+        return {"render": color, "viewspace_points": None, "visibility_filter": visible, "radii": radii, "depth": invdepth}
     color, radii, invdepth, visible = dgr._C.render_mesh_forward(
         vertices.float(), faces, _alpha, _scale, pc._opacity, ALPHA_MODES[getattr(pc, "alpha_mode", "relu")], spf,
         dgr._empty(vertices.device) if splat_face is None else splat_face, pc._features_dc, pc._features_rest, bg_color, viewpoint_camera.world_view_transform,
@@ -283,12 +310,16 @@ def render_mesh_frame(vertices: torch.Tensor, faces: torch.Tensor, viewpoint_cam
 
 
 def render_animated(idxs, triangles, viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0,
-                    override_color=None):
+                    override_color=None, rest_rotation=None):
     """renderer/gaussian_animated_renderer/__init__.py:21-121: the mesh is deformed per frame, centres follow
     `pc.alpha @ triangles` (:61-67) and scale / rotation are re-derived from the deformed triangles (:72-73).
     With the fused op that is one kernel: assigning `pc.triangles` and calling `prepare_scaling_rot()` runs
-    the op on the explicit triangles; its xyz output is `alpha @ triangles`.  `pc` carries games_hip.model.HipMeshMixin."""
+    the op on the explicit triangles; its xyz output is `alpha @ triangles`.  `pc` carries games_hip.model.HipMeshMixin.
+    `rest_rotation`: pose-local SH (games_hip.local_sh) -- inside the fused frame, else as colours computed in torch and passed on
+    as `override_color`."""
     from .mesh_op import identity_faces, triangles_to_gaussians
+    if rest_rotation is not None:
+        _no_override_with_local_sh("render_animated", override_color)
     if _fused_frame_ok(pc, pipe, override_color):
         # forward-only frame (the animated drivers run under no_grad): K0 inside the preprocess thread, explicit triangles as an
         # identity-indexed mesh.  (The cached kernel sigmoid is what the unfused frame would read from get_opacity.)
@@ -297,10 +328,12 @@ def render_animated(idxs, triangles, viewpoint_camera, pc, pipe, bg_color: torch
             raise RuntimeError(f"render_animated: {F_} triangles for a model with {int(pc._alpha.shape[0])} faces")
         pc.triangles = triangles
         return render_mesh_frame(triangles.reshape(3 * F_, 3), identity_faces(triangles.device, F_), viewpoint_camera, pc, pipe, bg_color,
-                                 scaling_modifier)
+                                 scaling_modifier, rest_rotation)
     pc.triangles = triangles
     out = triangles_to_gaussians(triangles, pc._alpha, pc._scale, getattr(pc, "alpha_mode", "relu"), fused_activations=True)
     pc.hip_install_derived(*out[2:6])
+    if rest_rotation is not None:
+        override_color = _local_sh_override(pc, viewpoint_camera, out[1], out[5], rest_rotation)
     return render(viewpoint_camera, _View(pc, out[1]), pipe, bg_color, scaling_modifier, override_color)
 
 
@@ -313,12 +346,23 @@ def _points_frame_ok(pc, pipe, override_color) -> bool:
             and pc._features_rest.is_cuda and 0 <= int(pc.active_sh_degree) <= 3 and _kernel_opacity_current(pc))
 
 
-def render_points_frame(triangles: torch.Tensor, viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, eps=1e-8):
+def render_points_frame(triangles: torch.Tensor, viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, eps=1e-8,
+                        rest_rotation=None):
     """One forward-only frame straight from pseudo-triangles [P,3,3]: the triangle -> Gaussian arithmetic runs inside the rasterizer's
     preprocess thread (no points launch, no per-Gaussian tensors).  Same image, bit for bit, as the points op followed by the
     rasterizer on its outputs; callers check `_points_frame_ok`.  As with `render_mesh_frame`, `pc._scaling` / `pc._rotation` keep the
-    values of the last prepare_scaling_rot() and `viewspace_points` is None."""
+    values of the last prepare_scaling_rot() and `viewspace_points` is None.  `rest_rotation` ([P,4]): pose-local SH, as in
+    `render_mesh_frame`; None: the frame as ever."""
     H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
+    if rest_rotation is not None:
+        from .local_sh import prepared_rest_rotation
+        rest = prepared_rest_rotation(rest_rotation, int(triangles.shape[0]), triangles.device)
+        color, radii, invdepth, visible = dgr._C.render_points_forward_local_sh(
+            triangles, pc._opacity, pc._features_dc, pc._features_rest, bg_color, viewpoint_camera.world_view_transform,
+            viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W, math.tan(viewpoint_camera.FoVx * 0.5),
+            math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing), bool(pipe.debug), int(pc.active_sh_degree),
+            float(eps), float(getattr(pc, "eps_s0", 1e-8)), rest.q)
+        return {"render": color, "viewspace_points": None, "visibility_filter": visible, "radii": radii, "depth": invdepth}
     color, radii, invdepth, visible = dgr._C.render_points_forward(
         triangles, pc._opacity, pc._features_dc, pc._features_rest, bg_color, viewpoint_camera.world_view_transform,
         viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W, math.tan(viewpoint_camera.FoVx * 0.5),
@@ -327,13 +371,20 @@ def render_points_frame(triangles: torch.Tensor, viewpoint_camera, pc, pipe, bg_
     return {"render": color, "viewspace_points": None, "visibility_filter": visible, "radii": radii, "depth": invdepth}
 
 
-def render_points_animated(triangles, viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None):
+def render_points_animated(triangles, viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None,
+                           rest_rotation=None):
     """renderer/gaussian_points_animated_renderer/__init__.py:21-115 with its signature and return dict: centres are `triangles[:, 0]`
     (:61), scale / rotation come from `pc.prepare_scaling_rot(triangles)` (:66).  Forward-only frames the fused path supports go
     pseudo-triangles -> image in the rasterizer's own launches (`render_points_frame`); everything else runs the model's
-    prepare_scaling_rot (the points op on a HipPointsMixin model, differentiable to the triangles) and then `render()`."""
+    prepare_scaling_rot (the points op on a HipPointsMixin model, differentiable to the triangles) and then `render()`.
+    `rest_rotation`: pose-local SH (games_hip.local_sh) -- inside the fused frame, else as colours computed in torch and passed on as
+    `override_color`."""
+    if rest_rotation is not None:
+        _no_override_with_local_sh("render_points_animated", override_color)
     if _points_frame_ok(pc, pipe, override_color):
-        return render_points_frame(triangles, viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
+        return render_points_frame(triangles, viewpoint_camera, pc, pipe, bg_color, scaling_modifier, rest_rotation=rest_rotation)
     pc.prepare_scaling_rot(triangles)
     centre = pc._hip_points_centre(triangles) if hasattr(pc, "_hip_points_centre") else triangles[:, 0]
+    if rest_rotation is not None:
+        override_color = _local_sh_override(pc, viewpoint_camera, centre, pc.get_rotation, rest_rotation)
     return render(viewpoint_camera, _View(pc, centre), pipe, bg_color, scaling_modifier, override_color)

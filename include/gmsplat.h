@@ -391,6 +391,20 @@ int64_t gms_rasterize_forward_free(const GmsRasterForwardArgs *args, const GmsFr
 int32_t gms_rasterize_backward_free(const GmsRasterBackwardArgs *args, const GmsFreeArgs *free_args, float *dL_d_scaling,
                                     float *dL_d_rotation, float *dL_d_opacity, void *stream);
 
+/* gms_rasterize_forward on a forward-only frame straight from a mesh or from pseudo-triangles (`args->mesh` or `args->points` set),
+ * with spherical harmonics that turn with the face / triangle (additive to ABI 10).  The SH coefficients of Gaussian i were learned in
+ * the pose whose rotation is rest_rotation[i] = q_0 (unit, (w, x, y, z)); the frame derives the unit quaternion q_t, and the SH row is
+ * evaluated on
+ *     n_local = R(q_0) R(q_t)^T n,      n = normalize(xyz_t - campos),  R(q): the reference's build_rotation
+ * instead of n.  Where q_t and q_0 give the same rotation the frame is gms_rasterize_forward's up to rounding; the sign of either
+ * quaternion does not matter; at active degree 0 the image is the same bit for bit.  Projection, covariance, opacity, depth and radii
+ * are gms_rasterize_forward's own.  `rest_rotation`: device, [P,4] float32, 16-byte aligned, read once per Gaussian by the preprocess
+ * thread.  Returns GMS_ERR_INVALID_ARGUMENT (gms_last_error names the cause) when rest_rotation is NULL or misaligned, when neither
+ * `mesh` nor `points` is set, or when any `mesh_out_*` is set (a training frame: its backward would read a direction derivative this
+ * frame does not store).  Everything else -- return value, capacity hint, count ticket, no_host_wait (capturable) -- as
+ * gms_rasterize_forward; the launches are accounted under GMS_K_PREPROCESS_FWD. */
+int64_t gms_rasterize_forward_local_sh(const GmsRasterForwardArgs *args, const float *rest_rotation, void *stream);
+
 /* ---- exact 3-NN mean squared distance ---------------------------------
  * Replaces the un-vendored `simple_knn._C.distCUDA2(points)` (.gitmodules:1-3) called at
  * scene/gaussian_model.py:134 and games/flat_splatting/scene/flat_gaussian_model.py:47 to size the initial
