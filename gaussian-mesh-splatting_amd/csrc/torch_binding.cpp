@@ -1368,6 +1368,92 @@ Tensor bind_apply(const Tensor &face_idx, const Tensor &alpha, const Tensor &gui
     return out;
 }
 
+// ---------------------------------------------------------------------------------------------- guide mesh estimated from Gaussians
+// (scripts/create_dummy_mesh.py's step; csrc/guide_mesh.hip).  Shapes and values are checked by games_hip/guide_mesh.py, which names
+// the caller's arguments; here only what keeps the kernels inside their buffers.
+GmsGridSpec grid_spec(const std::vector<int64_t> &n, const std::vector<double> &origin, double voxel, const char *what)
+{
+    TORCH_CHECK(n.size() == 3 && origin.size() == 3, what, ": n and origin hold three values each");
+    GmsGridSpec g;
+    for (int k = 0; k < 3; k++) {
+        TORCH_CHECK(n[k] >= 3 && n[k] <= INT32_MAX, what, ": n[", k, "] = ", n[k], " outside [3, 2^31)");
+        g.n[k] = (int32_t)n[k]; g.origin[k] = (float)origin[k];
+    }
+    TORCH_CHECK((double)n[0] * (double)n[1] * (double)n[2] < 2147483648.0, what, ": a grid of ", n[0], " x ", n[1], " x ", n[2], " nodes is 2^31 nodes or more");
+    g.voxel = (float)voxel;
+    return g;
+}
+
+struct FieldIn { Tensor means, scales, rotations; int64_t P; };
+FieldIn field_inputs(const Tensor &means_, const Tensor &scales_, const Tensor &rotations_, const char *what)
+{
+    require_gpu(means_); require_gpu(scales_); require_gpu(rotations_);
+    TORCH_CHECK(means_.dim() == 2 && means_.size(1) == 3, what, ": means must have dimensions (P, 3)");
+    const int64_t P = means_.size(0);
+    TORCH_CHECK(scales_.dim() == 2 && scales_.size(0) == P && scales_.size(1) == 3, what, ": scales must have dimensions (P, 3)");
+    TORCH_CHECK(rotations_.dim() == 2 && rotations_.size(0) == P && rotations_.size(1) == 4, what, ": rotations must have dimensions (P, 4)");
+    TORCH_CHECK(P == 0 || (scales_.device() == means_.device() && rotations_.device() == means_.device()), what, ": the Gaussians' tensors live on different devices");
+    return {f32c(means_.detach()), f32c(scales_.detach()), f32c(rotations_.detach()), P};
+}
+
+// -> [min x, min y, min z, max x, max y, max z] of the Gaussians' 3-sigma boxes (one host wait)
+std::vector<double> density_bounds(const Tensor &means_, const Tensor &scales_, const Tensor &rotations_)
+{
+    FieldIn in = field_inputs(means_, scales_, rotations_, "density_bounds");
+    TORCH_CHECK(in.P > 0 && in.means.is_cuda(), "density_bounds: no Gaussians");
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(in.means.device());
+    Tensor work = torch::empty({256}, torch::TensorOptions().dtype(torch::kUInt8).device(in.means.device()));
+    float b[6];
+    check_rc(gms_density_bounds(in.P, cf(in.means), cf(in.scales), cf(in.rotations), b, work.data_ptr(), 256, stream_of(in.means)), "gms_density_bounds");
+    return {b[0], b[1], b[2], b[3], b[4], b[5]};
+}
+
+// -> values float32 [n2, n1, n0]; launches only.  `opacities_`: [P], or empty: all 1
+Tensor density_grid(const std::vector<int64_t> &n, const std::vector<double> &origin, double voxel, const Tensor &means_, const Tensor &scales_,
+                    const Tensor &rotations_, const Tensor &opacities_, double min_sigma_voxels)
+{
+    const GmsGridSpec g = grid_spec(n, origin, voxel, "density_grid");
+    FieldIn in = field_inputs(means_, scales_, rotations_, "density_grid");
+    require_gpu(opacities_);
+    TORCH_CHECK(in.P > 0 && in.means.is_cuda(), "density_grid: no Gaussians (the field of none is all zero: the caller makes it)");
+    const c10::Device device = in.means.device();
+    const bool has_op = opacities_.defined() && opacities_.numel() > 0;
+    TORCH_CHECK(!has_op || (opacities_.numel() == in.P && opacities_.device() == device), "density_grid: opacities must hold P values on the means' device");
+    Tensor op = f32c(opacities_.detach());
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(device);
+    const size_t bytes = gms_density_grid_workspace_bytes(&g, in.P);
+    TORCH_CHECK(bytes > 0, "density_grid: ", gms_last_error());
+    Tensor work = torch::empty({(int64_t)bytes}, torch::TensorOptions().dtype(torch::kUInt8).device(device));
+    Tensor values = torch::empty({n[2], n[1], n[0]}, torch::TensorOptions().dtype(torch::kFloat).device(device));
+    check_rc(gms_density_grid(&g, in.P, cf(in.means), cf(in.scales), cf(in.rotations), has_op ? cf(op) : nullptr, (float)min_sigma_voxels, mf(values),
+                              work.data_ptr(), bytes, stream_of(device)), "gms_density_grid");
+    return values;
+}
+
+// values float32 [n2, n1, n0] -> (vertices [V,3], faces int32 [F,3]); one host wait (the two counts)
+std::tuple<Tensor, Tensor> surface_nets(const std::vector<int64_t> &n, const std::vector<double> &origin, double voxel, const Tensor &values_, double level)
+{
+    const GmsGridSpec g = grid_spec(n, origin, voxel, "surface_nets");
+    require_gpu(values_);
+    TORCH_CHECK(values_.is_cuda() && values_.dim() == 3 && values_.size(0) == n[2] && values_.size(1) == n[1] && values_.size(2) == n[0],
+                "surface_nets: values must be a device tensor of dimensions (n[2], n[1], n[0])");
+    Tensor values = f32c(values_.detach());
+    const auto dev = values.device();
+    c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
+    const int64_t N = n[0] * n[1] * n[2];
+    Tensor flags = torch::empty({4 * N}, torch::TensorOptions().dtype(torch::kUInt8).device(dev));
+    check_rc(gms_surface_nets_count(&g, cf(values), (float)level, flags.data_ptr<uint8_t>(), stream_of(dev)), "gms_surface_nets_count");
+    Tensor scan = at::cumsum(flags, 0, torch::kInt);
+    Tensor counts = torch::stack({scan[N - 1], scan[4 * N - 1]}).cpu();
+    const int64_t V = counts[0].item<int32_t>(), F = 2 * ((int64_t)counts[1].item<int32_t>() - V);
+    TORCH_CHECK(V >= 0 && F >= 0 && F <= INT32_MAX, "surface_nets: more than 2^31 - 1 vertices and quads");
+    Tensor vertices = torch::empty({V, 3}, torch::TensorOptions().dtype(torch::kFloat).device(dev));
+    Tensor faces = torch::empty({F, 3}, torch::TensorOptions().dtype(torch::kInt).device(dev));
+    check_rc(gms_surface_nets_emit(&g, cf(values), (float)level, flags.data_ptr<uint8_t>(), scan.data_ptr<int32_t>(), (int32_t)V, (int32_t)F,
+                                   V ? mf(vertices) : nullptr, F ? faces.data_ptr<int32_t>() : nullptr, stream_of(dev)), "gms_surface_nets_emit");
+    return {vertices, faces};
+}
+
 // ---------------------------------------------------------------------------------------------- FLAME layer (csrc/flame.hip)
 // tables = the packed model of games_hip.flame.FlameData.to(device): [v_template [V,3], shapedirs [L,V*3], posedirs [(J-1)*9,V*3],
 // lbs_weights [V,J], joints_template [J,3], joints_shapedirs [L,J*3]].  The joint rotations come as tensors of 3 n floats each with the
@@ -1699,6 +1785,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("bind_pseudomesh", &bind_pseudomesh, "bind pseudo-triangles [P,3,3] to the nearest faces of a guide mesh: (face_idx int32 [P], alpha [P,3,3], n_degenerate)", nogil());
     m.def("bind_apply", &bind_apply, "pseudo-triangles [P,3,3] of a binding on (edited) guide vertices; launches only", py::arg("face_idx"), py::arg("alpha"),
           py::arg("guide_vertices"), py::arg("guide_faces"), py::arg("out") = py::none(), nogil());
+    m.def("density_bounds", &density_bounds, "box of the Gaussians' 3-sigma boxes: [min xyz, max xyz]; one host wait", nogil());
+    m.def("density_grid", &density_grid, "density field of Gaussians on a regular grid: values float32 [n2,n1,n0]; launches only", py::arg("n"), py::arg("origin"),
+          py::arg("voxel"), py::arg("means"), py::arg("scales"), py::arg("rotations"), py::arg("opacities"), py::arg("min_sigma_voxels"), nogil());
+    m.def("surface_nets", &surface_nets, "iso-surface of a grid by surface nets: (vertices [V,3], faces int32 [F,3]); one host wait", nogil());
     m.def("densify_stats", &densify_stats, "per-iteration densification statistics, in place on (max_radii2D, xyz_gradient_accum, denom); one launch", nogil());
     m.def("densify_plan", &densify_plan, "clone / split / prune decisions as a source map: (src int32 [P'], kind int32 [P'], counts)", nogil());
     m.def("densify_apply", &densify_apply, "gather the six parameters and their Adam moments through a plan: (params, exp_avg, exp_avg_sq)", nogil());

@@ -200,6 +200,11 @@ class DensifyTensor(C.Structure):
     ]
 
 
+class GridSpec(C.Structure):
+    """GmsGridSpec: n[0] x n[1] x n[2] nodes, node (i, j, k) at origin + (i, j, k) * voxel, x fastest in memory."""
+    _fields_ = [("n", C.c_int32 * 3), ("origin", C.c_float * 3), ("voxel", C.c_float)]
+
+
 def flame_saved_floats(V: int) -> int:
     """GMS_FLAME_SAVED_FLOATS."""
     return 3 * int(V) + 24 * FLAME_MAX_JOINTS
@@ -217,6 +222,7 @@ EXPORTS = (
     "gms_set_upstream_scale_mod_grad", "gms_get_upstream_scale_mod_grad", "gms_profile_event_overhead_us",
     "gms_points_prepare_vertices", "gms_points_to_gaussians_forward", "gms_points_to_gaussians_backward",
     "gms_bind_workspace_bytes", "gms_bind_pseudomesh", "gms_bind_apply",
+    "gms_density_grid_workspace_bytes", "gms_density_bounds", "gms_density_grid", "gms_surface_nets_count", "gms_surface_nets_emit",
     "gms_flame_workspace_bytes", "gms_flame_forward", "gms_flame_backward",
     "gms_densify_stats", "gms_densify_plan_workspace_bytes", "gms_densify_plan", "gms_densify_apply",
     "gms_image_metrics_workspace_bytes", "gms_image_metrics",
@@ -295,6 +301,18 @@ def load():
                                             C.POINTER(C.c_int32), C.c_void_p, C.c_size_t, C.c_void_p]
         lib.gms_bind_apply.restype = C.c_int32
         lib.gms_bind_apply.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.gms_density_grid_workspace_bytes.restype = C.c_size_t
+        lib.gms_density_grid_workspace_bytes.argtypes = [C.POINTER(GridSpec), C.c_int64]
+        lib.gms_density_bounds.restype = C.c_int32
+        lib.gms_density_bounds.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.gms_density_grid.restype = C.c_int32
+        lib.gms_density_grid.argtypes = [C.POINTER(GridSpec), C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
+                                         C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.gms_surface_nets_count.restype = C.c_int32
+        lib.gms_surface_nets_count.argtypes = [C.POINTER(GridSpec), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        lib.gms_surface_nets_emit.restype = C.c_int32
+        lib.gms_surface_nets_emit.argtypes = [C.POINTER(GridSpec), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
         lib.gms_flame_workspace_bytes.restype = C.c_size_t
         lib.gms_flame_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         lib.gms_flame_forward.restype = C.c_int32

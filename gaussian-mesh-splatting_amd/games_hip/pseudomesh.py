@@ -6,6 +6,7 @@ the frame of the same face of an edited guide -- a host KDTree and three torch.l
 binding is made once and a pose is one kernel:
 
     save_pseudomesh_info(gaussians, out_dir)                          # triangles.pt + the OBJ soup (scripts/save_pseudomesh.py:62-90)
+    guide = guide_mesh.create_dummy_mesh(out_dir, save_dir)             # the mesh to edit (scripts/create_dummy_mesh.py; guide_mesh.py)
     binding = bind_pseudomesh(triangles, guide.vertices, guide.faces)   # once: face_idx [P] + alpha [P,3,3]
     triangles_k = deform_pseudomesh(binding, edited_vertices_k, faces)  # per pose
     render_points_animated(triangles_k, view, gaussians, pipe, bg)      # or animate.render_points_mesh_animated / GraphedBoundAnimation

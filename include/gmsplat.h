@@ -438,6 +438,54 @@ int32_t gms_bind_apply(int64_t P, const int32_t *face_idx /* [P] */, const float
                        const float *guide_vertices /* [V,3] */, int32_t F, const int32_t *guide_faces /* [F,3] */,
                        float *triangles_out /* [P,3,3] */, void *stream);
 
+/* ---- a guide mesh estimated from Gaussians (scripts/create_dummy_mesh.py's step; csrc/guide_mesh.hip; additive to ABI 10) ----
+ * The reference makes the editable mesh with an alpha shape of the pseudo-triangles' corners; here it is the iso-surface of a density
+ * field of the Gaussians.  The kernels of these entry points have no GMS_K_* profile id: GMS_K_COUNT stays 23.
+ *
+ * GmsGridSpec: a regular grid of n[0] x n[1] x n[2] nodes, node (i, j, k) at origin + (i, j, k) * voxel, x fastest in memory
+ * (array index (k * n[1] + j) * n[0] + i).  Every n[k] in [3, 2^24] and n[0] n[1] n[2] < 2^31, else GMS_ERR_INVALID_ARGUMENT with the
+ * sizes in gms_last_error.  The outermost layer of nodes is outside by definition, which closes every surface.
+ *
+ * gms_density_bounds: bounds_out (HOST, 6 floats: min xyz, max xyz) = the box of the boxes mu_k +- 3 sqrt(sum_j (R_kj s_j)^2) of
+ * all Gaussians with finite values, the scales as given; with none, values that are not a box (min > max or NaN: the caller
+ * checks).  One stream synchronisation.
+ * `workspace`: at least 256 bytes of device scratch.
+ *
+ * gms_density_grid: values_out[node] = sum over the Gaussians of
+ *     w = o max(exp(-d2 / 2) - e0, 0) / (1 - e0),   d2 = sum_k (q_k / sigma_k)^2,   q = R^T (x - mu),
+ *     sigma_k = max(s_k, min_sigma_voxels * voxel),   e0 = exp(-9 / 2)
+ * (means [P,3], activated scales [P,3], unit quaternions [P,4] (w, x, y, z), R the reference's build_rotation, activated opacities
+ * [P] or NULL: all 1), and 0 on the outermost layer.  Each w is rounded to the nearest multiple of 2^-32 and summed with 64-bit
+ * integer atomics, the float32 value is one conversion of that sum: the result is the same bit for bit from call to call and for
+ * any order of the Gaussians.  Gaussians with non-finite values, a NaN weight or a negative opacity add nothing.  Launches only:
+ * no allocation, no host wait.  `workspace`: gms_density_grid_workspace_bytes(grid, P) bytes (0: the grid is invalid).
+ *
+ * gms_surface_nets_count: flags_out [4 N] uint8 for N = n[0] n[1] n[2]: [N cells by their lowest node | x edges | y edges | z edges
+ * by their lower node]; a node is inside iff it is off the outermost layer and values >= level; a cell is flagged iff its eight
+ * corners disagree, an edge iff its ends do.  The caller scans the flags (inclusive, int32, in this order): V = scan[N - 1] and
+ * F = 2 (scan[4 N - 1] - V).
+ * gms_surface_nets_emit: vertices_out [V,3] in cell order: the mean of the crossing points t = (level - fa) / (fb - fa), clamped to
+ * [1/32, 31/32], of the cell's sign-changing edges, in world coordinates; faces_out [F,3] int32 in (edge axis, node) order: the
+ * quad of the four cells around a flagged edge, its normal pointing from the inside end to the outside end, split along the
+ * shorter diagonal (a tie: the diagonal through the lowest cell).  All float32 without contraction.  V = F = 0 succeeds and
+ * writes nothing.  Both launch only. */
+typedef struct GmsGridSpec {
+    int32_t n[3];
+    float origin[3];
+    float voxel;
+} GmsGridSpec;
+size_t gms_density_grid_workspace_bytes(const GmsGridSpec *grid, int64_t P);
+int32_t gms_density_bounds(int64_t P, const float *means /* [P,3] */, const float *scales /* [P,3] */, const float *rotations /* [P,4] */,
+                           float *bounds_out /* HOST [6] */, void *workspace, size_t workspace_bytes, void *stream);
+int32_t gms_density_grid(const GmsGridSpec *grid, int64_t P, const float *means /* [P,3] */, const float *scales /* [P,3] */,
+                         const float *rotations /* [P,4] */, const float *opacities /* [P] or NULL */, float min_sigma_voxels,
+                         float *values_out /* [n2,n1,n0] */, void *workspace, size_t workspace_bytes, void *stream);
+int32_t gms_surface_nets_count(const GmsGridSpec *grid, const float *values /* [n2,n1,n0] */, float level, uint8_t *flags_out /* [4 N] */,
+                               void *stream);
+int32_t gms_surface_nets_emit(const GmsGridSpec *grid, const float *values, float level, const uint8_t *flags /* [4 N] */,
+                              const int32_t *scan /* [4 N] */, int32_t V, int32_t F, float *vertices_out /* [V,3] */,
+                              int32_t *faces_out /* [F,3] */, void *stream);
+
 /* ---- fused L1 + SSIM photometric loss ---------------------------------
  * Replaces train.py:106-107 built on utils/loss_utils.py:17-18 (l1_loss) and :33-63 (ssim: 11x11 Gaussian window,
  * sigma 1.5, zero padding, C1=0.01^2, C2=0.03^2, mean over every pixel of every plane):
