@@ -45,6 +45,12 @@ inline Tensor f32c(const Tensor &t)
     return r.is_contiguous() ? r : r.contiguous();
 }
 
+// an optional tensor among an autograd node's saved tensors: kept as an empty placeholder, read back as undefined
+inline Tensor keep_opt(const Tensor &t, const torch::TensorOptions &o) { return (t.defined() && t.numel()) ? t : torch::empty({0}, o); }
+inline Tensor kept_opt(const Tensor &t) { return t.numel() ? t : Tensor(); }
+// an optional index table (splat_face, face_splat_offset) as contiguous int32; absent or empty: undefined
+inline Tensor i32c(const Tensor &t) { return (t.defined() && t.numel()) ? t.to(torch::kInt).contiguous() : Tensor(); }
+
 inline void require_gpu(const Tensor &t)
 {
     TORCH_CHECK(!t.defined() || t.numel() == 0 || t.is_cuda(),
@@ -99,45 +105,34 @@ static int64_t quantize_capacity(int64_t x)
 
 struct LastCall { int64_t num_rendered = 0, num_units = 0, hint = 0, P = 0; int W = 0, H = 0; Tensor radii, image, binning, geom; } g_last;
 // which way the mesh backward of the most recent render_mesh backward went (last_stats()["mesh_backward_route"])
-enum MeshBwdRoute { MESH_BWD_NONE = 0, MESH_BWD_TAIL4, MESH_BWD_TAIL_RUNS, MESH_BWD_LAUNCH };
-static std::atomic<int> g_mesh_bwd_route{MESH_BWD_NONE};
+static std::atomic<const char *> g_mesh_bwd_route{"none"};
 std::atomic<bool> g_keep_buffers{false};
+
+// A process-wide switch that starts from an environment variable: unset, `dflt`; set, on unless it reads as 0.  set() overrides both.
+struct EnvToggle {
+    const char *name; bool dflt; std::atomic<int> v{-1};
+    bool get()
+    {
+        if (v.load() < 0) { const char *e = getenv(name); int expected = -1; v.compare_exchange_strong(expected, (e ? atoi(e) != 0 : dflt) ? 1 : 0); }
+        return v.load() != 0;
+    }
+    void set(bool on) { v.store(on ? 1 : 0); }
+};
 
 struct Forward {
     int64_t num_rendered = 0, num_units = 0, capacity = 0;
     int64_t ticket[2] = {0, 0}, launched_units = 0;      // deferred read-back (set_deferred_counts): the counts are redeemed at the start of the backward
-    Tensor color, radii, invdepth, geom, binning, image;
+    Tensor color, radii, invdepth, geom, binning, image, visible;      // visible: radii > 0 out of the preprocess kernel (`visibility_filter`); may be undefined
 };
 // Deferred read-back of the instance count (gmsplat.h, count_ticket_out): opt-in, because an overflowed frame can
 // only be REPORTED at the start of its backward (the loss has been computed on an incomplete image by then): the backward raises
 // "GMS_DEFERRED_OVERFLOW" and the training loop redoes the step (games_hip/train.py, bench.py); the reference's own loop cannot.
-static std::atomic<int> g_defer_counts{-1};
-bool deferred_counts()
-{
-    int v = g_defer_counts.load();
-    if (v < 0) { const char *e = getenv("GMS_DEFER_COUNTS"); int expected = -1; g_defer_counts.compare_exchange_strong(expected, (e && atoi(e) != 0) ? 1 : 0); v = g_defer_counts.load(); }
-    return v != 0;
-}
-void set_deferred_counts(bool on) { g_defer_counts.store(on ? 1 : 0); }
+EnvToggle g_defer_counts{"GMS_DEFER_COUNTS", false};
 // the mesh backward inside preprocess_bwd for frames rendered straight from the mesh (GmsRasterBackwardArgs.mesh, ABI 8); on by default
-static std::atomic<int> g_fused_mesh_bwd{-1};
-bool fused_mesh_backward()
-{
-    int v = g_fused_mesh_bwd.load();
-    if (v < 0) { const char *e = getenv("GMS_TRAIN_FUSED_BWD"); int expected = -1; g_fused_mesh_bwd.compare_exchange_strong(expected, (e && atoi(e) == 0) ? 0 : 1); v = g_fused_mesh_bwd.load(); }
-    return v != 0;
-}
-void set_fused_mesh_backward(bool on) { g_fused_mesh_bwd.store(on ? 1 : 0); }
+EnvToggle g_fused_mesh_bwd{"GMS_TRAIN_FUSED_BWD", true};
 // ... for runs of any length (more than four splats per face, CSR tables: preprocess_bwd_kernel<true, MeshRuns>).  GMS_TRAIN_FUSED_BWD_RUNS=0 /
 // set_fused_mesh_backward_runs(False) keeps the mesh_bwd launch for those shapes and leaves 1-4 splats per face as they are.
-static std::atomic<int> g_fused_mesh_bwd_runs{-1};
-bool fused_mesh_backward_runs()
-{
-    int v = g_fused_mesh_bwd_runs.load();
-    if (v < 0) { const char *e = getenv("GMS_TRAIN_FUSED_BWD_RUNS"); int expected = -1; g_fused_mesh_bwd_runs.compare_exchange_strong(expected, (e && atoi(e) == 0) ? 0 : 1); v = g_fused_mesh_bwd_runs.load(); }
-    return v != 0;
-}
-void set_fused_mesh_backward_runs(bool on) { g_fused_mesh_bwd_runs.store(on ? 1 : 0); }
+EnvToggle g_fused_mesh_bwd_runs{"GMS_TRAIN_FUSED_BWD_RUNS", true};
 // what a frame rendered straight from a mesh stores for its backward (GmsRasterForwardArgs.mesh_out_*, ABI 6)
 struct MeshOut { Tensor xyz, scaling_act, rotation_unit, opacity_act; };
 
@@ -150,7 +145,11 @@ FrameSettings frame_settings(c10::Device dev, const Tensor &bg, const Tensor &vi
     return {f32c(bg.to(dev)), f32c(view.to(dev)), f32c(proj.to(dev)), f32c(campos.to(dev)), H, W, tanx, tany, mod, D, prefiltered, aa, debug};
 }
 // Per-Gaussian inputs as contiguous float32.  A frame straight from a mesh or pseudo-triangles passes only the SH tensors.
-struct Gaussians { Tensor sh, sh_rest, means3D, colors, opac, scales, rots, cov; };
+struct Gaussians {
+    Tensor sh, sh_rest, means3D, colors, opac, scales, rots, cov;
+    std::vector<Tensor> pack() const { return {sh, sh_rest, means3D, colors, opac, scales, rots, cov}; }      // (the order in which RasterizeFn saves them)
+    static Gaussians unpack(const variable_list &saved) { auto t = saved.begin(); return {*t++, *t++, *t++, *t++, *t++, *t++, *t++, *t++}; }
+};
 Gaussians tensor_gaussians(const Tensor &means3D, const Tensor &sh, const Tensor &sh_rest, const Tensor &colors, const Tensor &opac,
                            const Tensor &scales, const Tensor &rots, const Tensor &cov)
 {
@@ -159,22 +158,59 @@ Gaussians tensor_gaussians(const Tensor &means3D, const Tensor &sh, const Tensor
     return {f32c(sh), f32c(sh_rest), f32c(means3D), f32c(colors), f32c(opac), f32c(scales), f32c(rots), f32c(cov)};
 }
 
-// `mesh` / `points`: the forward-only frame straight from a mesh or pseudo-triangles (gmsplat.h); `g` then holds only the SH tensors.
-// `free_args`: the frame straight from a free model's raw parameters (gms_rasterize_forward_free); `g` holds the SH tensors and means3D
-// `rest_rotation`: a mesh / points frame with pose-local SH (gms_rasterize_forward_local_sh): [P,4] unit quaternions the caller keeps alive
-Forward forward_core(const FrameSettings &s, int64_t P, c10::Device dev, const Gaussians &g, const Tensor &visible, bool use_hint,
-                     const GmsMeshArgs *mesh = nullptr, const MeshOut *mesh_out = nullptr, bool may_defer = false, const GmsPointsArgs *points = nullptr,
-                     const GmsFreeArgs *free_args = nullptr, const float *rest_rotation = nullptr)
+// Where a frame's Gaussians come from, by named constructor; what a source points at is the caller's and outlives the forward call.
+//   tensors(visible)      per-Gaussian tensors: `g` of forward_core holds them all; `visible`: the caller's [P] bool buffer for radii > 0, or undefined
+//   mesh(m, rest)         forward-only, from a mesh (GmsRasterForwardArgs.mesh): `g` holds only the SH tensors
+//   mesh_training(m, out) ... and `out` receives what the frame stores for its backward
+//   points(p, rest)       forward-only, from pseudo-triangles (GmsRasterForwardArgs.points): `g` holds only the SH tensors
+//   free(a)               from a free model's raw parameters (gms_rasterize_forward_free): `g` holds the SH tensors and means3D
+// `rest`: [P,4] unit quaternions for pose-local SH (gms_rasterize_forward_local_sh); nullptr: the plain frame.  No other combination exists.
+struct FrameSource {
+    const GmsMeshArgs *mesh_ = nullptr; const MeshOut *mesh_out = nullptr; const GmsPointsArgs *points_ = nullptr; const GmsFreeArgs *free_ = nullptr;
+    const float *rest_rotation = nullptr;
+    Tensor visible_out;
+    static FrameSource tensors(const Tensor &visible = Tensor()) { return {nullptr, nullptr, nullptr, nullptr, nullptr, visible}; }
+    static FrameSource mesh(const GmsMeshArgs &m, const float *rest = nullptr) { return {&m, nullptr, nullptr, nullptr, rest}; }
+    static FrameSource mesh_training(const GmsMeshArgs &m, const MeshOut &out) { return {&m, &out}; }
+    static FrameSource points(const GmsPointsArgs &p, const float *rest = nullptr) { return {nullptr, nullptr, &p, nullptr, rest}; }
+    static FrameSource free(const GmsFreeArgs &a) { return {nullptr, nullptr, nullptr, &a}; }
+    // points `a` at the source and runs the C entry point of its kind; `entry`: that entry's name, for check_rc
+    int64_t run(GmsRasterForwardArgs &a, void *stream, const char *&entry) const
+    {
+        a.mesh = mesh_; a.points = points_;
+        if (mesh_out) {
+            a.mesh_out_xyz = mf(mesh_out->xyz); a.mesh_out_scaling_act = mf(mesh_out->scaling_act);
+            a.mesh_out_rotation_unit = mf(mesh_out->rotation_unit); a.mesh_out_opacity_act = mf(mesh_out->opacity_act);
+        }
+        if (rest_rotation) { entry = "gms_rasterize_forward_local_sh"; return gms_rasterize_forward_local_sh(&a, rest_rotation, stream); }
+        if (free_) { entry = "gms_rasterize_forward_free"; return gms_rasterize_forward_free(&a, free_, stream); }
+        entry = "gms_rasterize_forward"; return gms_rasterize_forward(&a, stream);
+    }
+};
+// `use_hint`: size the binning buffer by the capacity hint of this shape; `may_defer`: a backward follows, which can redeem deferred counts
+struct ForwardOptions { bool use_hint = false, may_defer = false; };
+
+// What GmsRasterForwardArgs and GmsRasterBackwardArgs share: the sizes, the camera and the per-Gaussian inputs.  -> whether `g` has SH
+template <class Args>
+bool frame_args(Args &a, const FrameSettings &s, const Gaussians &g, int64_t P)
+{
+    const bool has_sh = g.sh.defined() && g.sh.numel() > 0, split = g.sh_rest.defined() && g.sh_rest.numel() > 0;
+    a.P = (int32_t)P; a.D = (int32_t)s.D; a.M = (int32_t)(split ? g.sh.size(1) + g.sh_rest.size(1) : has_sh ? g.sh.size(1) : 0);
+    a.width = (int32_t)s.W; a.height = (int32_t)s.H;
+    a.background = cf(s.bg); a.means3D = cf(g.means3D); a.shs = cf(g.sh); a.shs_rest = split ? cf(g.sh_rest) : nullptr;
+    a.colors_precomp = cf(g.colors); a.opacities = cf(g.opac); a.scales = cf(g.scales); a.rotations = cf(g.rots); a.cov3D_precomp = cf(g.cov);
+    a.viewmatrix = cf(s.view); a.projmatrix = cf(s.proj); a.campos = cf(s.campos);
+    a.scale_modifier = (float)s.mod; a.tan_fovx = (float)s.tanx; a.tan_fovy = (float)s.tany; a.antialiasing = s.aa; a.debug = s.debug;
+    return has_sh;
+}
+
+Forward forward_core(const FrameSettings &s, int64_t P, c10::Device dev, const Gaussians &g, const FrameSource &src, ForwardOptions opt)
 {
     c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
-    const bool has_sh = g.sh.defined() && g.sh.numel() > 0;
-    if (has_sh) TORCH_CHECK(g.sh.dim() == 3 && g.sh.size(0) == P && g.sh.size(2) == 3, "sh must have dimensions (num_points, num_coeffs, 3)");
-    int64_t M = has_sh ? g.sh.size(1) : 0;
-    const bool split = g.sh_rest.defined() && g.sh_rest.numel() > 0;
-    if (split) M = g.sh.size(1) + g.sh_rest.size(1);
-
+    if (g.sh.defined() && g.sh.numel() > 0) TORCH_CHECK(g.sh.dim() == 3 && g.sh.size(0) == P && g.sh.size(2) == 3, "sh must have dimensions (num_points, num_coeffs, 3)");
     auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
     Forward f;
+    f.visible = (src.mesh_ || src.points_ || src.free_) ? torch::empty({P}, fopt.dtype(torch::kBool)) : src.visible_out;
     f.color = torch::empty({3, s.H, s.W}, fopt);
     f.invdepth = torch::empty({1, s.H, s.W}, fopt);
     f.radii = torch::empty({P}, fopt.dtype(torch::kInt));
@@ -183,7 +219,7 @@ Forward forward_core(const FrameSettings &s, int64_t P, c10::Device dev, const G
     const auto key = std::make_tuple((int)dev.index(), (int)s.W, (int)s.H, P);
     // deterministic mode (gmsplat.h): no capacity hint -- the segment length and the choice of compositing kernels then depend on the
     // frame alone (the exact instance count), not on what earlier frames of this shape looked like: run 1 == run 2 bit for bit
-    if (use_hint && !gms_get_deterministic()) {
+    if (opt.use_hint && !gms_get_deterministic()) {
         std::lock_guard<std::mutex> lk(g_mu);
         auto it = g_capacity.find(key);
         if (it != g_capacity.end()) hint = quantize_capacity(it->second + it->second / 4 + 4096);
@@ -199,37 +235,25 @@ Forward forward_core(const FrameSettings &s, int64_t P, c10::Device dev, const G
     Slot geom{Tensor(), dev, false}, binning{Tensor(), dev, false}, image{Tensor(), dev, false};
     int64_t num_units = 0;
     GmsRasterForwardArgs a{};
-    a.P = (int32_t)P; a.D = (int32_t)s.D; a.M = (int32_t)M; a.width = (int32_t)s.W; a.height = (int32_t)s.H;
-    a.background = cf(s.bg); a.means3D = cf(g.means3D); a.shs = cf(g.sh); a.shs_rest = split ? cf(g.sh_rest) : nullptr;
-    a.colors_precomp = cf(g.colors); a.opacities = cf(g.opac); a.scales = cf(g.scales); a.rotations = cf(g.rots);
-    a.cov3D_precomp = cf(g.cov); a.viewmatrix = cf(s.view); a.projmatrix = cf(s.proj); a.campos = cf(s.campos);
-    a.scale_modifier = (float)s.mod; a.tan_fovx = (float)s.tanx; a.tan_fovy = (float)s.tany;
-    a.prefiltered = s.prefiltered; a.antialiasing = s.aa; a.debug = s.debug;
+    frame_args(a, s, g, P);
+    a.prefiltered = s.prefiltered;
     a.out_color = mf(f.color); a.out_invdepth = mf(f.invdepth); a.radii = P ? f.radii.data_ptr<int32_t>() : nullptr;
     a.geom_alloc = alloc_cb; a.geom_ctx = &geom; a.binning_alloc = alloc_cb; a.binning_ctx = &binning;
     a.image_alloc = alloc_cb; a.image_ctx = &image;
     a.binning_capacity_hint = hint;
-    a.visible = (visible.defined() && visible.numel()) ? static_cast<uint8_t *>(visible.data_ptr()) : nullptr;
+    a.visible = (f.visible.defined() && f.visible.numel()) ? static_cast<uint8_t *>(f.visible.data_ptr()) : nullptr;
     a.num_units_out = &num_units;
     a.no_host_wait = capturing ? 1 : 0;
-    a.mesh = mesh;
-    a.points = points;
-    if (mesh && mesh_out) {
-        a.mesh_out_xyz = mf(mesh_out->xyz); a.mesh_out_scaling_act = mf(mesh_out->scaling_act);
-        a.mesh_out_rotation_unit = mf(mesh_out->rotation_unit); a.mesh_out_opacity_act = mf(mesh_out->opacity_act);
-    }
-    int64_t ticket[2] = {0, 0};
-    const bool defer = may_defer && hint > 0 && !capturing && P > 0 && deferred_counts();
-    if (defer) a.count_ticket_out = ticket;
-    const int64_t n = rest_rotation ? gms_rasterize_forward_local_sh(&a, rest_rotation, stream)
-                      : free_args   ? gms_rasterize_forward_free(&a, free_args, stream)
-                                    : gms_rasterize_forward(&a, stream);
+    const bool defer = opt.may_defer && hint > 0 && !capturing && P > 0 && g_defer_counts.get();
+    if (defer) a.count_ticket_out = f.ticket;
+    const char *entry = nullptr;
+    const int64_t n = src.run(a, stream, entry);
     TORCH_CHECK(!(geom.failed || binning.failed || image.failed), "scratch allocation failed (out of device memory?)");
-    check_rc(n, rest_rotation ? "gms_rasterize_forward_local_sh" : free_args ? "gms_rasterize_forward_free" : "gms_rasterize_forward");
+    check_rc(n, entry);
     f.num_rendered = n; f.num_units = num_units;
     f.capacity = (hint > 0 && n <= hint) ? hint : (n > 0 ? n : 1);
     f.geom = geom.t; f.binning = binning.t; f.image = image.t;
-    if (defer) { f.ticket[0] = ticket[0]; f.ticket[1] = ticket[1]; f.launched_units = gms_last_launched_units(); f.num_rendered = -1; f.capacity = hint; }
+    if (defer) { f.launched_units = gms_last_launched_units(); f.num_rendered = -1; f.capacity = hint; }
     {
         std::lock_guard<std::mutex> lk(g_mu);
         int64_t &c = g_capacity[key];
@@ -245,6 +269,27 @@ struct Backward { Tensor dmeans2D, dcolors, dopacity, dmeans3D, dcov3D, dsh, dsh
 struct MeshGrads { Tensor d_vertices, d_alpha, d_scale, d_opacity; };
 // outputs of the getters' backward when it runs in the tail of preprocess_bwd (gms_rasterize_backward_free)
 struct FreeGrads { Tensor d_scaling, d_rotation, d_opacity; };
+// What runs in the tail of preprocess_bwd behind the rasterizer's own backward: nothing, the mesh backward, or the getters' backward of a frame
+// straight from raw parameters (which therefore writes no dL/d(opacity, scales, rotations): alloc_backward).  Pointers as in FrameSource.
+struct BackwardTail {
+    enum Kind { NONE, MESH, FREE } kind = NONE;
+    const GmsMeshArgs *mesh_ = nullptr; const MeshGrads *mesh_grads = nullptr; const GmsFreeArgs *free_ = nullptr; const FreeGrads *free_grads = nullptr;
+    static BackwardTail none() { return {}; }
+    static BackwardTail mesh(const GmsMeshArgs &m, const MeshGrads &g) { return {MESH, &m, &g}; }
+    static BackwardTail free(const GmsFreeArgs &a, const FreeGrads &g) { return {FREE, nullptr, nullptr, &a, &g}; }
+    // points `a` at the tail and runs the C entry point of its kind
+    void run(GmsRasterBackwardArgs &a, void *stream) const
+    {
+        if (kind == MESH) {
+            a.mesh = mesh_; a.mesh_dL_dvertices = mf(mesh_grads->d_vertices); a.mesh_dL_dalpha = mf(mesh_grads->d_alpha);
+            a.mesh_dL_dscale = mf(mesh_grads->d_scale); a.mesh_dL_d_opacity = mf(mesh_grads->d_opacity);
+        }
+        if (kind == FREE)
+            check_rc(gms_rasterize_backward_free(&a, free_, mf(free_grads->d_scaling), mf(free_grads->d_rotation), mf(free_grads->d_opacity), stream),
+                     "gms_rasterize_backward_free");
+        else check_rc(gms_rasterize_backward(&a, stream), "gms_rasterize_backward");
+    }
+};
 
 // The gradient outputs of a backward call.  The autograd fast path allocates them in FORWARD, before the C call (there the
 // host runs ahead of the GPU and then waits for the instance count anyway), so that between "N has arrived" and "blend_bwd is
@@ -258,9 +303,9 @@ static std::atomic<bool> g_sh_factor{false};
 static std::map<int, std::vector<Tensor>> g_factors;
 constexpr size_t MAX_QUEUED_FACTORS = 256;
 
-// `raw`: a frame straight from raw parameters writes no dL/d(opacity, scales, rotations)
-Backward alloc_backward(const Gaussians &g, bool raw = false)
+Backward alloc_backward(const Gaussians &g, BackwardTail::Kind tail = BackwardTail::NONE)
 {
+    const bool raw = tail == BackwardTail::FREE;
     const int64_t P = g.means3D.size(0);
     auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(g.means3D.device());
     const bool has_sh = g.sh.defined() && g.sh.numel() > 0, split = g.sh_rest.defined() && g.sh_rest.numel() > 0;
@@ -279,17 +324,13 @@ Backward alloc_backward(const Gaussians &g, bool raw = false)
     return b;
 }
 
-// `f`: the forward's radii, scratch tensors and counts
+// `f`: the forward's radii, scratch tensors and counts; `prealloc`: the outputs the forward allocated, if it did
 Backward backward_core(const FrameSettings &s, const Gaussians &g, const Forward &f, const Tensor &dL_dcolor_, const Tensor &dL_dinvd_,
-                       const Backward *prealloc = nullptr, const GmsMeshArgs *mesh = nullptr, const MeshGrads *mesh_grads = nullptr,
-                       const GmsFreeArgs *free_args = nullptr, const FreeGrads *free_grads = nullptr)
+                       std::optional<Backward> prealloc, const BackwardTail &tail)
 {
     const auto dev = g.means3D.device();
     c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
     const int64_t P = g.means3D.size(0);
-    const bool has_sh = g.sh.defined() && g.sh.numel() > 0, split = g.sh_rest.defined() && g.sh_rest.numel() > 0;
-    int64_t M = has_sh ? g.sh.size(1) : 0;
-    if (split) M = g.sh.size(1) + g.sh_rest.size(1);
     auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
     Tensor gcol = f32c(dL_dcolor_), ginv = f32c(dL_dinvd_);
     void *stream = stream_of(dev);
@@ -301,14 +342,10 @@ Backward backward_core(const FrameSettings &s, const Gaussians &g, const Forward
         if (it != g_accum.end()) { accum = it->second; g_accum.erase(it); }
     }
     if (!accum.defined()) accum = torch::zeros({std::max<int64_t>(P, 1), 16}, fopt);
-    Backward b = prealloc ? *prealloc : alloc_backward(g, free_args != nullptr);
+    Backward b = prealloc ? std::move(*prealloc) : alloc_backward(g, tail.kind);
     GmsRasterBackwardArgs a{};
-    a.P = (int32_t)P; a.D = (int32_t)s.D; a.M = (int32_t)M; a.width = (int32_t)s.W; a.height = (int32_t)s.H;
+    const bool has_sh = frame_args(a, s, g, P);
     a.num_rendered = f.num_rendered; a.binning_capacity = f.capacity;
-    a.background = cf(s.bg); a.means3D = cf(g.means3D); a.shs = cf(g.sh); a.shs_rest = split ? cf(g.sh_rest) : nullptr;
-    a.colors_precomp = cf(g.colors); a.opacities = cf(g.opac); a.scales = cf(g.scales); a.rotations = cf(g.rots); a.cov3D_precomp = cf(g.cov);
-    a.viewmatrix = cf(s.view); a.projmatrix = cf(s.proj); a.campos = cf(s.campos);
-    a.scale_modifier = (float)s.mod; a.tan_fovx = (float)s.tanx; a.tan_fovy = (float)s.tany; a.antialiasing = s.aa; a.debug = s.debug;
     a.radii = P ? f.radii.data_ptr<int32_t>() : nullptr;
     a.geom_buffer = f.geom.numel() ? f.geom.data_ptr() : nullptr;
     a.binning_buffer = f.binning.numel() ? f.binning.data_ptr() : nullptr;
@@ -318,10 +355,6 @@ Backward backward_core(const FrameSettings &s, const Gaussians &g, const Forward
     a.dL_dmeans3D = mf(b.dmeans3D); a.dL_dcov3D = mf(b.dcov3D); a.dL_dsh = mf(b.dsh); a.dL_dsh_rest = mf(b.dsh_rest);
     a.dL_dscales = mf(b.dscales); a.dL_drotations = mf(b.drots);
     a.grad_accum_rezero = 1; a.num_units = f.num_units;
-    if (mesh && mesh_grads) {
-        a.mesh = mesh; a.mesh_dL_dvertices = mf(mesh_grads->d_vertices); a.mesh_dL_dalpha = mf(mesh_grads->d_alpha);
-        a.mesh_dL_dscale = mf(mesh_grads->d_scale); a.mesh_dL_d_opacity = mf(mesh_grads->d_opacity);
-    }
     a.sh_factor_mode = (has_sh && b.dcolors.defined()) ? 1 : 0;
     a.factor_campos_row = (a.sh_factor_mode && b.dcolors.size(0) == P + 1) ? 1 : 0;      // row P = the camera centre
     if (a.sh_factor_mode) {
@@ -329,16 +362,10 @@ Backward backward_core(const FrameSettings &s, const Gaussians &g, const Forward
         TORCH_CHECK(g_factors[(int)dev.index()].size() < MAX_QUEUED_FACTORS, "factorised SH mode: ", MAX_QUEUED_FACTORS,
                     " factors queued on this device and never taken (call take_sh_factors() every step, or set_sh_factor_mode(False))");
     }
-    if (P > 0 && free_args)
-        check_rc(gms_rasterize_backward_free(&a, free_args, mf(free_grads->d_scaling), mf(free_grads->d_rotation), mf(free_grads->d_opacity), stream),
-                 "gms_rasterize_backward_free");
-    else if (P > 0) check_rc(gms_rasterize_backward(&a, stream), "gms_rasterize_backward");
-    if (a.sh_factor_mode) {          // factorised mode: queue the factor (rows 0..P-1 + camera centre) for the exchange
+    if (P > 0) tail.run(a, stream);
+    {   // only a call that completed queues its factor (rows 0..P-1 + camera centre) for the exchange and hands its (re-zeroed) buffer back
         std::lock_guard<std::mutex> lk(g_mu);
-        g_factors[(int)dev.index()].push_back(b.dcolors);
-    }
-    {   // only a call that completed hands its (re-zeroed) buffer back
-        std::lock_guard<std::mutex> lk(g_mu);
+        if (a.sh_factor_mode) g_factors[(int)dev.index()].push_back(b.dcolors);
         if (g_accum.size() >= 8) g_accum.clear();
         g_accum[akey] = accum;
     }
@@ -357,7 +384,7 @@ rasterize_gaussians(const Tensor &background, const Tensor &means3D, const Tenso
     const Gaussians g = tensor_gaussians(means3D, sh, Tensor(), colors, opacity, scales, rotations, cov3D_precomp);
     const FrameSettings s = frame_settings(means3D.device(), background, viewmatrix, projmatrix, campos, image_height, image_width, tan_fovx,
                                            tan_fovy, scale_modifier, degree, prefiltered, antialiasing, debug);
-    Forward f = forward_core(s, means3D.size(0), means3D.device(), g, Tensor(), false);
+    Forward f = forward_core(s, means3D.size(0), means3D.device(), g, FrameSource::tensors(), {});
     return std::make_tuple(f.num_rendered, f.color, f.radii, f.geom, f.binning, f.image, f.invdepth);
 }
 
@@ -375,7 +402,7 @@ rasterize_gaussians_backward(const Tensor &background, const Tensor &means3D, co
                                            scale_modifier, degree, false, antialiasing, debug);
     Forward f;
     f.radii = radii; f.geom = geomBuffer; f.binning = binningBuffer; f.image = imageBuffer; f.num_rendered = R; f.capacity = R > 0 ? R : 1;
-    Backward b = backward_core(s, g, f, dL_dout_color, dL_dout_invdepth);
+    Backward b = backward_core(s, g, f, dL_dout_color, dL_dout_invdepth, std::nullopt, BackwardTail::none());
     return std::make_tuple(b.dmeans2D, b.dcolors, b.dopacity, b.dmeans3D, b.dcov3D, b.dsh, b.dscales, b.drots);
 }
 
@@ -391,6 +418,9 @@ Tensor mark_visible(const Tensor &means3D, const Tensor &viewmatrix, const Tenso
 }
 
 // ---------------------------------------------------------------------------------------------- autograd fast path
+// Will a backward follow a node with these differentiable inputs?  (Decided before apply(): inside forward() the graph node may not exist.)
+template <class... T> bool will_backward(const T &...inputs) { return at::GradMode::is_enabled() && (inputs.requires_grad() || ...); }
+
 // What an autograd node keeps of its frame: the settings and the forward's radii / scratch go to the end of its saved tensors, the
 // scalars and the frame record (counts, capacity, deferred ticket) to saved_data
 void save_frame(AutogradContext *ctx, std::vector<Tensor> tensors, const FrameSettings &s, const Forward &f)
@@ -405,11 +435,11 @@ void save_frame(AutogradContext *ctx, std::vector<Tensor> tensors, const FrameSe
 std::pair<FrameSettings, Forward> load_frame(AutogradContext *ctx, const variable_list &saved)
 {
     auto &d = ctx->saved_data;
-    const size_t k = saved.size() - 8;
-    FrameSettings s{saved[k + 4], saved[k + 5], saved[k + 6], saved[k + 7], d["H"].toInt(), d["W"].toInt(), d["tanx"].toDouble(),
-                    d["tany"].toDouble(), d["mod"].toDouble(), d["D"].toInt(), false, d["aa"].toBool(), d["debug"].toBool()};
+    auto t = saved.end() - 8;          // (what save_frame appended, in its order)
     Forward f;
-    f.radii = saved[k]; f.geom = saved[k + 1]; f.binning = saved[k + 2]; f.image = saved[k + 3];
+    f.radii = *t++; f.geom = *t++; f.binning = *t++; f.image = *t++;
+    FrameSettings s{*t++, *t++, *t++, *t++, d["H"].toInt(), d["W"].toInt(), d["tanx"].toDouble(), d["tany"].toDouble(), d["mod"].toDouble(),
+                    d["D"].toInt(), false, d["aa"].toBool(), d["debug"].toBool()};
     f.num_rendered = d["R"].toInt(); f.num_units = d["units"].toInt(); f.capacity = d["cap"].toInt();
     f.ticket[0] = d["ticket0"].toInt(); f.ticket[1] = d["ticket1"].toInt(); f.launched_units = d["launched"].toInt();
     return {s, f};
@@ -443,24 +473,43 @@ void redeem_counts(AutogradContext *ctx, const FrameSettings &s, Forward &f, con
 
 // The backward's outputs, allocated in the forward (see Backward) and handed out once: a second backward through a retained graph
 // allocates its own
-Tensor Backward::*const kBackwardFields[9] = {&Backward::dmeans2D, &Backward::dcolors, &Backward::dopacity, &Backward::dmeans3D, &Backward::dcov3D,
-                                              &Backward::dsh, &Backward::dsh_rest, &Backward::dscales, &Backward::drots};
 void stash_backward(AutogradContext *ctx, const Backward &b)
 {
-    for (int k = 0; k < 9; k++)
-        if ((b.*kBackwardFields[k]).defined()) ctx->saved_data[std::string("pre") + char('0' + k)] = b.*kBackwardFields[k];
-    ctx->saved_data["pre"] = true;
+    ctx->saved_data["pre"] = std::vector<Tensor>{b.dmeans2D, b.dcolors, b.dopacity, b.dmeans3D, b.dcov3D, b.dsh, b.dsh_rest, b.dscales, b.drots};
 }
 std::optional<Backward> take_backward(AutogradContext *ctx)
 {
-    if (!ctx->saved_data.count("pre")) return std::nullopt;
-    Backward b;
-    for (int k = 0; k < 9; k++) {
-        const std::string key = std::string("pre") + char('0' + k);
-        if (ctx->saved_data.count(key)) { b.*kBackwardFields[k] = ctx->saved_data[key].toTensor(); ctx->saved_data.erase(key); }
-    }
-    ctx->saved_data.erase("pre");
-    return b;
+    auto it = ctx->saved_data.find("pre");
+    if (it == ctx->saved_data.end()) return std::nullopt;
+    const std::vector<Tensor> v = it->second.toTensorVector();          // (Backward's fields, in their order; undefined ones stay undefined)
+    ctx->saved_data.erase(it);
+    auto t = v.begin();
+    return Backward{*t++, *t++, *t++, *t++, *t++, *t++, *t++, *t++, *t++};
+}
+
+// What the forwards of the three frame nodes share, and what such a forward leaves for its backward.  `stored`: the Gaussians as the rasterizer's backward
+// reads them; when one will follow, its outputs are allocated for them here, before the C call (see alloc_backward).  `saved`: the node's own tensors (its pack()).
+struct FrameKeep { bool will_backward; const Gaussians &stored; std::vector<Tensor> saved; };
+Forward frame_forward(AutogradContext *ctx, const FrameSettings &s, int64_t P, c10::Device dev, const Gaussians &g, const FrameSource &src,
+                      ForwardOptions opt, FrameKeep keep)
+{
+    ctx->set_materialize_grads(false);      // an unused output (inverse depth in train.py) arrives undefined: its channel is skipped
+    const auto tail = src.free_ ? BackwardTail::FREE : BackwardTail::NONE;          // (a frame from raw parameters: the getters' backward follows in the tail)
+    if (keep.will_backward && dev.is_cuda()) { c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev); stash_backward(ctx, alloc_backward(keep.stored, tail)); }
+    Forward f = forward_core(s, P, dev, g, src, opt);
+    save_frame(ctx, std::move(keep.saved), s, f);
+    return f;
+}
+// ... and the backwards: `saved` ends with what save_frame appended, `grads` = dL/d(image, radii, inverse depth), `g`: the Gaussians as the
+// rasterizer's backward reads them, `tail()`: the node's BackwardTail, built (and its outputs allocated) only once the counts are redeemed
+template <class Tail>
+Backward frame_backward(AutogradContext *ctx, const variable_list &saved, const variable_list &grads, const Gaussians &g, Tail &&tail)
+{
+    auto [s, f] = load_frame(ctx, saved);
+    Tensor gcol = grads[0].defined() ? grads[0] : torch::zeros({3, s.H, s.W}, g.means3D.options());
+    std::optional<Backward> pre = take_backward(ctx);
+    redeem_counts(ctx, s, f, g.means3D);
+    return backward_core(s, g, f, gcol, grads[2], std::move(pre), tail());
 }
 
 class RasterizeFn : public torch::autograd::Function<RasterizeFn> {
@@ -470,13 +519,10 @@ public:
                                  Tensor campos, int64_t H, int64_t W, double tanx, double tany, double mod, int64_t D, bool prefiltered,
                                  bool aa, bool debug, Tensor visible_out, bool use_hint, bool will_backward)
     {
-        ctx->set_materialize_grads(false);      // an unused output (inverse depth in train.py) arrives undefined: its channel is skipped
         const Gaussians g = tensor_gaussians(means3D, sh, sh_rest, colors, opacities, scales, rotations, cov3D);
         const auto dev = means3D.device();
-        const FrameSettings s = frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, D, prefiltered, aa, debug);
-        if (will_backward && means3D.is_cuda()) { c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev); stash_backward(ctx, alloc_backward(g)); }
-        Forward f = forward_core(s, means3D.size(0), dev, g, visible_out, use_hint, nullptr, nullptr, will_backward && use_hint);
-        save_frame(ctx, {g.sh, g.sh_rest, g.means3D, g.colors, g.opac, g.scales, g.rots, g.cov}, s, f);
+        Forward f = frame_forward(ctx, frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, D, prefiltered, aa, debug), means3D.size(0), dev, g,
+                                  FrameSource::tensors(visible_out), {use_hint, will_backward && use_hint}, {will_backward, g, g.pack()});
         ctx->mark_non_differentiable({f.radii});
         return {f.color, f.radii, f.invdepth};
     }
@@ -484,12 +530,8 @@ public:
     static variable_list backward(AutogradContext *ctx, variable_list grads)
     {
         auto saved = ctx->get_saved_variables();
-        const Gaussians g{saved[0], saved[1], saved[2], saved[3], saved[4], saved[5], saved[6], saved[7]};
-        auto [s, f] = load_frame(ctx, saved);
-        Tensor gcol = grads[0].defined() ? grads[0] : torch::zeros({3, s.H, s.W}, g.means3D.options());
-        std::optional<Backward> pre = take_backward(ctx);
-        redeem_counts(ctx, s, f, g.means3D);
-        Backward b = backward_core(s, g, f, gcol, grads[2], pre ? &*pre : nullptr);
+        const Gaussians g = Gaussians::unpack(saved);
+        Backward b = frame_backward(ctx, saved, grads, g, [] { return BackwardTail::none(); });
         Tensor none;
         if (g.sh.defined() && g.sh.numel() > 0) b.dcolors = none;          // (factorised mode: the factor is not a gradient of `colors`)
         return {b.dmeans3D, b.dmeans2D, b.dsh, b.dsh_rest, b.dcolors, b.dopacity, b.dscales, b.drots, b.dcov3D,
@@ -503,11 +545,9 @@ std::tuple<Tensor, Tensor, Tensor> rasterize(const Tensor &means3D, const Tensor
                                              const Tensor &campos, int64_t H, int64_t W, double tanx, double tany, double mod, int64_t D,
                                              bool prefiltered, bool aa, bool debug, const Tensor &visible_out, bool use_hint)
 {
-    const bool will_backward = at::GradMode::is_enabled() &&
-        (means3D.requires_grad() || means2D.requires_grad() || sh.requires_grad() || sh_rest.requires_grad() || colors.requires_grad() ||
-         opacities.requires_grad() || scales.requires_grad() || rotations.requires_grad() || cov3D.requires_grad());
-    auto out = RasterizeFn::apply(means3D, means2D, sh, sh_rest, colors, opacities, scales, rotations, cov3D, bg, view, proj, campos, H,
-                                  W, tanx, tany, mod, D, prefiltered, aa, debug, visible_out, use_hint, will_backward);
+    auto out = RasterizeFn::apply(means3D, means2D, sh, sh_rest, colors, opacities, scales, rotations, cov3D, bg, view, proj, campos, H, W, tanx, tany,
+                                  mod, D, prefiltered, aa, debug, visible_out, use_hint,
+                                  will_backward(means3D, means2D, sh, sh_rest, colors, opacities, scales, rotations, cov3D));
     return std::make_tuple(out[0], out[1], out[2]);
 }
 
@@ -566,8 +606,7 @@ py::dict last_stats()
     d["num_rendered"] = g_last.num_rendered; d["num_units"] = g_last.num_units; d["capacity_hint"] = g_last.hint;
     d["P"] = g_last.P; d["width"] = g_last.W; d["height"] = g_last.H; d["deepest_tile"] = gms_last_deepest_tile();
     d["used_micro"] = (int)gms_last_used_micro();
-    static const char *const routes[] = {"none", "tail4", "tail_runs", "launch"};
-    d["mesh_backward_route"] = routes[g_mesh_bwd_route.load()];
+    d["mesh_backward_route"] = g_mesh_bwd_route.load();
     if (g_last.radii.defined()) { d["radii"] = g_last.radii; d["image"] = g_last.image; d["binning"] = g_last.binning; d["geom"] = g_last.geom; }
     return d;
 }
@@ -628,42 +667,41 @@ const float *rest_rotation_ptr(const char *what, const Tensor &rest_rotation, in
 // Forward-only frame of the animated render drivers (games_hip.animate): mesh -> image in the rasterizer's own launches, K0 inside
 // the preprocess thread (GmsRasterForwardArgs.mesh).  Returns (image, radii, inverse depth, radii > 0).
 // `rest_rotation` (render_mesh_forward_local_sh; undefined: the plain frame): the SH rows are evaluated on the pose-local direction.
-std::tuple<Tensor, Tensor, Tensor, Tensor> mesh_forward_frame(const char *what, const Tensor &vertices, const Tensor &faces, const Tensor &_alpha,
-                                                      const Tensor &_scale, const Tensor &_opacity, int64_t mode, int64_t spf,
+std::tuple<Tensor, Tensor, Tensor, Tensor> mesh_forward_frame(const char *what, const Tensor &rest_rotation, const Tensor &vertices, const Tensor &faces,
+                                                      const Tensor &_alpha, const Tensor &_scale, const Tensor &_opacity, int64_t mode, int64_t spf,
                                                       const Tensor &splat_face, const Tensor &sh_dc, const Tensor &sh_rest, const Tensor &bg,
                                                       const Tensor &view, const Tensor &proj, const Tensor &campos, int64_t H, int64_t W,
-                                                      double tanx, double tany, double mod, bool aa, bool debug, const Tensor &rest_rotation)
+                                                      double tanx, double tany, double mod, bool aa, bool debug)
 {
     const int64_t P = check_mesh_frame(what, vertices, faces, _alpha, _scale, _opacity, spf, splat_face, sh_dc, sh_rest);
     const float *rest = rest_rotation.defined() ? rest_rotation_ptr(what, rest_rotation, P, sh_dc.device()) : nullptr;
     Tensor v = f32c(vertices), al = f32c(_alpha), sc = f32c(_scale), op = f32c(_opacity);
     GmsMeshArgs m = mesh_args(v, faces, al, sc, mode, spf, Tensor(), splat_face, true, op);
-    Tensor visible = torch::empty({P}, sh_dc.options().dtype(torch::kBool));          // radii > 0, written by the preprocess kernel
     const auto dev = sh_dc.device();
     Forward f = forward_core(frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, 3, false, aa, debug), P, dev,
-                             {f32c(sh_dc), f32c(sh_rest)}, visible, true, &m, nullptr, false, nullptr, nullptr, rest);
-    return std::make_tuple(f.color, f.radii, f.invdepth, visible);
+                             {f32c(sh_dc), f32c(sh_rest)}, FrameSource::mesh(m, rest), {true, false});
+    return std::make_tuple(f.color, f.radii, f.invdepth, f.visible);
 }
-std::tuple<Tensor, Tensor, Tensor, Tensor> render_mesh_forward(const Tensor &vertices, const Tensor &faces, const Tensor &_alpha, const Tensor &_scale,
-                                                       const Tensor &_opacity, int64_t mode, int64_t spf, const Tensor &splat_face,
-                                                       const Tensor &sh_dc, const Tensor &sh_rest, const Tensor &bg, const Tensor &view,
-                                                       const Tensor &proj, const Tensor &campos, int64_t H, int64_t W, double tanx, double tany,
-                                                       double mod, bool aa, bool debug)
+// The two Python entries of a forward-only frame `frame(what, rest_rotation, args...)`: (args...), and with SH that turn with the face or
+// triangle (gms_rasterize_forward_local_sh) the same arguments, then rest_rotation [P,4]
+template <class R, class... A>
+auto plain_entry(R (*frame)(const char *, const Tensor &, A...), const char *what) { return [=](A... args) { return frame(what, Tensor(), args...); }; }
+template <class R, class... A>
+auto local_sh_entry(R (*frame)(const char *, const Tensor &, A...), const char *what)
 {
-    return mesh_forward_frame("render_mesh_forward", vertices, faces, _alpha, _scale, _opacity, mode, spf, splat_face, sh_dc, sh_rest, bg, view, proj,
-                              campos, H, W, tanx, tany, mod, aa, debug, Tensor());
+    return [=](A... args, const Tensor &rest_rotation) {
+        TORCH_CHECK(rest_rotation.defined(), what, ": rest_rotation is required");
+        return frame(what, rest_rotation, args...);
+    };
 }
-// ... with spherical harmonics that turn with the face (gms_rasterize_forward_local_sh): the same arguments, then rest_rotation [P,4]
-std::tuple<Tensor, Tensor, Tensor, Tensor> render_mesh_forward_local_sh(const Tensor &vertices, const Tensor &faces, const Tensor &_alpha,
-                                                                const Tensor &_scale, const Tensor &_opacity, int64_t mode, int64_t spf,
-                                                                const Tensor &splat_face, const Tensor &sh_dc, const Tensor &sh_rest,
-                                                                const Tensor &bg, const Tensor &view, const Tensor &proj, const Tensor &campos,
-                                                                int64_t H, int64_t W, double tanx, double tany, double mod, bool aa, bool debug,
-                                                                const Tensor &rest_rotation)
+
+// The vertex-gradient buffer the forward cleared (`vgrad`; undefined: it cleared none) serves ONE backward; a second one through a retained
+// graph clears its own.  -> (the buffer for dL/dvertices, whether it comes cleared)
+std::pair<Tensor, bool> vertex_grad_once(AutogradContext *ctx, const Tensor &vgrad, const Tensor &vertices)
 {
-    TORCH_CHECK(rest_rotation.defined(), "render_mesh_forward_local_sh: rest_rotation is required");
-    return mesh_forward_frame("render_mesh_forward_local_sh", vertices, faces, _alpha, _scale, _opacity, mode, spf, splat_face, sh_dc, sh_rest, bg,
-                              view, proj, campos, H, W, tanx, tany, mod, aa, debug, rest_rotation);
+    if (!vgrad.defined() || ctx->saved_data["used"].toBool()) return {torch::empty_like(vertices), false};
+    ctx->saved_data["used"] = true;
+    return {vgrad, true};
 }
 
 class MeshFn : public torch::autograd::Function<MeshFn> {
@@ -679,8 +717,7 @@ public:
         TORCH_CHECK(!has_op || fused, "_opacity fusion needs fused_activations=True");
         Tensor vertices = f32c(vertices_), _alpha = f32c(alpha_), _scale = f32c(scale_), _opacity = f32c(opacity_);
         Tensor faces = faces_.scalar_type() == torch::kLong ? faces_.contiguous() : faces_.to(torch::kLong).contiguous();
-        Tensor fso = fso_.defined() && fso_.numel() ? fso_.to(torch::kInt).contiguous() : Tensor();
-        Tensor sf = sf_.defined() && sf_.numel() ? sf_.to(torch::kInt).contiguous() : Tensor();
+        Tensor fso = i32c(fso_), sf = i32c(sf_);
         const int64_t P = _scale.numel();
         auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
         Tensor alpha = torch::empty_like(_alpha), xyz = torch::empty({P, 3}, fopt), scaling = torch::empty({P, 3}, fopt);
@@ -694,9 +731,7 @@ public:
         a.prezero = mf(vgrad); a.prezero_count = vgrad.defined() ? vgrad.numel() : 0;
         check_rc(gms_mesh_to_gaussians_forward(&a, mf(alpha), mf(xyz), mf(scaling), mf(rotation), mf(sact), mf(runit), mf(oact),
                                                stream_of(vertices)), "gms_mesh_to_gaussians_forward");
-        ctx->save_for_backward({vertices, faces, _alpha, _scale, fso.defined() ? fso : torch::empty({0}, fopt),
-                                sf.defined() ? sf : torch::empty({0}, fopt), has_op ? _opacity : torch::empty({0}, fopt),
-                                vgrad.defined() ? vgrad : torch::empty({0}, fopt)});
+        ctx->save_for_backward({vertices, faces, _alpha, _scale, keep_opt(fso, fopt), keep_opt(sf, fopt), keep_opt(_opacity, fopt), keep_opt(vgrad, fopt)});
         ctx->saved_data["mode"] = mode; ctx->saved_data["spf"] = spf; ctx->saved_data["fused"] = fused; ctx->saved_data["used"] = false;
         if (fused) {
             ctx->mark_non_differentiable({alpha, scaling, rotation});
@@ -709,9 +744,10 @@ public:
 
     static variable_list backward(AutogradContext *ctx, variable_list g)
     {
-        auto s = ctx->get_saved_variables();
-        const Tensor &vertices = s[0], &faces = s[1], &_alpha = s[2], &_scale = s[3];
-        Tensor fso = s[4].numel() ? s[4] : Tensor(), sf = s[5].numel() ? s[5] : Tensor(), _opacity = s[6].numel() ? s[6] : Tensor();
+        auto saved = ctx->get_saved_variables();
+        auto t = saved.begin();          // (the order of forward's save_for_backward)
+        const Tensor &vertices = *t++, &faces = *t++, &_alpha = *t++, &_scale = *t++;
+        Tensor fso = kept_opt(*t++), sf = kept_opt(*t++), _opacity = kept_opt(*t++), vgrad = kept_opt(*t++);
         const bool fused = ctx->saved_data["fused"].toBool();
         const auto dev = vertices.device();
         c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
@@ -721,11 +757,7 @@ public:
         Tensor g_op = (fused && g.size() > 6) ? g[6] : Tensor();
         auto gz = [&](const Tensor &t, int64_t c) { return t.defined() ? f32c(t) : torch::zeros({P, c}, fopt); };
         g_xyz = gz(g_xyz, 3); g_scaling = gz(g_scaling, 3); g_rot = gz(g_rot, 4);
-        // the pre-cleared vertex-gradient buffer serves ONE backward; a second one through a retained graph clears its own
-        Tensor d_vertices;
-        bool prezeroed = false;
-        if (s[7].numel() && !ctx->saved_data["used"].toBool()) { d_vertices = s[7]; prezeroed = true; ctx->saved_data["used"] = true; }
-        else d_vertices = torch::empty_like(vertices);
+        auto [d_vertices, prezeroed] = vertex_grad_once(ctx, vgrad, vertices);
         Tensor d_alpha = torch::empty_like(_alpha), d_scale = torch::empty_like(_scale), d_opacity;
         const bool want_op = _opacity.defined() && g_op.defined();
         if (want_op) { g_op = f32c(g_op); d_opacity = torch::empty_like(_opacity); }
@@ -743,9 +775,7 @@ public:
 std::vector<Tensor> mesh_to_gaussians(const Tensor &vertices, const Tensor &faces, const Tensor &_alpha, const Tensor &_scale, int64_t mode,
                                       int64_t spf, const Tensor &fso, const Tensor &sf, bool fused, const Tensor &_opacity)
 {
-    // (whether a backward will follow is decided here: inside forward() the graph node may not exist)
-    return MeshFn::apply(vertices, faces, _alpha, _scale, mode, spf, fso, sf, fused, _opacity,
-                         at::GradMode::is_enabled() && vertices.requires_grad());
+    return MeshFn::apply(vertices, faces, _alpha, _scale, mode, spf, fso, sf, fused, _opacity, will_backward(vertices));
 }
 
 // ---------------------------------------------------------------------------------------------- pseudo-triangle -> Gaussian (gs_points)
@@ -801,7 +831,7 @@ public:
         GmsPointsArgs a = points_args(triangles, _opacity, eps, eps_s0);
         check_rc(gms_points_to_gaussians_forward(&a, mf(xyz), mf(scaling), mf(rotation), mf(sact), mf(runit), mf(oact), stream_of(triangles)),
                  "gms_points_to_gaussians_forward");
-        ctx->save_for_backward({triangles, has_op ? _opacity : torch::empty({0}, fopt)});
+        ctx->save_for_backward({triangles, keep_opt(_opacity, fopt)});
         ctx->saved_data["eps"] = eps; ctx->saved_data["eps_s0"] = eps_s0;
         ctx->mark_non_differentiable({scaling, rotation});
         if (has_op) return {xyz, scaling, rotation, sact, runit, oact};
@@ -811,8 +841,8 @@ public:
     static variable_list backward(AutogradContext *ctx, variable_list g)
     {
         auto s = ctx->get_saved_variables();
-        const Tensor &triangles = s[0];
-        Tensor _opacity = s[1].numel() ? s[1] : Tensor();
+        const Tensor &triangles = s.front();
+        Tensor _opacity = kept_opt(s.back());
         const auto dev = triangles.device();
         c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
         const int64_t P = triangles.size(0);
@@ -840,11 +870,10 @@ std::vector<Tensor> points_to_gaussians(const Tensor &triangles, const Tensor &_
 // rasterizer's own launches, the points op inside the preprocess thread (GmsRasterForwardArgs.points).  Returns (image, radii,
 // inverse depth, radii > 0).
 // `rest_rotation` (render_points_forward_local_sh; undefined: the plain frame): the SH rows are evaluated on the pose-local direction.
-std::tuple<Tensor, Tensor, Tensor, Tensor> points_forward_frame(const Tensor &triangles_, const Tensor &_opacity, const Tensor &sh_dc,
-                                                        const Tensor &sh_rest, const Tensor &bg, const Tensor &view, const Tensor &proj,
+std::tuple<Tensor, Tensor, Tensor, Tensor> points_forward_frame(const char *what, const Tensor &rest_rotation, const Tensor &triangles_, const Tensor &_opacity,
+                                                        const Tensor &sh_dc, const Tensor &sh_rest, const Tensor &bg, const Tensor &view, const Tensor &proj,
                                                         const Tensor &campos, int64_t H, int64_t W, double tanx, double tany, double mod,
-                                                        bool aa, bool debug, int64_t sh_degree, double eps, double eps_s0,
-                                                        const Tensor &rest_rotation)
+                                                        bool aa, bool debug, int64_t sh_degree, double eps, double eps_s0)
 {
     Tensor tri = points_triangles(triangles_, "render_points_forward");
     require_gpu(_opacity); require_gpu(sh_dc); require_gpu(sh_rest);
@@ -854,32 +883,12 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> points_forward_frame(const Tensor &tr
     TORCH_CHECK(op.numel() == P && sh_dc.size(0) == P && sh_rest.size(0) == P, "render_points_forward: P mismatch");
     TORCH_CHECK(tri.device() == sh_dc.device() && op.device() == sh_dc.device(), "render_points_forward: triangles and SH tensors live on different devices");
     check_split_sh("render_points_forward", sh_dc, sh_rest);
-    const float *rest = rest_rotation.defined() ? rest_rotation_ptr("render_points_forward_local_sh", rest_rotation, P, sh_dc.device()) : nullptr;
+    const float *rest = rest_rotation.defined() ? rest_rotation_ptr(what, rest_rotation, P, sh_dc.device()) : nullptr;
     GmsPointsArgs pa = points_args(tri, op, eps, eps_s0);
-    Tensor visible = torch::empty({P}, sh_dc.options().dtype(torch::kBool));          // radii > 0, written by the preprocess kernel
     const auto dev = sh_dc.device();
     Forward f = forward_core(frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, sh_degree, false, aa, debug), P, dev,
-                             {f32c(sh_dc), f32c(sh_rest)}, visible, true, nullptr, nullptr, false, &pa, nullptr, rest);
-    return std::make_tuple(f.color, f.radii, f.invdepth, visible);
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor> render_points_forward(const Tensor &triangles_, const Tensor &_opacity, const Tensor &sh_dc,
-                                                         const Tensor &sh_rest, const Tensor &bg, const Tensor &view, const Tensor &proj,
-                                                         const Tensor &campos, int64_t H, int64_t W, double tanx, double tany, double mod,
-                                                         bool aa, bool debug, int64_t sh_degree, double eps, double eps_s0)
-{
-    return points_forward_frame(triangles_, _opacity, sh_dc, sh_rest, bg, view, proj, campos, H, W, tanx, tany, mod, aa, debug, sh_degree, eps, eps_s0,
-                                Tensor());
-}
-// ... with spherical harmonics that turn with the triangle (gms_rasterize_forward_local_sh): the same arguments, then rest_rotation [P,4]
-std::tuple<Tensor, Tensor, Tensor, Tensor> render_points_forward_local_sh(const Tensor &triangles_, const Tensor &_opacity, const Tensor &sh_dc,
-                                                                  const Tensor &sh_rest, const Tensor &bg, const Tensor &view, const Tensor &proj,
-                                                                  const Tensor &campos, int64_t H, int64_t W, double tanx, double tany,
-                                                                  double mod, bool aa, bool debug, int64_t sh_degree, double eps, double eps_s0,
-                                                                  const Tensor &rest_rotation)
-{
-    TORCH_CHECK(rest_rotation.defined(), "render_points_forward_local_sh: rest_rotation is required");
-    return points_forward_frame(triangles_, _opacity, sh_dc, sh_rest, bg, view, proj, campos, H, W, tanx, tany, mod, aa, debug, sh_degree, eps, eps_s0,
-                                rest_rotation);
+                             {f32c(sh_dc), f32c(sh_rest)}, FrameSource::points(pa, rest), {true, false});
+    return std::make_tuple(f.color, f.radii, f.invdepth, f.visible);
 }
 
 // ---------------------------------------------------------------------------------------------- training frame straight from the mesh
@@ -893,6 +902,19 @@ Gaussians stored_gaussians(const MeshOut &mo, const Tensor &dc, const Tensor &re
 {
     return {dc, rest, mo.xyz, Tensor(), mo.opacity_act, mo.scaling_act, mo.rotation_unit, Tensor()};
 }
+// what RenderMeshFn saves, in this order; optional: sf (splat_face), vgrad (the vertex-gradient buffer the forward cleared), fso (face_splat_offset)
+struct MeshFrameSaved {
+    Tensor v, faces, al, sc, op, sf, vgrad; MeshOut mo; Tensor dc, rest, fso;
+    std::vector<Tensor> pack(const torch::TensorOptions &o) const
+    {
+        return {v, faces, al, sc, op, keep_opt(sf, o), keep_opt(vgrad, o), mo.xyz, mo.scaling_act, mo.rotation_unit, mo.opacity_act, dc, rest, keep_opt(fso, o)};
+    }
+    static MeshFrameSaved unpack(const variable_list &saved)
+    {
+        auto t = saved.begin();
+        return {*t++, *t++, *t++, *t++, *t++, kept_opt(*t++), kept_opt(*t++), {*t++, *t++, *t++, *t++}, *t++, *t++, kept_opt(*t++)};
+    }
+};
 
 class RenderMeshFn : public torch::autograd::Function<RenderMeshFn> {
 public:
@@ -901,71 +923,57 @@ public:
                                  Tensor view, Tensor proj, Tensor campos, int64_t H, int64_t W, double tanx, double tany, double mod,
                                  bool aa, bool debug, bool vertex_grad, bool will_backward, int64_t sh_degree, Tensor face_splat_offset)
     {
-        ctx->set_materialize_grads(false);
         TORCH_CHECK(sh_degree >= 0 && sh_degree <= 3, "render_mesh: active SH degree ", sh_degree, " (storage is degree 3: 0 .. 3)");
         const int64_t P = check_mesh_frame("render_mesh", vertices_, faces, alpha_, scale_, opacity_, spf, splat_face, sh_dc, sh_rest);
         const auto dev = vertices_.device();
         c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
-        Tensor v = f32c(vertices_), al = f32c(alpha_), sc = f32c(scale_), op = f32c(opacity_), dc = f32c(sh_dc), rest = f32c(sh_rest);
         auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
-        MeshOut mo{torch::empty({P, 3}, fopt), torch::empty({P, 3}, fopt), torch::empty({P, 4}, fopt), torch::empty_like(op)};
-        Tensor vgrad = will_backward && vertex_grad ? torch::empty_like(v) : Tensor();
-        if (will_backward) stash_backward(ctx, alloc_backward(stored_gaussians(mo, dc, rest)));      // (see Backward)
-        Tensor sf = (splat_face.defined() && splat_face.numel()) ? splat_face.to(torch::kInt).contiguous() : Tensor();
-        Tensor fso = (face_splat_offset.defined() && face_splat_offset.numel()) ? face_splat_offset.to(torch::kInt).contiguous() : Tensor();
-        TORCH_CHECK(!fso.defined() || (fso.numel() == faces.size(0) + 1 && fso.device() == dev), "render_mesh: face_splat_offset must hold F + 1 offsets on the mesh's device");
-        GmsMeshArgs m = mesh_args(v, faces, al, sc, mode, spf, Tensor(), sf, true, op);
-        m.prezero = mf(vgrad); m.prezero_count = vgrad.defined() ? vgrad.numel() : 0;
-        // `visibility_filter` (radii > 0, renderer/gaussian_renderer/__init__.py:108) out of the preprocess kernel, as on the two-node route
-        Tensor visible = torch::empty({P}, fopt.dtype(torch::kBool));
-        const FrameSettings s = frame_settings(dc.device(), bg, view, proj, campos, H, W, tanx, tany, mod, sh_degree, false, aa, debug);
-        Forward f = forward_core(s, P, dc.device(), {dc, rest}, visible, true, &m, &mo, will_backward);
-        save_frame(ctx, {v, faces, al, sc, op, sf.defined() ? sf : torch::empty({0}, fopt), vgrad.defined() ? vgrad : torch::empty({0}, fopt),
-                         mo.xyz, mo.scaling_act, mo.rotation_unit, mo.opacity_act, dc, rest, fso.defined() ? fso : torch::empty({0}, fopt)}, s, f);
+        MeshFrameSaved k{f32c(vertices_), faces, f32c(alpha_), f32c(scale_), f32c(opacity_), i32c(splat_face), Tensor(), {}, f32c(sh_dc), f32c(sh_rest),
+                         i32c(face_splat_offset)};
+        k.mo = {torch::empty({P, 3}, fopt), torch::empty({P, 3}, fopt), torch::empty({P, 4}, fopt), torch::empty_like(k.op)};
+        if (will_backward && vertex_grad) k.vgrad = torch::empty_like(k.v);
+        TORCH_CHECK(!k.fso.defined() || (k.fso.numel() == faces.size(0) + 1 && k.fso.device() == dev), "render_mesh: face_splat_offset must hold F + 1 offsets on the mesh's device");
+        GmsMeshArgs m = mesh_args(k.v, faces, k.al, k.sc, mode, spf, Tensor(), k.sf, true, k.op);
+        m.prezero = mf(k.vgrad); m.prezero_count = k.vgrad.defined() ? k.vgrad.numel() : 0;
+        Forward f = frame_forward(ctx, frame_settings(k.dc.device(), bg, view, proj, campos, H, W, tanx, tany, mod, sh_degree, false, aa, debug), P,
+                                  k.dc.device(), {k.dc, k.rest}, FrameSource::mesh_training(m, k.mo), {true, will_backward},
+                                  {will_backward, stored_gaussians(k.mo, k.dc, k.rest), k.pack(fopt)});
         ctx->saved_data["mode"] = mode; ctx->saved_data["spf"] = spf; ctx->saved_data["used"] = false;
         // the stored Gaussians are by-products for the model's attributes: gradients reach the mesh parameters through THIS node
-        ctx->mark_non_differentiable({f.radii, mo.xyz, mo.scaling_act, mo.rotation_unit, mo.opacity_act, visible});
-        return {f.color, f.radii, f.invdepth, mo.xyz, mo.scaling_act, mo.rotation_unit, mo.opacity_act, visible};
+        ctx->mark_non_differentiable({f.radii, k.mo.xyz, k.mo.scaling_act, k.mo.rotation_unit, k.mo.opacity_act, f.visible});
+        return {f.color, f.radii, f.invdepth, k.mo.xyz, k.mo.scaling_act, k.mo.rotation_unit, k.mo.opacity_act, f.visible};
     }
 
     static variable_list backward(AutogradContext *ctx, variable_list grads)
     {
         auto saved = ctx->get_saved_variables();
-        const Tensor &v = saved[0], &faces = saved[1], &al = saved[2], &sc = saved[3], &op = saved[4];
-        Tensor sf = saved[5].numel() ? saved[5] : Tensor(), fso = saved[13].numel() ? saved[13] : Tensor();
-        const Gaussians g = stored_gaussians({saved[7], saved[8], saved[9], saved[10]}, saved[11], saved[12]);
-        auto [s, f] = load_frame(ctx, saved);
-        const auto dev = v.device();
-        c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
-        Tensor gcol = grads[0].defined() ? grads[0] : torch::zeros({3, s.H, s.W}, g.means3D.options());
-        std::optional<Backward> pre = take_backward(ctx);
-        redeem_counts(ctx, s, f, g.means3D);
-        Tensor d_vertices;
-        bool prezeroed = false;
-        if (saved[6].numel() && !ctx->saved_data["used"].toBool()) { d_vertices = saved[6]; prezeroed = true; ctx->saved_data["used"] = true; }
-        else d_vertices = torch::empty_like(v);
-        Tensor d_alpha = torch::empty_like(al), d_scale = torch::empty_like(sc), d_opacity = torch::empty_like(op);
-        GmsMeshArgs a = mesh_args(v, faces, al, sc, ctx->saved_data["mode"].toInt(), ctx->saved_data["spf"].toInt(), fso, sf, true, op);
-        a.vertex_grad_prezeroed = prezeroed;
-        // The mesh backward INSIDE preprocess_bwd (ABI 8): the thread of a Gaussian carries its gradients on through the face -> Gaussian
-        // parameterization from registers -- no dL/dxyz / dL/dscale / dL/drot / dL/dopacity tensors, no mesh_bwd launch.  Needs the vertex
-        // gradient buffer the forward cleared and float-atomics mode.  1-4 splats per face: the tail of preprocess_bwd_kernel<true>; more, or
-        // CSR tables: the segmented reduction of preprocess_bwd_kernel<true, MeshRuns>.  GMS_TRAIN_FUSED_BWD=0 keeps the two launches for every shape,
-        // GMS_TRAIN_FUSED_BWD_RUNS=0 for the second class alone.
-        const bool tail4 = a.splats_per_face >= 1 && a.splats_per_face <= 4;
-        const bool fused_bwd = fused_mesh_backward() && (tail4 || fused_mesh_backward_runs()) && prezeroed && !gms_get_deterministic() && !g_sh_factor.load();
-        g_mesh_bwd_route.store(!fused_bwd ? MESH_BWD_LAUNCH : tail4 ? MESH_BWD_TAIL4 : MESH_BWD_TAIL_RUNS);
-        MeshGrads mg{d_vertices, d_alpha, d_scale, d_opacity};
-        Backward b = backward_core(s, g, f, gcol, grads[2], pre ? &*pre : nullptr, fused_bwd ? &a : nullptr, fused_bwd ? &mg : nullptr);
+        const MeshFrameSaved k = MeshFrameSaved::unpack(saved);
+        c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(k.v.device());
+        MeshGrads mg; GmsMeshArgs a; bool fused_bwd = false;
+        Backward b = frame_backward(ctx, saved, grads, stored_gaussians(k.mo, k.dc, k.rest), [&] {
+            auto [d_vertices, prezeroed] = vertex_grad_once(ctx, k.vgrad, k.v);
+            mg = MeshGrads{d_vertices, torch::empty_like(k.al), torch::empty_like(k.sc), torch::empty_like(k.op)};
+            a = mesh_args(k.v, k.faces, k.al, k.sc, ctx->saved_data["mode"].toInt(), ctx->saved_data["spf"].toInt(), k.fso, k.sf, true, k.op);
+            a.vertex_grad_prezeroed = prezeroed;
+            // The mesh backward INSIDE preprocess_bwd (ABI 8): the thread of a Gaussian carries its gradients on through the face -> Gaussian
+            // parameterization from registers -- no dL/dxyz / dL/dscale / dL/drot / dL/dopacity tensors, no mesh_bwd launch.  Needs the vertex
+            // gradient buffer the forward cleared and float-atomics mode.  1-4 splats per face: the tail of preprocess_bwd_kernel<true>; more, or
+            // CSR tables: the segmented reduction of preprocess_bwd_kernel<true, MeshRuns>.  GMS_TRAIN_FUSED_BWD=0 keeps the two launches for
+            // every shape, GMS_TRAIN_FUSED_BWD_RUNS=0 for the second class alone.
+            const bool tail4 = a.splats_per_face >= 1 && a.splats_per_face <= 4;
+            fused_bwd = g_fused_mesh_bwd.get() && (tail4 || g_fused_mesh_bwd_runs.get()) && prezeroed && !gms_get_deterministic() && !g_sh_factor.load();
+            g_mesh_bwd_route.store(!fused_bwd ? "launch" : tail4 ? "tail4" : "tail_runs");
+            return fused_bwd ? BackwardTail::mesh(a, mg) : BackwardTail::none();
+        });
         if (!fused_bwd) {
             // ... else through the mesh -> Gaussian parameterization as a launch of its own (fused activations: gradients w.r.t. exp / normalize /
             // sigmoid outputs).  Non-uniform splat counts: its per-face part walks the CSR offsets the node carries for this.
-            TORCH_CHECK(a.splats_per_face > 0 || fso.defined(), "render_mesh backward: the mesh backward launch of non-uniform splat counts needs face_splat_offset");
-            check_rc(gms_mesh_to_gaussians_backward(&a, cf(b.dmeans3D), cf(b.dscales), cf(b.drots), cf(b.dopacity), mf(d_vertices), mf(d_alpha),
-                                                    mf(d_scale), mf(d_opacity), stream_of(v)), "gms_mesh_to_gaussians_backward");
+            TORCH_CHECK(a.splats_per_face > 0 || k.fso.defined(), "render_mesh backward: the mesh backward launch of non-uniform splat counts needs face_splat_offset");
+            check_rc(gms_mesh_to_gaussians_backward(&a, cf(b.dmeans3D), cf(b.dscales), cf(b.drots), cf(b.dopacity), mf(mg.d_vertices), mf(mg.d_alpha),
+                                                    mf(mg.d_scale), mf(mg.d_opacity), stream_of(k.v)), "gms_mesh_to_gaussians_backward");
         }
         Tensor none;
-        return {d_vertices, none, d_alpha, d_scale, d_opacity, b.dsh, b.dsh_rest, b.dmeans2D,
+        return {mg.d_vertices, none, mg.d_alpha, mg.d_scale, mg.d_opacity, b.dsh, b.dsh_rest, b.dmeans2D,
                 none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none, none};
     }
 };
@@ -975,11 +983,9 @@ std::vector<Tensor> render_mesh(const Tensor &vertices, const Tensor &faces, con
                                 const Tensor &bg, const Tensor &view, const Tensor &proj, const Tensor &campos, int64_t H, int64_t W, double tanx,
                                 double tany, double mod, bool aa, bool debug, int64_t sh_degree, const std::optional<Tensor> &face_splat_offset)
 {
-    const bool will_backward = at::GradMode::is_enabled() &&
-        (vertices.requires_grad() || _alpha.requires_grad() || _scale.requires_grad() || _opacity.requires_grad() || sh_dc.requires_grad() ||
-         sh_rest.requires_grad() || means2D.requires_grad());
     return RenderMeshFn::apply(vertices, faces, _alpha, _scale, _opacity, sh_dc, sh_rest, means2D, mode, spf, splat_face, bg, view, proj, campos, H, W,
-                               tanx, tany, mod, aa, debug, vertices.requires_grad(), will_backward, sh_degree,
+                               tanx, tany, mod, aa, debug, vertices.requires_grad(),
+                               will_backward(vertices, _alpha, _scale, _opacity, sh_dc, sh_rest, means2D), sh_degree,
                                face_splat_offset ? *face_splat_offset : torch::empty({0}, faces.options().dtype(torch::kInt)));      // (a defined tensor: autograd asks every tensor argument for its device)
 }
 
@@ -1026,8 +1032,8 @@ public:
 
     static variable_list backward(AutogradContext *ctx, variable_list g)
     {
-        auto s = ctx->get_saved_variables();
-        const FreeIn in{s[0], s[1], s[2]};
+        auto s = ctx->get_saved_variables(); auto t = s.begin();
+        const FreeIn in{*t++, *t++, *t++};
         const auto dev = in.scaling.device();
         c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
         Tensor gs = g[0].defined() ? f32c(g[0]) : Tensor(), gq = g[1].defined() ? f32c(g[1]) : Tensor(), gop = g[2].defined() ? f32c(g[2]) : Tensor();
@@ -1044,13 +1050,21 @@ std::vector<Tensor> free_to_gaussians(const Tensor &_scaling, const Tensor &_rot
     return FreeFn::apply(_scaling, _rotation, _opacity, eps_s0);
 }
 
+// what RenderFreeFn saves, in this order
+struct FreeFrameSaved {
+    Tensor xyz; FreeIn in; Tensor dc, rest;
+    std::vector<Tensor> pack() const { return {xyz, in.scaling, in.rotation, in.opacity, dc, rest}; }
+    static FreeFrameSaved unpack(const variable_list &saved) { auto t = saved.begin(); return {*t++, {*t++, *t++, *t++}, *t++, *t++}; }
+    // the Gaussians as the rasterizer reads them: the rest comes from `in` inside the kernels
+    Gaussians gaussians() const { return {dc, rest, xyz, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()}; }
+};
+
 class RenderFreeFn : public torch::autograd::Function<RenderFreeFn> {
 public:
     static variable_list forward(AutogradContext *ctx, Tensor xyz_, Tensor scaling_, Tensor rotation_, Tensor opacity_, Tensor sh_dc, Tensor sh_rest,
                                  Tensor means2D, Tensor bg, Tensor view, Tensor proj, Tensor campos, int64_t H, int64_t W, double tanx, double tany,
                                  double mod, bool aa, bool debug, int64_t sh_degree, double eps_s0, bool will_backward)
     {
-        ctx->set_materialize_grads(false);
         TORCH_CHECK(sh_degree >= 0 && sh_degree <= 3, "render_free: active SH degree ", sh_degree, " (storage is degree 3: 0 .. 3)");
         require_gpu(xyz_); require_gpu(sh_dc); require_gpu(sh_rest);
         TORCH_CHECK(xyz_.dim() == 2 && xyz_.size(1) == 3, "render_free: _xyz must have dimensions (P, 3)");
@@ -1062,39 +1076,29 @@ public:
         check_split_sh("render_free", sh_dc, sh_rest);
         const auto dev = xyz_.device();
         c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
-        Tensor xyz = f32c(xyz_), dc = f32c(sh_dc), rest = f32c(sh_rest);
-        auto fopt = torch::TensorOptions().dtype(torch::kFloat).device(dev);
-        const Gaussians g{dc, rest, xyz, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-        if (will_backward) stash_backward(ctx, alloc_backward(g, true));      // (see Backward)
+        const FreeFrameSaved k{f32c(xyz_), in, f32c(sh_dc), f32c(sh_rest)};
+        const Gaussians g = k.gaussians();
         const GmsFreeArgs fa = free_args_of(in, eps_s0);
-        Tensor visible = torch::empty({P}, fopt.dtype(torch::kBool));          // radii > 0, written by the preprocess kernel
-        const FrameSettings s = frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, sh_degree, false, aa, debug);
-        Forward f = forward_core(s, P, dev, g, visible, true, nullptr, nullptr, will_backward, nullptr, &fa);
-        if (will_backward) {
-            save_frame(ctx, {xyz, in.scaling, in.rotation, in.opacity, dc, rest}, s, f);
-            ctx->saved_data["eps_s0"] = eps_s0;
-        }
-        ctx->mark_non_differentiable({f.radii, visible});
-        return {f.color, f.radii, f.invdepth, visible};
+        Forward f = frame_forward(ctx, frame_settings(dev, bg, view, proj, campos, H, W, tanx, tany, mod, sh_degree, false, aa, debug), P, dev, g,
+                                  FrameSource::free(fa), {true, will_backward}, {will_backward, g, k.pack()});
+        ctx->saved_data["eps_s0"] = eps_s0;
+        ctx->mark_non_differentiable({f.radii, f.visible});
+        return {f.color, f.radii, f.invdepth, f.visible};
     }
 
     static variable_list backward(AutogradContext *ctx, variable_list grads)
     {
         auto saved = ctx->get_saved_variables();
-        const Tensor &xyz = saved[0];
-        const FreeIn in{saved[1], saved[2], saved[3]};
-        const Gaussians g{saved[4], saved[5], xyz, Tensor(), Tensor(), Tensor(), Tensor(), Tensor()};
-        auto [s, f] = load_frame(ctx, saved);
-        const auto dev = xyz.device();
-        c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dev);
-        Tensor gcol = grads[0].defined() ? grads[0] : torch::zeros({3, s.H, s.W}, xyz.options());
-        std::optional<Backward> pre = take_backward(ctx);
-        redeem_counts(ctx, s, f, xyz);
+        const FreeFrameSaved k = FreeFrameSaved::unpack(saved);
+        c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(k.xyz.device());
         // the getters' backward in the tail of preprocess_bwd (preprocess_bwd_kernel<false, FreeTail>): plain stores, so deterministic mode
         // and the factorised SH mode take it as well
-        const FreeGrads fg{torch::empty_like(in.scaling), torch::empty_like(in.rotation), torch::empty_like(in.opacity)};
-        const GmsFreeArgs fa = free_args_of(in, ctx->saved_data["eps_s0"].toDouble());
-        Backward b = backward_core(s, g, f, gcol, grads[2], pre ? &*pre : nullptr, nullptr, nullptr, &fa, &fg);
+        FreeGrads fg; GmsFreeArgs fa;
+        Backward b = frame_backward(ctx, saved, grads, k.gaussians(), [&] {
+            fg = FreeGrads{torch::empty_like(k.in.scaling), torch::empty_like(k.in.rotation), torch::empty_like(k.in.opacity)};
+            fa = free_args_of(k.in, ctx->saved_data["eps_s0"].toDouble());
+            return BackwardTail::free(fa, fg);
+        });
         Tensor none;
         return {b.dmeans3D, fg.d_scaling, fg.d_rotation, fg.d_opacity, b.dsh, b.dsh_rest, b.dmeans2D,
                 none, none, none, none, none, none, none, none, none, none, none, none, none, none};
@@ -1106,11 +1110,8 @@ std::vector<Tensor> render_free(const Tensor &xyz, const Tensor &_scaling, const
                                 const Tensor &campos, int64_t H, int64_t W, double tanx, double tany, double mod, bool aa, bool debug,
                                 int64_t sh_degree, double eps_s0)
 {
-    const bool will_backward = at::GradMode::is_enabled() &&
-        (xyz.requires_grad() || _scaling.requires_grad() || _rotation.requires_grad() || _opacity.requires_grad() || sh_dc.requires_grad() ||
-         sh_rest.requires_grad() || means2D.requires_grad());
     return RenderFreeFn::apply(xyz, _scaling, _rotation, _opacity, sh_dc, sh_rest, means2D, bg, view, proj, campos, H, W, tanx, tany, mod, aa,
-                               debug, sh_degree, eps_s0, will_backward);
+                               debug, sh_degree, eps_s0, will_backward(xyz, _scaling, _rotation, _opacity, sh_dc, sh_rest, means2D));
 }
 
 // ---------------------------------------------------------------------------------------------- fused L1 + SSIM
@@ -1138,7 +1139,7 @@ public:
         }
         GmsLossArgs a{(int32_t)planes, (int32_t)h, (int32_t)w, cf(x), cf(y), (float)w_l1, (float)w_ssim, (float)bias};
         check_rc(gms_l1_ssim_forward(&a, mf(dmaps), mf(partials), mf(out), stream_of(x)), "gms_l1_ssim_forward");
-        ctx->save_for_backward({x, y, dmaps.defined() ? dmaps : torch::empty({0}, fopt)});
+        ctx->save_for_backward({x, y, keep_opt(dmaps, fopt)});
         ctx->saved_data["w_l1"] = w_l1; ctx->saved_data["w_ssim"] = w_ssim; ctx->saved_data["bias"] = bias;
         Tensor value = out.select(0, 0), stats = out.narrow(0, 1, 2);
         ctx->mark_non_differentiable({stats});
@@ -1147,8 +1148,8 @@ public:
 
     static variable_list backward(AutogradContext *ctx, variable_list g)
     {
-        auto s = ctx->get_saved_variables();
-        const Tensor &x = s[0], &y = s[1], &dmaps = s[2];
+        auto s = ctx->get_saved_variables(); auto t = s.begin();
+        const Tensor &x = *t++, &y = *t++, &dmaps = *t++;
         Tensor none;
         if (!g[0].defined()) return {none, none, none, none, none, none};          // (the value was not used)
         TORCH_CHECK(dmaps.numel() > 0, "l1_ssim backward called but the forward ran without requires_grad");
@@ -1166,7 +1167,7 @@ public:
 
 std::vector<Tensor> l1_ssim(const Tensor &img, const Tensor &gt, double w_l1, double w_ssim, double bias)
 {
-    return L1SsimFn::apply(img, gt, w_l1, w_ssim, bias, at::GradMode::is_enabled() && img.requires_grad());
+    return L1SsimFn::apply(img, gt, w_l1, w_ssim, bias, will_backward(img));
 }
 
 // ---------------------------------------------------------------------------------------------- evaluation sums (csrc/metrics.hip)
@@ -1553,8 +1554,7 @@ public:
         variable_list keep(in.rots.begin(), in.rots.end());
         auto fopt = out.options();
         keep.push_back(in.shape); keep.push_back(in.expression);
-        keep.push_back(in.transl.defined() ? in.transl : torch::empty({0}, fopt));
-        keep.push_back(in.enlargement.defined() ? in.enlargement : torch::empty({0}, fopt));
+        keep.push_back(keep_opt(in.transl, fopt)); keep.push_back(keep_opt(in.enlargement, fopt));
         keep.push_back(saved);
         for (const Tensor &t : in.tables) keep.push_back(t);
         ctx->save_for_backward(keep);
@@ -1575,8 +1575,7 @@ public:
         FlameInputs in;
         in.rots.assign(s.begin(), s.begin() + nr);
         in.shape = s[nr]; in.expression = s[nr + 1];
-        if (s[nr + 2].numel()) in.transl = s[nr + 2];
-        if (s[nr + 3].numel()) in.enlargement = s[nr + 3];
+        in.transl = kept_opt(s[nr + 2]); in.enlargement = kept_opt(s[nr + 3]);
         const Tensor &saved = s[nr + 4];
         in.tables.assign(s.begin() + nr + 5, s.end());
         in.parents = ctx->saved_data["parents"].toIntVector();
@@ -1776,12 +1775,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("mark_visible", &mark_visible, nogil());
     m.def("rasterize", &rasterize, "differentiable rasterization (autograd node in C++)", nogil());
     m.def("mesh_to_gaussians", &mesh_to_gaussians, "differentiable mesh-face -> Gaussian parameterization", nogil());
-    m.def("render_mesh_forward", &render_mesh_forward, "forward-only frame straight from a mesh (K0 inside the preprocess thread)", nogil());
-    m.def("render_mesh_forward_local_sh", &render_mesh_forward_local_sh, "render_mesh_forward with SH evaluated on the pose-local direction: + rest_rotation [P,4]", nogil());
+    m.def("render_mesh_forward", plain_entry(&mesh_forward_frame, "render_mesh_forward"), "forward-only frame straight from a mesh (K0 inside the preprocess thread)", nogil());
+    m.def("render_mesh_forward_local_sh", local_sh_entry(&mesh_forward_frame, "render_mesh_forward_local_sh"), "render_mesh_forward with SH evaluated on the pose-local direction: + rest_rotation [P,4]", nogil());
     m.def("points_to_gaussians", &points_to_gaussians, "differentiable pseudo-triangle -> Gaussian: [xyz, scaling_raw, rotation_raw, scaling_act, rotation_unit(, opacity_act)]", nogil());
     m.def("points_prepare_vertices", &points_prepare_vertices, "Gaussian -> pseudo-triangle [P,3,3] (prepare_vertices)", nogil());
-    m.def("render_points_forward", &render_points_forward, "forward-only frame straight from pseudo-triangles (the points op inside the preprocess thread)", nogil());
-    m.def("render_points_forward_local_sh", &render_points_forward_local_sh, "render_points_forward with SH evaluated on the pose-local direction: + rest_rotation [P,4]", nogil());
+    m.def("render_points_forward", plain_entry(&points_forward_frame, "render_points_forward"), "forward-only frame straight from pseudo-triangles (the points op inside the preprocess thread)", nogil());
+    m.def("render_points_forward_local_sh", local_sh_entry(&points_forward_frame, "render_points_forward_local_sh"), "render_points_forward with SH evaluated on the pose-local direction: + rest_rotation [P,4]", nogil());
     m.def("bind_pseudomesh", &bind_pseudomesh, "bind pseudo-triangles [P,3,3] to the nearest faces of a guide mesh: (face_idx int32 [P], alpha [P,3,3], n_degenerate)", nogil());
     m.def("bind_apply", &bind_apply, "pseudo-triangles [P,3,3] of a binding on (edited) guide vertices; launches only", py::arg("face_idx"), py::arg("alpha"),
           py::arg("guide_vertices"), py::arg("guide_faces"), py::arg("out") = py::none(), nogil());
@@ -1827,12 +1826,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
     m.def("take_sh_factors", &take_sh_factors, py::arg("device") = -1);
     m.def("sh_grad_expand", &sh_grad_expand, "dsh (+)= sum_v Y(dir_v) (x) factor_v over the [V,P+1,3] factors", nogil());
     m.def("last_stats", &last_stats);
-    m.def("set_deferred_counts", &set_deferred_counts, "read the frame's instance count back at the start of the backward instead of inside the forward (opt-in)");
-    m.def("deferred_counts", &deferred_counts);
-    m.def("set_fused_mesh_backward", &set_fused_mesh_backward, "frames rendered straight from a mesh: run the mesh backward inside preprocess_bwd (default on)");
-    m.def("fused_mesh_backward", &fused_mesh_backward);
-    m.def("set_fused_mesh_backward_runs", &set_fused_mesh_backward_runs, "... for more than four splats per face and CSR tables (the segmented reduction; default on)");
-    m.def("fused_mesh_backward_runs", &fused_mesh_backward_runs);
+    m.def("set_deferred_counts", [](bool on) { g_defer_counts.set(on); }, "read the frame's instance count back at the start of the backward instead of inside the forward (opt-in)");
+    m.def("deferred_counts", []() { return g_defer_counts.get(); });
+    m.def("set_fused_mesh_backward", [](bool on) { g_fused_mesh_bwd.set(on); }, "frames rendered straight from a mesh: run the mesh backward inside preprocess_bwd (default on)");
+    m.def("fused_mesh_backward", []() { return g_fused_mesh_bwd.get(); });
+    m.def("set_fused_mesh_backward_runs", [](bool on) { g_fused_mesh_bwd_runs.set(on); }, "... for more than four splats per face and CSR tables (the segmented reduction; default on)");
+    m.def("fused_mesh_backward_runs", []() { return g_fused_mesh_bwd_runs.get(); });
     m.def("set_capacity", &set_capacity);
     m.def("clear_capacity", &clear_capacity);
     m.def("abi_version", []() { return (int64_t)gms_abi_version(); });

@@ -45,6 +45,12 @@ except ImportError as _e:          # not built (make -C csrc) or disabled: the c
         raise
     _C = None
 
+
+def extension(entry: str):
+    """The `_C` extension module if it is built, enabled and has `entry`, else None: the callers' other route (ctypes, torch) serves."""
+    return _C if _C is not None and hasattr(_C, entry) else None
+
+
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "last_stats", "SplitSH", "keep_buffers",
            "set_capacity_hint", "clear_capacity_hints"]
 

@@ -27,7 +27,7 @@ _ATTRS = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_ro
 
 def _ext():
     import diff_gaussian_rasterization as dgr
-    return dgr._C if dgr._C is not None and hasattr(dgr._C, "densify_apply") else None
+    return dgr.extension("densify_apply")
 
 
 def _f32c(t):

@@ -154,7 +154,7 @@ class FlameData:
 # ---------------------------------------------------------------------------------------------------- the two routes to the C ABI
 def _ext():
     import diff_gaussian_rasterization as dgr
-    return dgr._C if dgr._C is not None and hasattr(dgr._C, "flame_vertices") else None
+    return dgr.extension("flame_vertices")
 
 
 def _c_structs(tables, parents, rots, rot_joints, shape, expression, transl, enlargement, enlargement_scalar, swap):

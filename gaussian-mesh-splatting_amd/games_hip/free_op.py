@@ -15,10 +15,11 @@ EPS_S0 = 1e-8          # FlatGaussianModel.eps_s0
 
 def _C():
     import diff_gaussian_rasterization as dgr
-    if dgr._C is None or not hasattr(dgr._C, "free_to_gaussians"):
+    ext = dgr.extension("free_to_gaussians")
+    if ext is None:
         raise RuntimeError("the free-model ops need the diff_gaussian_rasterization._C extension module (build it: "
                            "`make -C gaussian-mesh-splatting_amd/csrc`)")
-    return dgr._C
+    return ext
 
 
 def free_to_gaussians(_scaling: torch.Tensor, _rotation: torch.Tensor, _opacity: torch.Tensor, eps_s0: float = EPS_S0):

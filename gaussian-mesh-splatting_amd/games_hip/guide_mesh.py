@@ -49,7 +49,7 @@ class DensityGrid:
 
 def _ext():
     import diff_gaussian_rasterization as dgr
-    return dgr._C if dgr._C is not None and hasattr(dgr._C, "surface_nets") else None
+    return dgr.extension("surface_nets")
 
 
 def _f32(x) -> float:

@@ -15,10 +15,11 @@ EPS_S0 = 1e-8          # PointsGaussianModel.eps_s0
 
 def _C():
     import diff_gaussian_rasterization as dgr
-    if dgr._C is None or not hasattr(dgr._C, "points_to_gaussians"):
+    ext = dgr.extension("points_to_gaussians")
+    if ext is None:
         raise RuntimeError("the gs_points ops need the diff_gaussian_rasterization._C extension module (build it: "
                            "`make -C gaussian-mesh-splatting_amd/csrc`)")
-    return dgr._C
+    return ext
 
 
 def points_to_gaussians(triangles: torch.Tensor, _opacity: torch.Tensor = None, eps: float = 1e-8, eps_s0: float = EPS_S0):

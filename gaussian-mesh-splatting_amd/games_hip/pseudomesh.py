@@ -47,7 +47,7 @@ class PseudomeshBinding:
 
 def _ext():
     import diff_gaussian_rasterization as dgr
-    return dgr._C if dgr._C is not None and hasattr(dgr._C, "bind_apply") else None
+    return dgr.extension("bind_apply")
 
 
 def guide_faces_int32(faces, device) -> torch.Tensor:

@@ -91,11 +91,19 @@ class _View:
 def _native_route(entry, knob, pc, pipe, override_color) -> bool:
     """What the three fused routes share: the extension has `entry`, the environment does not set `knob` to 0, nothing python-side
     is requested (the rasterizer's native SH / cov3D stages), split degree-3 SH STORAGE, contiguous."""
-    if (dgr._C is None or not hasattr(dgr._C, entry) or os.environ.get(knob, "1") == "0"
+    if (dgr.extension(entry) is None or os.environ.get(knob, "1") == "0"
             or override_color is not None or pipe.compute_cov3D_python or pipe.convert_SHs_python):
         return False
     fr, dc = getattr(pc, "_features_rest", None), getattr(pc, "_features_dc", None)
     return torch.is_tensor(fr) and fr.dim() == 3 and fr.shape[1] == 15 and fr.is_contiguous() and torch.is_tensor(dc) and dc.is_contiguous()
+
+
+def _camera_args(viewpoint_camera, pipe, bg_color, scaling_modifier):
+    """The eleven camera / frame arguments of every `_C.render_*` entry, in their order: bg, view, proj, campos, H, W, tanx, tany, mod,
+    aa, debug."""
+    return (bg_color, viewpoint_camera.world_view_transform, viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center,
+            int(viewpoint_camera.image_height), int(viewpoint_camera.image_width), math.tan(viewpoint_camera.FoVx * 0.5),
+            math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing), bool(pipe.debug))
 
 
 def _kernel_opacity_current(pc) -> bool:
@@ -137,13 +145,11 @@ def _render_training_frame_from_mesh(viewpoint_camera, pc, pipe, bg_color, scali
     if faces.dtype != torch.int64 or not faces.is_contiguous():
         faces = faces.long().contiguous()
     screenspace_points = _zero_points(_alpha.device, (int(_scale.numel()), 3))
-    H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
     image, radii, invdepth, xyz, scaling_act, rotation_unit, opacity_act, visible = dgr._C.render_mesh(
         vertices, faces, _alpha, _scale, pc._opacity, pc._features_dc, pc._features_rest, screenspace_points,
-        ALPHA_MODES[getattr(pc, "alpha_mode", "relu")], spf, dgr._empty(_alpha.device) if splat_face is None else splat_face, bg_color,
-        viewpoint_camera.world_view_transform, viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W,
-        math.tan(viewpoint_camera.FoVx * 0.5), math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing),
-        bool(pipe.debug), int(pc.active_sh_degree),          # (the ACTIVE degree: train.py:86-87 raises it every 1 000 iterations)
+        ALPHA_MODES[getattr(pc, "alpha_mode", "relu")], spf, dgr._empty(_alpha.device) if splat_face is None else splat_face,
+        *_camera_args(viewpoint_camera, pipe, bg_color, scaling_modifier),
+        int(pc.active_sh_degree),          # (the ACTIVE degree: train.py:86-87 raises it every 1 000 iterations)
         face_splat_offset)
     pc._hip_fused_frame(xyz, scaling_act, rotation_unit, opacity_act)
     # (`visibility_filter` = radii > 0 comes out of the preprocess kernel, as on the two-node route: no elementwise launch)
@@ -181,10 +187,7 @@ def _render_free_frame(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, i
     followed by the rasterize node (tests/test_gpu_free_frame.py).  `inputs`: _free_frame_inputs()."""
     xyz, scaling, rotation, opacity, dc, rest, eps_s0 = inputs
     screenspace_points = _zero_points(xyz.device, xyz.shape, xyz.dtype)
-    H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
-    args = (xyz, scaling, rotation, opacity, dc, rest, screenspace_points, bg_color, viewpoint_camera.world_view_transform,
-            viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W, math.tan(viewpoint_camera.FoVx * 0.5),
-            math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing), bool(pipe.debug),
+    args = (xyz, scaling, rotation, opacity, dc, rest, screenspace_points, *_camera_args(viewpoint_camera, pipe, bg_color, scaling_modifier),
             int(pc.active_sh_degree), eps_s0)
     if pipe.debug:      # as the two-node route (diff_gaussian_rasterization.rasterize_gaussians): a failing forward leaves its inputs behind
         snapshot = dgr._cpu_copy(args)
@@ -282,7 +285,6 @@ def render_mesh_frame(vertices: torch.Tensor, faces: torch.Tensor, viewpoint_cam
     against the others, say; `faces` is then ignored (the model's concatenated faces and splat table are used).
     `rest_rotation` ([P,4], games_hip.local_sh.rest_rotation_of): the SH rows are evaluated on the direction taken back into the pose
     the coefficients were learned in (gms_rasterize_forward_local_sh); None: the frame as ever."""
-    H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
     if isinstance(vertices, (list, tuple)):
         with torch.no_grad():
             _, faces, _alpha, _scale, spf, splat_face, _ = pc._hip_frame_inputs()
@@ -291,21 +293,15 @@ def render_mesh_frame(vertices: torch.Tensor, faces: torch.Tensor, viewpoint_cam
             raise RuntimeError("render_mesh_frame: the per-mesh vertices do not have the model's vertex counts")
     else:
         _alpha, _scale, spf, splat_face = pc._alpha, getattr(pc, getattr(pc, "_hip_scale_attr", "_scale")), int(pc._alpha.shape[1]), None
+    args = (vertices.float(), faces, _alpha, _scale, pc._opacity, ALPHA_MODES[getattr(pc, "alpha_mode", "relu")], spf,
+            dgr._empty(vertices.device) if splat_face is None else splat_face, pc._features_dc, pc._features_rest,
+            *_camera_args(viewpoint_camera, pipe, bg_color, scaling_modifier))
     if rest_rotation is not None:
         from .local_sh import prepared_rest_rotation
         rest = prepared_rest_rotation(rest_rotation, int(_scale.numel()), vertices.device)
-        color, radii, invdepth, visible = dgr._C.render_mesh_forward_local_sh(
-            vertices.float(), faces, _alpha, _scale, pc._opacity, ALPHA_MODES[getattr(pc, "alpha_mode", "relu")], spf,
-            dgr._empty(vertices.device) if splat_face is None else splat_face, pc._features_dc, pc._features_rest, bg_color,
-            viewpoint_camera.world_view_transform, viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W,
-            math.tan(viewpoint_camera.FoVx * 0.5), math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing),
-            bool(pipe.debug), rest.q)
-        return {"render": color, "viewspace_points": None, "visibility_filter": visible, "radii": radii, "depth": invdepth}
-    color, radii, invdepth, visible = dgr._C.render_mesh_forward(
-        vertices.float(), faces, _alpha, _scale, pc._opacity, ALPHA_MODES[getattr(pc, "alpha_mode", "relu")], spf,
-        dgr._empty(vertices.device) if splat_face is None else splat_face, pc._features_dc, pc._features_rest, bg_color, viewpoint_camera.world_view_transform,
-        viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W, math.tan(viewpoint_camera.FoVx * 0.5),
-        math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing), bool(pipe.debug))
+        color, radii, invdepth, visible = dgr._C.render_mesh_forward_local_sh(*args, rest.q)
+    else:
+        color, radii, invdepth, visible = dgr._C.render_mesh_forward(*args)
     return {"render": color, "viewspace_points": None, "visibility_filter": visible, "radii": radii, "depth": invdepth}
 
 
@@ -353,21 +349,14 @@ def render_points_frame(triangles: torch.Tensor, viewpoint_camera, pc, pipe, bg_
     rasterizer on its outputs; callers check `_points_frame_ok`.  As with `render_mesh_frame`, `pc._scaling` / `pc._rotation` keep the
     values of the last prepare_scaling_rot() and `viewspace_points` is None.  `rest_rotation` ([P,4]): pose-local SH, as in
     `render_mesh_frame`; None: the frame as ever."""
-    H, W = int(viewpoint_camera.image_height), int(viewpoint_camera.image_width)
+    args = (triangles, pc._opacity, pc._features_dc, pc._features_rest, *_camera_args(viewpoint_camera, pipe, bg_color, scaling_modifier),
+            int(pc.active_sh_degree), float(eps), float(getattr(pc, "eps_s0", 1e-8)))
     if rest_rotation is not None:
         from .local_sh import prepared_rest_rotation
         rest = prepared_rest_rotation(rest_rotation, int(triangles.shape[0]), triangles.device)
-        color, radii, invdepth, visible = dgr._C.render_points_forward_local_sh(
-            triangles, pc._opacity, pc._features_dc, pc._features_rest, bg_color, viewpoint_camera.world_view_transform,
-            viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W, math.tan(viewpoint_camera.FoVx * 0.5),
-            math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing), bool(pipe.debug), int(pc.active_sh_degree),
-            float(eps), float(getattr(pc, "eps_s0", 1e-8)), rest.q)
-        return {"render": color, "viewspace_points": None, "visibility_filter": visible, "radii": radii, "depth": invdepth}
-    color, radii, invdepth, visible = dgr._C.render_points_forward(
-        triangles, pc._opacity, pc._features_dc, pc._features_rest, bg_color, viewpoint_camera.world_view_transform,
-        viewpoint_camera.full_proj_transform, viewpoint_camera.camera_center, H, W, math.tan(viewpoint_camera.FoVx * 0.5),
-        math.tan(viewpoint_camera.FoVy * 0.5), float(scaling_modifier), bool(pipe.antialiasing), bool(pipe.debug), int(pc.active_sh_degree),
-        float(eps), float(getattr(pc, "eps_s0", 1e-8)))
+        color, radii, invdepth, visible = dgr._C.render_points_forward_local_sh(*args, rest.q)
+    else:
+        color, radii, invdepth, visible = dgr._C.render_points_forward(*args)
     return {"render": color, "viewspace_points": None, "visibility_filter": visible, "radii": radii, "depth": invdepth}
 
 
