@@ -71,4 +71,13 @@ void grid_build(int N, const float *points, KnnHeader *hd, size_t max_cells, con
 // another point set binned into the cells of the grid `hd` already describes (points outside its box land in the clamped cell)
 void grid_bin(int N, const float *points, const KnnHeader *hd, size_t max_cells, const GridBins &b, hipStream_t stream);
 
+// ---- the node grid of guide_mesh.hip and grid_components.hip: a GmsGridSpec as the kernels take it
+struct Grid {
+    int n[3];
+    float origin[3], h;
+    __host__ __device__ int64_t nodes() const { return (int64_t)n[0] * n[1] * n[2]; }
+};
+// the limits of GmsGridSpec (guide_mesh.hip); false with the sizes in gms_last_error, `who` naming the entry point
+bool grid_ok(const GmsGridSpec *s, const char *who, Grid &G);
+
 }  // namespace gms

@@ -38,12 +38,6 @@ constexpr float FIELD_SCALE = 4294967296.0f;                 // 1 / quantum
 constexpr int BIG_BOX = 16384;                               // nodes: 64 blocks of 256 threads take one node each
 constexpr int BIG_BLOCKS_PER_BOX = BIG_BOX / BLOCK, BIG_ROWS = 256;
 
-struct Grid {
-    int n[3];
-    float origin[3], h;
-    __host__ __device__ int64_t nodes() const { return (int64_t)n[0] * n[1] * n[2]; }
-};
-
 // the Gaussian as the field reads it
 struct FieldGaussian {
     float mu[3], R[9], inv_sigma[3], ext[3], o;
@@ -313,7 +307,7 @@ __global__ void __launch_bounds__(BLOCK) surface_nets_faces_kernel(Grid G, const
     else             { o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[0]; o[4] = q[2]; o[5] = q[3]; }
 }
 
-static bool grid_ok(const GmsGridSpec *s, const char *who, Grid &G)
+bool grid_ok(const GmsGridSpec *s, const char *who, Grid &G)
 {
     if (!s) { set_error("%s: grid is NULL", who); return false; }
     for (int k = 0; k < 3; k++)

@@ -223,6 +223,7 @@ EXPORTS = (
     "gms_points_prepare_vertices", "gms_points_to_gaussians_forward", "gms_points_to_gaussians_backward",
     "gms_bind_workspace_bytes", "gms_bind_pseudomesh", "gms_bind_apply",
     "gms_density_grid_workspace_bytes", "gms_density_bounds", "gms_density_grid", "gms_surface_nets_count", "gms_surface_nets_emit",
+    "gms_grid_components_workspace_bytes", "gms_grid_components", "gms_grid_clean",
     "gms_flame_workspace_bytes", "gms_flame_forward", "gms_flame_backward",
     "gms_densify_stats", "gms_densify_plan_workspace_bytes", "gms_densify_plan", "gms_densify_apply",
     "gms_image_metrics_workspace_bytes", "gms_image_metrics",
@@ -313,6 +314,13 @@ def load():
         lib.gms_surface_nets_emit.restype = C.c_int32
         lib.gms_surface_nets_emit.argtypes = [C.POINTER(GridSpec), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                               C.c_void_p, C.c_void_p]
+        lib.gms_grid_components_workspace_bytes.restype = C.c_size_t
+        lib.gms_grid_components_workspace_bytes.argtypes = [C.POINTER(GridSpec)]
+        lib.gms_grid_components.restype = C.c_int32
+        lib.gms_grid_components.argtypes = [C.POINTER(GridSpec), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.gms_grid_clean.restype = C.c_int32
+        lib.gms_grid_clean.argtypes = [C.POINTER(GridSpec), C.c_void_p, C.c_float, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.c_void_p]
         lib.gms_flame_workspace_bytes.restype = C.c_size_t
         lib.gms_flame_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         lib.gms_flame_forward.restype = C.c_int32

@@ -3,7 +3,7 @@ package itself, and so are LPIPS (games_hip.lpips) and the guide-mesh estimate (
 so `import games_hip` stays as cheap as it was."""
 _EVALUATE = ("MetricTable", "metrics_from_rows", "evaluate_views", "training_report", "render_set", "write_png")
 _LPIPS = ("LpipsVgg", "lpips", "lpips_rows")
-_GUIDE_MESH = ("DensityGrid", "density_grid", "surface_nets", "estimate_guide_mesh", "create_dummy_mesh")
+_GUIDE_MESH = ("DensityGrid", "density_grid", "surface_nets", "grid_components", "clean_grid", "estimate_guide_mesh", "create_dummy_mesh")
 __all__ = list(_EVALUATE) + list(_LPIPS) + list(_GUIDE_MESH)
 
 

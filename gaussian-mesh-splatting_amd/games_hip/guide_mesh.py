@@ -4,7 +4,10 @@ takes in the reference's pseudo-mesh workflow, between save_pseudomesh_info and 
 The reference takes the alpha shape of the pseudo-triangles' corners (open3d, a Delaunay triangulation on the host).  Here the mesh
 is the iso-surface of a density field of the Gaussians on a regular grid, extracted with surface nets: closed, consistently oriented
 (normals point away from the splats), one vertex per cell the surface crosses, so `resolution` decides how coarse -- how editable -- it
-is.  Like the alpha shape it is a thin shell around a surface of flat splats, with an inner and an outer wall; both are kept.
+is.  Like the alpha shape it is a thin shell around a surface of flat splats, with an inner and an outer wall, and every floater adds a
+stray closed surface.  `fill_cavities` and `min_component_nodes` / `keep_largest` repair both in the field (clean_grid): the inner wall
+bounds a cavity -- outside nodes that cannot reach the grid's border -- and a floater is a small component of inside nodes.  A shell
+with a hole has no cavity and keeps both walls.
 
     triangles = save_pseudomesh_info(gaussians, out_dir)                  # [P,3,3]
     vertices, faces = estimate_guide_mesh(triangles, resolution=128)      # float32 [V,3], int32 [F,3] on the GPU
@@ -13,6 +16,8 @@ is.  Like the alpha shape it is a thin shell around a surface of flat splats, wi
 
     density_grid(means, scales, rotations, opacities)   the field: every Gaussian adds o max(exp(-d2/2) - e0, 0) / (1 - e0) to the nodes
                                                         of its 3-sigma box, each scale floored at min_sigma_voxels voxels
+    grid_components(grid, level)                        labels and sizes of the connected components of the grid's nodes
+    clean_grid(grid, level, fill_cavities=...)          the field with small inside components removed and cavities filled
     surface_nets(grid, level)                           the surface where the field crosses `level`
 
 The field is summed in 64-bit fixed point, so it -- and the mesh -- is the same bit for bit from run to run and for any order of the
@@ -49,7 +54,7 @@ class DensityGrid:
 
 def _ext():
     import diff_gaussian_rasterization as dgr
-    return dgr.extension("surface_nets")
+    return dgr.extension("_grid_components")          # (private names there: the module's public surface is recorded and stays)
 
 
 def _f32(x) -> float:
@@ -130,6 +135,41 @@ def _surface_nets_ctypes(n, origin, voxel, values, level):
     return vertices, faces
 
 
+def _components_ctypes(n, origin, voxel, values, level):
+    from diff_gaussian_rasterization import _lib
+    lib = _lib.load()
+    dev = values.device
+    spec = _spec(n, origin, voxel)
+    labels = torch.empty(n[2], n[1], n[0], dtype=torch.int32, device=dev)
+    sizes = torch.empty(n[2], n[1], n[0], dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        nbytes = lib.gms_grid_components_workspace_bytes(C.byref(spec))
+        if not nbytes:
+            _lib.check(-1, "gms_grid_components_workspace_bytes")
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rc = lib.gms_grid_components(C.byref(spec), _lib.ptr(values), level, _lib.ptr(labels), _lib.ptr(sizes), _lib.ptr(work), nbytes,
+                                     C.c_void_p(_lib.stream_ptr(dev)))
+    _lib.check(rc, "gms_grid_components")
+    return labels, sizes
+
+
+def _clean_ctypes(n, origin, voxel, values, level, fill_cavities, min_component_nodes, keep_largest):
+    from diff_gaussian_rasterization import _lib
+    lib = _lib.load()
+    dev = values.device
+    spec = _spec(n, origin, voxel)
+    out = torch.empty(n[2], n[1], n[0], dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        nbytes = lib.gms_grid_components_workspace_bytes(C.byref(spec))
+        if not nbytes:
+            _lib.check(-1, "gms_grid_components_workspace_bytes")
+        work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        rc = lib.gms_grid_clean(C.byref(spec), _lib.ptr(values), level, int(fill_cavities), min_component_nodes, int(keep_largest), _lib.ptr(out),
+                                _lib.ptr(work), nbytes, C.c_void_p(_lib.stream_ptr(dev)))
+    _lib.check(rc, "gms_grid_clean")
+    return out
+
+
 @torch.no_grad()
 def density_grid(means, scales, rotations, opacities=None, *, resolution: int = 128, bounds=None, min_sigma_voxels: float = 1.0,
                  pad: int = None) -> DensityGrid:
@@ -190,13 +230,8 @@ def density_grid(means, scales, rotations, opacities=None, *, resolution: int = 
     return DensityGrid(values, origin, voxel)
 
 
-@torch.no_grad()
-def surface_nets(grid: DensityGrid, level: float = 0.5):
-    """The surface where `grid` crosses `level`, by surface nets: (vertices float32 [V,3] in world coordinates, faces int32 [F,3]), on
-    the grid's device.  A node is inside iff values >= level and it is not on the grid's outermost layer, so the mesh is closed; faces
-    are wound so that normals point from inside to outside.  Vertices come in cell order, faces in (edge axis, node) order: the same
-    arrays from run to run.  No surface: V = F = 0.  One host wait (the two counts that size the outputs)."""
-    who = "surface_nets"
+def _grid_arguments(who, grid, level):
+    """(values float32 contiguous, n, origin, voxel, level) of a DensityGrid on a GPU, checked"""
     if not isinstance(grid, DensityGrid):
         raise TypeError(f"{who}: grid must be a DensityGrid")
     values = _device_tensor(who, "grid.values", grid.values, "(n2, n1, n0) with at least 3 nodes per axis", lambda t: t.dim() == 3 and min(t.shape) >= 3)
@@ -208,10 +243,58 @@ def surface_nets(grid: DensityGrid, level: float = 0.5):
         raise ValueError(f"{who}: grid.origin must hold three values and grid.voxel must be positive and finite")
     if not math.isfinite(level):
         raise ValueError(f"{who}: level must be finite, not {level!r}")
+    return values, n, origin, voxel, float(level)
+
+
+def _cleaning_arguments(who, fill_cavities, min_component_nodes, keep_largest):
+    if isinstance(min_component_nodes, bool) or int(min_component_nodes) != min_component_nodes or not 0 <= min_component_nodes < MAX_NODES:
+        raise ValueError(f"{who}: min_component_nodes must be an integer in [0, 2^31), not {min_component_nodes!r}")
+    return bool(fill_cavities), int(min_component_nodes), bool(keep_largest)
+
+
+@torch.no_grad()
+def surface_nets(grid: DensityGrid, level: float = 0.5):
+    """The surface where `grid` crosses `level`, by surface nets: (vertices float32 [V,3] in world coordinates, faces int32 [F,3]), on
+    the grid's device.  A node is inside iff values >= level and it is not on the grid's outermost layer, so the mesh is closed; faces
+    are wound so that normals point from inside to outside.  Vertices come in cell order, faces in (edge axis, node) order: the same
+    arrays from run to run.  No surface: V = F = 0.  One host wait (the two counts that size the outputs)."""
+    values, n, origin, voxel, level = _grid_arguments("surface_nets", grid, level)
     ext = _ext()
     if ext is not None:
-        return tuple(ext.surface_nets(list(n), list(origin), voxel, values, float(level)))
-    return _surface_nets_ctypes(n, origin, voxel, values, float(level))
+        return tuple(ext.surface_nets(list(n), list(origin), voxel, values, level))
+    return _surface_nets_ctypes(n, origin, voxel, values, level)
+
+
+@torch.no_grad()
+def grid_components(grid: DensityGrid, level: float = 0.5):
+    """The connected components of the grid's nodes: (labels, sizes), int32 [n2, n1, n0] on the grid's device.  A node is inside iff
+    values >= level and it is not on the outermost layer (surface_nets' rule); two nodes are joined iff they share a grid edge and lie
+    on the same side.  labels = the smallest linear index (k n1 + j) n0 + i of the node's component, so the exterior is the component
+    0 and a cavity node is an outside node with another label; sizes.reshape(-1)[r] = the nodes of the component labelled r, 0 where r
+    is no label.  The same arrays from run to run.  No host wait."""
+    values, n, origin, voxel, level = _grid_arguments("grid_components", grid, level)
+    ext = _ext()
+    if ext is not None:
+        return tuple(ext._grid_components(list(n), list(origin), voxel, values, level))
+    return _components_ctypes(n, origin, voxel, values, level)
+
+
+@torch.no_grad()
+def clean_grid(grid: DensityGrid, level: float = 0.5, *, fill_cavities: bool = True, min_component_nodes: int = 0, keep_largest: bool = False) -> DensityGrid:
+    """A new grid whose surface at `level` has no floaters and no inner wall; `grid` is not modified.  Two steps, in this order:
+    every inside component is removed (its nodes become the float32 just below `level`) unless it has at least `min_component_nodes`
+    nodes and, with `keep_largest`, is the largest one (a tie: the smallest label); then, on that result, every cavity node becomes
+    `level`, if `fill_cavities`.  All other nodes keep their bits, and no rewritten node has a sign-changing edge, so surface_nets sees
+    only crossings of the original field.  A shell with a hole has no cavity: it keeps both walls.  No host wait."""
+    who = "clean_grid"
+    values, n, origin, voxel, level = _grid_arguments(who, grid, level)
+    fill_cavities, min_component_nodes, keep_largest = _cleaning_arguments(who, fill_cavities, min_component_nodes, keep_largest)
+    ext = _ext()
+    if ext is not None:
+        out = ext._clean_grid(list(n), list(origin), voxel, values, level, fill_cavities, min_component_nodes, keep_largest)
+    else:
+        out = _clean_ctypes(n, origin, voxel, values, level, fill_cavities, min_component_nodes, keep_largest)
+    return DensityGrid(out, origin, voxel)
 
 
 def _gaussians_of(source, opacities, who):
@@ -231,27 +314,36 @@ def _gaussians_of(source, opacities, who):
 
 
 @torch.no_grad()
-def estimate_guide_mesh(source, *, resolution: int = 128, level: float = 0.5, bounds=None, min_sigma_voxels: float = 1.0, opacities=None):
+def estimate_guide_mesh(source, *, resolution: int = 128, level: float = 0.5, bounds=None, min_sigma_voxels: float = 1.0, opacities=None,
+                        fill_cavities: bool = False, min_component_nodes: int = 0, keep_largest: bool = False):
     """A closed guide mesh around the splats of `source`: pseudo-triangles [P,3,3] (through points_op.points_to_gaussians; opacity 1
     unless `opacities` gives activated ones) or a model with get_xyz / get_scaling / get_rotation / get_opacity (gs_flat, gs,
     gs_points, gs_mesh).  Returns (vertices float32 [V,3], faces int32 [F,3]) on the GPU, as bind_pseudomesh and io_mesh.save_obj take
-    them.  Two host waits (the box, the counts); one with `bounds`."""
-    means, scales, rotations, op = _gaussians_of(source, opacities, "estimate_guide_mesh")
+    them.  With `fill_cavities`, `min_component_nodes` or `keep_largest` the field goes through clean_grid first: one wall instead of a
+    shell, no floaters.  Two host waits (the box, the counts); one with `bounds`; cleaning adds none."""
+    who = "estimate_guide_mesh"
+    fill_cavities, min_component_nodes, keep_largest = _cleaning_arguments(who, fill_cavities, min_component_nodes, keep_largest)
+    means, scales, rotations, op = _gaussians_of(source, opacities, who)
     grid = density_grid(means, scales, rotations, op, resolution=resolution, bounds=bounds, min_sigma_voxels=min_sigma_voxels)
+    if fill_cavities or min_component_nodes or keep_largest:
+        grid = clean_grid(grid, level, fill_cavities=fill_cavities, min_component_nodes=min_component_nodes, keep_largest=keep_largest)
     return surface_nets(grid, level)
 
 
 @torch.no_grad()
-def create_dummy_mesh(pseudomesh, save_dir, scale=2, resolution: int = 128, level: float = 0.5, device="cuda") -> io_mesh.TriMesh:
+def create_dummy_mesh(pseudomesh, save_dir, scale=2, resolution: int = 128, level: float = 0.5, device="cuda", *, fill_cavities: bool = False,
+                      min_component_nodes: int = 0, keep_largest: bool = False) -> io_mesh.TriMesh:
     """scripts/create_dummy_mesh.py: `pseudomesh` is the `triangles.pt` save_pseudomesh_info wrote (its path, or the directory that
     holds it) or the triangles [P,3,3] themselves.  Writes `{save_dir}/dummy_mesh_scale_{scale}.obj`, the vertices multiplied by `scale`
-    as the reference's are, and returns the mesh in model coordinates (vertices float64 [V,3], faces int64 [F,3])."""
+    as the reference's are, and returns the mesh in model coordinates (vertices float64 [V,3], faces int64 [F,3]).  The three cleaning
+    arguments are estimate_guide_mesh's."""
     if not torch.is_tensor(pseudomesh):
         path = os.fspath(pseudomesh)
         if os.path.isdir(path):
             path = os.path.join(path, "triangles.pt")
         pseudomesh = torch.load(path, map_location="cpu")
-    vertices, faces = estimate_guide_mesh(pseudomesh.to(device=device, dtype=torch.float32), resolution=resolution, level=level)
+    vertices, faces = estimate_guide_mesh(pseudomesh.to(device=device, dtype=torch.float32), resolution=resolution, level=level,
+                                          fill_cavities=fill_cavities, min_component_nodes=min_component_nodes, keep_largest=keep_largest)
     os.makedirs(save_dir, exist_ok=True)
     io_mesh.save_obj(os.path.join(save_dir, f"dummy_mesh_scale_{scale}.obj"), vertices * scale, faces)
     return io_mesh.TriMesh(vertices.cpu().numpy().astype(np.float64), faces.cpu().numpy().astype(np.int64))

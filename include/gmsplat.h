@@ -486,6 +486,38 @@ int32_t gms_surface_nets_emit(const GmsGridSpec *grid, const float *values, floa
                               const int32_t *scan /* [4 N] */, int32_t V, int32_t F, float *vertices_out /* [V,3] */,
                               int32_t *faces_out /* [F,3] */, void *stream);
 
+/* ---- connected components of a grid; cavities filled, small components dropped (csrc/grid_components.hip; additive to ABI 10) ----
+ * What makes the guide mesh above editable: around a surface of flat splats the field's iso-surface is a shell with an inner wall,
+ * and every floater adds a stray closed surface.  Both are statements about the components of the grid's nodes, and are repaired
+ * in the field, so gms_surface_nets_* run unchanged on the result.  No GMS_K_* profile id here either: GMS_K_COUNT stays 23.
+ * Grids are GmsGridSpec's, refused as above.  N = n[0] n[1] n[2].
+ *
+ * A node is inside iff it is off the outermost layer and values >= level (the rule of gms_surface_nets_count: NaN is outside).
+ * Two nodes are joined iff they share a grid edge and lie on the same side; inside and outside components are labelled together.
+ *
+ * gms_grid_components: labels_out [N] int32 = the smallest array index among the nodes of the node's component, so the exterior
+ * (it holds the outermost layer, and node 0) has label 0, and a cavity node is an outside node with another label.  sizes_out
+ * [N] int32 or NULL: the number of nodes of the component whose label is the index, 0 at every index that is no label.  Integer
+ * atomics only: the same bits from call to call.  `level` may be infinite, not NaN.
+ *
+ * gms_grid_clean: values_out [N] float32 (it may be `values` itself, else the two do not overlap) = values after
+ *   1. every inside component is removed -- its nodes written nextafterf(level, -inf) -- unless it has at least
+ *      min_component_nodes (>= 0) nodes and, with keep_largest, is the largest inside component (a tie: the smallest label);
+ *   2. on the result of 1, labelled again, every cavity node is written `level`, if fill_cavities.
+ * (A removed component that touched the exterior opens its own cavities; one that lay in a cavity is covered by the fill.)
+ * Every other node keeps its bits; with all three switches off values_out is a copy.  No rewritten node has a sign-changing
+ * edge afterwards.  `level` must be finite.
+ *
+ * Both launch only: no allocation, no host wait.  `workspace`: gms_grid_components_workspace_bytes(grid) bytes of device scratch
+ * (0: the grid is invalid), less is GMS_ERR_CAPACITY; gms_grid_clean keeps its labels and sizes there, gms_grid_components labels
+ * in labels_out and takes the same size for both. */
+size_t gms_grid_components_workspace_bytes(const GmsGridSpec *grid);
+int32_t gms_grid_components(const GmsGridSpec *grid, const float *values /* [n2,n1,n0] */, float level, int32_t *labels_out /* [N] */,
+                            int32_t *sizes_out /* [N] or NULL */, void *workspace, size_t workspace_bytes, void *stream);
+int32_t gms_grid_clean(const GmsGridSpec *grid, const float *values /* [n2,n1,n0] */, float level, int32_t fill_cavities,
+                       int64_t min_component_nodes, int32_t keep_largest, float *values_out /* [n2,n1,n0] */, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
 /* ---- fused L1 + SSIM photometric loss ---------------------------------
  * Replaces train.py:106-107 built on utils/loss_utils.py:17-18 (l1_loss) and :33-63 (ssim: 11x11 Gaussian window,
  * sigma 1.5, zero padding, C1=0.01^2, C2=0.03^2, mean over every pixel of every plane):
