@@ -180,23 +180,16 @@ using namespace gms;
 
 // workspace: [degenerate counter + grid header | face centroids | query centroids | face bins | query bins]
 struct BindWorkspace {
-    uint32_t *degenerate; KnnHeader *hd; float *fcent, *qcent; GridBins fb, qb; size_t mc, bytes;
-    BindWorkspace(void *base, int64_t P, int32_t F)
-    {
-        const size_t p = (size_t)(P > 0 ? P : 1), f = (size_t)(F > 0 ? F : 1);
-        mc = grid_max_cells(F);
-        char *w = (char *)base;
-        degenerate = (uint32_t *)w;           w += 256;
-        hd = (KnnHeader *)w;                  w += 256;
-        fcent = (float *)w;                   w += align_up(f * 12, 256);
-        qcent = (float *)w;                   w += align_up(p * 12, 256);
-        fb = GridBins::carve(w, mc, f);       w += GridBins::bytes(mc, f);
-        qb = GridBins::carve(w, mc, p);       w += GridBins::bytes(mc, p);
-        bytes = (size_t)(w - (char *)base);
-    }
+    Carver c; int64_t P; int32_t F;
+    size_t p = (size_t)(P > 0 ? P : 1), f = (size_t)(F > 0 ? F : 1), mc = grid_max_cells(F);
+    uint32_t *degenerate = c.take<uint32_t>(1);
+    KnnHeader *hd = c.take<KnnHeader>(1);
+    float *fcent = c.take<float>(3 * f), *qcent = c.take<float>(3 * p);
+    GridBins fb = GridBins::layout(c, mc, f), qb = GridBins::layout(c, mc, p);
+    size_t bytes = c.offset;
 };
 
-extern "C" size_t gms_bind_workspace_bytes(int64_t P, int32_t F) { return BindWorkspace(nullptr, P, F).bytes; }
+extern "C" size_t gms_bind_workspace_bytes(int64_t P, int32_t F) { return BindWorkspace{nullptr, P, F}.bytes; }
 
 extern "C" int32_t gms_bind_pseudomesh(int64_t P, const float *triangles, int32_t V, const float *guide_vertices, int32_t F,
                                        const int32_t *guide_faces, int32_t *face_idx_out, float *alpha_out, int32_t *degenerate_count_out,
@@ -215,7 +208,7 @@ extern "C" int32_t gms_bind_pseudomesh(int64_t P, const float *triangles, int32_
         return GMS_ERR_INVALID_ARGUMENT;
     }
     if (workspace_bytes < gms_bind_workspace_bytes(P, F)) { set_error("gms_bind_pseudomesh: workspace too small"); return GMS_ERR_CAPACITY; }
-    const BindWorkspace w(workspace, P, F);
+    const BindWorkspace w{workspace, P, F};
     const unsigned nbp = (unsigned)((P + BLOCK - 1) / BLOCK), nbf = (unsigned)((F + BLOCK - 1) / BLOCK);
     GMS_HIP_CHECK(hipMemsetAsync(w.degenerate, 0, 4, stream));
     bind_centroid_kernel<<<nbf, BLOCK, 0, stream>>>(F, nullptr, guide_vertices, guide_faces, w.fcent);

@@ -242,22 +242,17 @@ extern "C" int32_t gms_densify_stats(int64_t P, const int32_t *radii, const floa
 
 // workspace: [totals | flags [P] | per-block counts, then offsets, [blocks,3]]
 struct DensifyWorkspace {
-    uint32_t *totals; uint8_t *flags; uint32_t *block_counts; size_t blocks, bytes;
-    DensifyWorkspace(void *base, int64_t P)
-    {
-        const size_t p = (size_t)(P > 0 ? P : 1);
-        blocks = (p + BLOCK - 1) / BLOCK;
-        char *w = (char *)base;
-        totals = (uint32_t *)w;           w += 256;
-        flags = (uint8_t *)w;             w += align_up(p, 256);
-        block_counts = (uint32_t *)w;     w += align_up(blocks * 12, 256);
-        bytes = (size_t)(w - (char *)base);
-    }
+    Carver c; int64_t P;
+    size_t p = (size_t)(P > 0 ? P : 1), blocks = (p + BLOCK - 1) / BLOCK;
+    uint32_t *totals = c.take<uint32_t>(3);
+    uint8_t *flags = c.take<uint8_t>(p);
+    uint32_t *block_counts = c.take<uint32_t>(blocks * 3);
+    size_t bytes = c.offset;
 };
 
 constexpr int64_t DENSIFY_MAX_P = (int64_t)1 << 30;       // 2 P rows of output stay inside int32 / uint32 counts
 
-extern "C" size_t gms_densify_plan_workspace_bytes(int64_t P) { return DensifyWorkspace(nullptr, P).bytes; }
+extern "C" size_t gms_densify_plan_workspace_bytes(int64_t P) { return DensifyWorkspace{nullptr, P}.bytes; }
 
 extern "C" int32_t gms_densify_plan(int64_t P, int32_t S, const float *xyz_gradient_accum, const float *denom, const float *opacity,
                                     const float *scaling, float grad_threshold, float dense_threshold, float min_opacity, int32_t prune_world,
@@ -281,7 +276,7 @@ extern "C" int32_t gms_densify_plan(int64_t P, int32_t S, const float *xyz_gradi
         return GMS_ERR_INVALID_ARGUMENT;
     }
     if (workspace_bytes < gms_densify_plan_workspace_bytes(P)) { set_error("gms_densify_plan: workspace too small"); return GMS_ERR_CAPACITY; }
-    const DensifyWorkspace w(workspace, P);
+    const DensifyWorkspace w{workspace, P};
     const DensifyPlanArgs a{P, S, xyz_gradient_accum, denom, opacity, scaling, grad_threshold, dense_threshold, min_opacity, world_threshold, eps_s0,
                             prune_world ? 1 : 0};
     densify_decide_kernel<<<(unsigned)w.blocks, BLOCK, 0, stream>>>(a, w.flags, w.block_counts);

@@ -366,13 +366,13 @@ static int32_t flame_validate(const char *what, const GmsFlameModel *m, const Gm
 
 using namespace gms;
 
-extern "C" size_t gms_flame_workspace_bytes(int32_t V, int32_t J, int32_t L)
-{
-    if (V < 0) V = 0;
-    if (J < 2) J = 2;
-    if (L < 0) L = 0;
-    return align_up((size_t)(flame_blocks(V) > 0 ? flame_blocks(V) : 1) * flame_row_floats(J, L) * 4, 256);
-}
+struct FlameWorkspace {      // of gms_flame_backward: a row of partial parameter gradients per block of flame_bwd_vertices
+    Carver c; int32_t V, J, L;
+    float *partials = c.take<float>((size_t)max(flame_blocks(max(V, 0)), 1) * flame_row_floats(max(J, 2), max(L, 0)));
+    size_t bytes = c.offset;
+};
+
+extern "C" size_t gms_flame_workspace_bytes(int32_t V, int32_t J, int32_t L) { return FlameWorkspace{nullptr, V, J, L}.bytes; }
 
 extern "C" int32_t gms_flame_forward(const GmsFlameModel *model, const GmsFlameParams *params, float *vertices_out, float *saved_out, void *stream_)
 {
@@ -400,9 +400,10 @@ extern "C" int32_t gms_flame_backward(const GmsFlameModel *model, const GmsFlame
     if (!saved || !dL_dvertices || !workspace) { set_error("gms_flame_backward: null pointer"); return GMS_ERR_INVALID_ARGUMENT; }
     if (workspace_bytes < gms_flame_workspace_bytes(model->V, model->J, model->L)) { set_error("gms_flame_backward: workspace too small"); return GMS_ERR_CAPACITY; }
     const int nblk = flame_blocks(model->V);
+    float *const partials = FlameWorkspace{workspace, model->V, model->J, model->L}.partials;
     flame_bwd_vertices_kernel<<<nblk, WAVE, 0, stream>>>(*model, *params, saved, dL_dvertices, params->enlargement ? grads->d_enlargement : nullptr,
-                                                         (float *)workspace);
-    flame_bwd_params_kernel<<<1, FL_PARAM_BLOCK, 0, stream>>>(*model, *params, saved, (const float *)workspace, nblk, *grads);
+                                                         partials);
+    flame_bwd_params_kernel<<<1, FL_PARAM_BLOCK, 0, stream>>>(*model, *params, saved, partials, nblk, *grads);
     GMS_KERNEL_CHECK(0, stream, "flame_bwd");
     return GMS_OK;
 }

@@ -35,8 +35,26 @@ struct __attribute__((aligned(16))) SplatRec {
     float4 q0, q1, q2;
 };
 
-// ---- scratch buffer layouts (carved from the caller's three buffers, 256-B aligned chunks)
-__host__ __device__ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// ---- scratch buffer layouts
+// Every device scratch buffer is ONE caller-owned allocation that the library cuts into arrays, each starting on a 256-byte boundary.
+// A layout is stated once, as a walk over a Carver with one take<T>(n) per array in the order the arrays lie in the buffer: over the
+// buffer's address the walk yields the arrays' pointers, over a null base null pointers and, in `offset`, the bytes the buffer needs.
+// A size function and the code that cuts the buffer thus run the same statements; an array is added by adding its one take.  A layout
+// nested in another (GridBins, gms_grid.h) continues the outer walk.  The workspaces private to one file are structs whose members
+// take their arrays in their own initialisers (members are initialised in the order they are declared): W{workspace, sizes...} cuts,
+// W{nullptr, sizes...}.bytes sizes.  (images.hip, resize.hip: one array each at the 16-byte alignment of include/gmsplat.h.)
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+struct Carver {
+    char *base; size_t offset = 0;      // offset: bytes taken so far
+    Carver(void *b) : base((char *)b) {}
+    template <class T> T *take(size_t n)
+    {
+        T *p = base ? (T *)(base + offset) : nullptr;
+        offset += align_up(n * sizeof(T), 256);
+        return p;
+    }
+};
 
 struct GeomState {
     SplatRec *rec;      // [P]
@@ -49,22 +67,18 @@ struct GeomState {
                         //     preprocess_fwd for visible Gaussians of SH frames only (culled Gaussians and colors_precomp frames leave it
                         //     untouched); preprocess_bwd contracts it with dL/dcolour instead of reading the coefficient rows again
     static constexpr size_t SH_DDIR = 9;
-    static __host__ __device__ size_t bytes(size_t P)
-    {
-        return align_up(P * sizeof(SplatRec), 256) + align_up(P * 4, 256) + align_up(P, 256) + align_up(P * sizeof(ushort4), 256) +
-               align_up(P * SH_DDIR * 4, 256);
-    }
-    static __host__ __device__ GeomState carve(void *base, size_t P)
+    static GeomState layout(Carver &c, size_t P)
     {
         GeomState g;
-        char *p = (char *)base;
-        g.rec = (SplatRec *)p; p += align_up(P * sizeof(SplatRec), 256);
-        g.depth = (float *)p;  p += align_up(P * 4, 256);
-        g.clamped = (uint8_t *)p; p += align_up(P, 256);
-        g.rect = (ushort4 *)p; p += align_up(P * sizeof(ushort4), 256);
-        g.sh_ddir = (float *)p;
+        g.rec = c.take<SplatRec>(P);
+        g.depth = c.take<float>(P);
+        g.clamped = c.take<uint8_t>(P);
+        g.rect = c.take<ushort4>(P);
+        g.sh_ddir = c.take<float>(P * SH_DDIR);
         return g;
     }
+    static size_t bytes(size_t P) { Carver c(nullptr); layout(c, P); return c.offset; }
+    static GeomState carve(void *base, size_t P) { Carver c(base); return layout(c, P); }
 };
 
 struct ImageState {
@@ -84,30 +98,29 @@ struct ImageState {
                             //          the forward micro-tile launches that stage the tile's units): bounds the colour behind any splat in
                             //          the backward's fixed-point gradient table (blend_micro.hip)
     uint32_t *scan_out;     // [4]     {N, deepest tile, work units} of this frame, for the launch that publishes them to the host
-    static __host__ __device__ size_t bytes(size_t W, size_t H)
+    struct Published { size_t n_contrib, scan_out; };      // byte offsets the C ABI publishes (gms_image_n_contrib_offset, _counts_offset)
+    static ImageState layout(Carver &c, size_t W, size_t H, Published *at = nullptr)
     {
-        size_t T = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
-        return 2 * align_up(W * H * 4, 256) + 2 * align_up(T * 4, 256) + 3 * align_up((T + 1) * 4, 256) +
-               align_up(8 * (T + 1) * 4, 256) + 2 * align_up(T * 4, 256) + 256;
-    }
-    static __host__ __device__ ImageState carve(void *base, size_t W, size_t H)
-    {
-        size_t T = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
+        const size_t T = ((W + TILE - 1) / TILE) * ((H + TILE - 1) / TILE);
         ImageState s;
-        char *p = (char *)base;
-        s.final_T = (float *)p;        p += align_up(W * H * 4, 256);
-        s.n_contrib = (uint32_t *)p;   p += align_up(W * H * 4, 256);
-        s.tile_count = (uint32_t *)p;  p += align_up(T * 4, 256);
-        s.tile_cursor = (uint32_t *)p; p += align_up(T * 4, 256);
-        s.tile_offset = (uint32_t *)p; p += align_up((T + 1) * 4, 256);
-        s.unit_first = (uint32_t *)p;  p += align_up((T + 1) * 4, 256);
-        s.mseg_first = (uint32_t *)p;  p += align_up((T + 1) * 4, 256);
-        s.scan_rows = (uint32_t *)p;   p += align_up(8 * (T + 1) * 4, 256);
-        s.tile_dead = (uint32_t *)p;   p += align_up(T * 4, 256);
-        s.tile_cmax = (uint32_t *)p;   p += align_up(T * 4, 256);
-        s.scan_out = (uint32_t *)p;
+        s.final_T = c.take<float>(W * H);
+        if (at) at->n_contrib = c.offset;
+        s.n_contrib = c.take<uint32_t>(W * H);
+        s.tile_count = c.take<uint32_t>(T);
+        s.tile_cursor = c.take<uint32_t>(T);
+        s.tile_offset = c.take<uint32_t>(T + 1);
+        s.unit_first = c.take<uint32_t>(T + 1);
+        s.mseg_first = c.take<uint32_t>(T + 1);
+        s.scan_rows = c.take<uint32_t>(8 * (T + 1));
+        s.tile_dead = c.take<uint32_t>(T);
+        s.tile_cmax = c.take<uint32_t>(T);
+        if (at) at->scan_out = c.offset;
+        s.scan_out = c.take<uint32_t>(4);
         return s;
     }
+    static size_t bytes(size_t W, size_t H) { Carver c(nullptr); layout(c, W, H); return c.offset; }
+    static Published published(size_t W, size_t H) { Carver c(nullptr); Published at; layout(c, W, H, &at); return at; }
+    static ImageState carve(void *base, size_t W, size_t H) { Carver c(base); return layout(c, W, H); }
 };
 
 // Binning buffer: sorted keys, unit table and per-(unit, pixel) segment state.  Sized from the
@@ -132,30 +145,25 @@ struct BinningState {
     static __host__ __device__ size_t n_deep(size_t N, size_t T) { return N / 1024 + T + 2; }
     static __host__ __device__ size_t n_multi(size_t N) { return N / 1024 + 2; }
     static __host__ __device__ size_t n_order(size_t N, size_t T, size_t L) { return (n_units(N, T, L) + 511) / 512 * 512; }      // (the blend launches' grid: gms_blend.h, blend_grid_units)
-    static __host__ __device__ size_t order_bytes(size_t N, size_t T, size_t L, bool micro)
-    {
-        return micro ? align_up(n_units(N, T, L) * 2, 256) + align_up(n_order(N, T, L) * 4, 256) : 0;
-    }
-    static __host__ __device__ size_t bytes(size_t N, size_t T, size_t L, bool micro)
-    {
-        return align_up((N > 0 ? N : 1) * 8, 256) + align_up(n_units(N, T, L) * 32, 256) +
-               align_up(n_slots(N, L) * 7 * TILE_PIX * 4, 256) + align_up(n_deep(N, T) * 8, 256) + align_up(n_multi(N) * 4, 256) +
-               (micro ? align_up((N > 0 ? N : 1) * 2, 256) : 0);
-    }
-    static __host__ __device__ BinningState carve(void *base, size_t N, size_t T, size_t L)
+    struct Ends { size_t tables, mmask; };      // offsets reached before and after `mmask`: a buffer without the micro arrays ends at `tables`
+    static BinningState layout(Carver &c, size_t N, size_t T, size_t L, Ends *ends = nullptr)
     {
         BinningState b;
-        char *p = (char *)base;
-        b.keys = (uint64_t *)p;      p += align_up((N > 0 ? N : 1) * 8, 256);
-        b.unit_tile = (uint4 *)p;    p += align_up(n_units(N, T, L) * 32, 256);
-        b.seg_state = (float *)p;    p += align_up(n_slots(N, L) * 7 * TILE_PIX * 4, 256);
-        b.deep_tab = (uint2 *)p;     p += align_up(n_deep(N, T) * 8, 256);
-        b.multi_tab = (uint32_t *)p; p += align_up(n_multi(N) * 4, 256);
-        b.mmask = (uint16_t *)p;     p += align_up((N > 0 ? N : 1) * 2, 256);      // (this and what follows: present only in micro mode)
-        b.unit_cost = (uint16_t *)p; p += align_up(n_units(N, T, L) * 2, 256);
-        b.bwd_order = (uint32_t *)p;
+        b.keys = c.take<uint64_t>(N > 0 ? N : 1);
+        b.unit_tile = c.take<uint4>(2 * n_units(N, T, L));
+        b.seg_state = c.take<float>(n_slots(N, L) * 7 * TILE_PIX);
+        b.deep_tab = c.take<uint2>(n_deep(N, T));
+        b.multi_tab = c.take<uint32_t>(n_multi(N));
+        if (ends) ends->tables = c.offset;
+        b.mmask = c.take<uint16_t>(N > 0 ? N : 1);
+        if (ends) ends->mmask = c.offset;
+        b.unit_cost = c.take<uint16_t>(n_units(N, T, L));
+        b.bwd_order = c.take<uint32_t>(n_order(N, T, L));
         return b;
     }
+    static size_t bytes(size_t N, size_t T, size_t L, bool micro) { Carver c(nullptr); Ends e; layout(c, N, T, L, &e); return micro ? e.mmask : e.tables; }
+    static size_t order_bytes(size_t N, size_t T, size_t L, bool micro) { Carver c(nullptr); Ends e; layout(c, N, T, L, &e); return micro ? c.offset - e.mmask : 0; }
+    static BinningState carve(void *base, size_t N, size_t T, size_t L) { Carver c(base); return layout(c, N, T, L); }
 };
 
 // inclusive scan over the first WIDTH lanes of a wave (shuffles; binning.hip's tile scans and the unit order of gms_blend.h)

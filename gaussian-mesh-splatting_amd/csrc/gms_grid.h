@@ -46,20 +46,16 @@ struct GridBins {
     uint32_t *cell_count, *cell_start, *cell_cursor;      // [max_cells + 1] each
     uint32_t *point_cell;                                 // [N]
     float4 *sorted;                                       // [N]
-    static size_t bytes(size_t max_cells, size_t N)
+    // always part of a workspace (knn.hip, bind.hip), whose walk it continues (gms_common.h: scratch buffer layouts)
+    static GridBins layout(Carver &c, size_t max_cells, size_t N)
     {
         N = N > 0 ? N : 1;
-        return align_up((max_cells + 1) * 4, 256) * 3 + align_up(N * 4, 256) + align_up(N * 16, 256);
-    }
-    static GridBins carve(void *base, size_t max_cells, size_t N)
-    {
         GridBins b;
-        char *w = (char *)base;
-        b.cell_count = (uint32_t *)w;         w += align_up((max_cells + 1) * 4, 256);
-        b.cell_start = (uint32_t *)w;         w += align_up((max_cells + 1) * 4, 256);
-        b.cell_cursor = (uint32_t *)w;        w += align_up((max_cells + 1) * 4, 256);
-        b.point_cell = (uint32_t *)w;         w += align_up((N > 0 ? N : 1) * 4, 256);
-        b.sorted = (float4 *)w;
+        b.cell_count = c.take<uint32_t>(max_cells + 1);
+        b.cell_start = c.take<uint32_t>(max_cells + 1);
+        b.cell_cursor = c.take<uint32_t>(max_cells + 1);
+        b.point_cell = c.take<uint32_t>(N);
+        b.sorted = c.take<float4>(N);
         return b;
     }
 };

@@ -250,11 +250,17 @@ static void component_sizes(int64_t N, const int32_t *labels, int32_t *sizes, hi
 using namespace gms;
 
 // workspace of gms_grid_clean: [the largest component's key | labels [N] int32 | sizes [N] int32]
+struct CleanWorkspace {
+    Carver c; int64_t N;
+    unsigned long long *best = c.take<unsigned long long>(1);
+    int32_t *labels = c.take<int32_t>((size_t)N), *sizes = c.take<int32_t>((size_t)N);
+    size_t bytes = c.offset;
+};
+
 extern "C" size_t gms_grid_components_workspace_bytes(const GmsGridSpec *grid)
 {
     Grid G;
-    if (!grid_ok(grid, "gms_grid_components_workspace_bytes", G)) return 0;
-    return 256 + 2 * align_up((size_t)G.nodes() * 4, 256);
+    return grid_ok(grid, "gms_grid_components_workspace_bytes", G) ? CleanWorkspace{nullptr, G.nodes()}.bytes : 0;
 }
 
 extern "C" int32_t gms_grid_components(const GmsGridSpec *grid, const float *values, float level, int32_t *labels_out, int32_t *sizes_out, void *workspace,
@@ -291,26 +297,23 @@ extern "C" int32_t gms_grid_clean(const GmsGridSpec *grid, const float *values, 
     if (min_component_nodes < 0) { set_error("gms_grid_clean: min_component_nodes is negative"); return GMS_ERR_INVALID_ARGUMENT; }
     if (workspace_bytes < gms_grid_components_workspace_bytes(grid)) { set_error("gms_grid_clean: workspace too small"); return GMS_ERR_CAPACITY; }
     const int64_t N = G.nodes();
-    char *w = (char *)workspace;
-    unsigned long long *best = (unsigned long long *)w;      w += 256;
-    int32_t *labels = (int32_t *)w;                          w += align_up((size_t)N * 4, 256);
-    int32_t *sizes = (int32_t *)w;
+    const CleanWorkspace w{workspace, N};
     // step 1: inside components that are not kept (every component has a node: a threshold of 0 or 1 removes nothing)
     if (min_component_nodes > 1 || keep_largest) {
-        label_components(G, values, level, labels, stream);
+        label_components(G, values, level, w.labels, stream);
         GMS_HIP_CHECK(hipMemsetAsync(workspace, 0, 256, stream));
-        GMS_HIP_CHECK(hipMemsetAsync(sizes, 0, (size_t)N * 4, stream));
-        component_sizes(N, labels, sizes, stream);
-        if (keep_largest) components_largest_kernel<<<node_blocks(N), BLOCK, 0, stream>>>(G, values, level, labels, sizes, best);
+        GMS_HIP_CHECK(hipMemsetAsync(w.sizes, 0, (size_t)N * 4, stream));
+        component_sizes(N, w.labels, w.sizes, stream);
+        if (keep_largest) components_largest_kernel<<<node_blocks(N), BLOCK, 0, stream>>>(G, values, level, w.labels, w.sizes, w.best);
         clean_remove_kernel<<<node_blocks(N), BLOCK, 0, stream>>>(G, values, level, nextafterf(level, -INFINITY), min_component_nodes, keep_largest ? 1 : 0,
-                                                                  labels, sizes, best, values_out);
+                                                                  w.labels, w.sizes, w.best, values_out);
     } else if (values_out != values) {
         GMS_HIP_CHECK(hipMemcpyAsync(values_out, values, (size_t)N * 4, hipMemcpyDeviceToDevice, stream));
     }
     // step 2, on the result of step 1 labelled again: a removed component may have opened a cavity to the exterior, or lie in one
     if (fill_cavities) {
-        label_components(G, values_out, level, labels, stream);
-        clean_fill_kernel<<<node_blocks(N), BLOCK, 0, stream>>>(G, level, labels, values_out);
+        label_components(G, values_out, level, w.labels, stream);
+        clean_fill_kernel<<<node_blocks(N), BLOCK, 0, stream>>>(G, level, w.labels, values_out);
     }
     GMS_KERNEL_CHECK(0, stream, "grid_clean");
     return GMS_OK;

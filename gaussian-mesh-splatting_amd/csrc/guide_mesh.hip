@@ -329,12 +329,20 @@ bool grid_ok(const GmsGridSpec *s, const char *who, Grid &G)
 
 using namespace gms;
 
-// workspace of gms_density_grid: [list counter | accumulators [N] uint64 | list [P] uint32]
+// workspace of gms_density_grid: [list counter | accumulators [N] uint64 | list [P] uint32]; the first `cleared` bytes start at zero
+struct DensityWorkspace {
+    Carver c; int64_t N, P;
+    uint32_t *big_count = c.take<uint32_t>(1);
+    unsigned long long *acc = c.take<unsigned long long>((size_t)N);
+    size_t cleared = c.offset;
+    uint32_t *big_list = c.take<uint32_t>((size_t)(P > 0 ? P : 1));
+    size_t bytes = c.offset;
+};
+
 extern "C" size_t gms_density_grid_workspace_bytes(const GmsGridSpec *grid, int64_t P)
 {
     Grid G;
-    if (!grid_ok(grid, "gms_density_grid_workspace_bytes", G) || P < 0) return 0;
-    return 256 + align_up((size_t)G.nodes() * 8, 256) + align_up((size_t)(P > 0 ? P : 1) * 4, 256);
+    return grid_ok(grid, "gms_density_grid_workspace_bytes", G) && P >= 0 ? DensityWorkspace{nullptr, G.nodes(), P}.bytes : 0;
 }
 
 extern "C" int32_t gms_density_bounds(int64_t P, const float *means, const float *scales, const float *rotations, float *bounds_out, void *workspace,
@@ -373,20 +381,17 @@ extern "C" int32_t gms_density_grid(const GmsGridSpec *grid, int64_t P, const fl
     if (!values_out || !workspace || (P > 0 && (!means || !scales || !rotations))) { set_error("gms_density_grid: null pointer"); return GMS_ERR_INVALID_ARGUMENT; }
     if (workspace_bytes < gms_density_grid_workspace_bytes(grid, P)) { set_error("gms_density_grid: workspace too small"); return GMS_ERR_CAPACITY; }
     const int64_t N = G.nodes();
-    char *w = (char *)workspace;
-    uint32_t *big_count = (uint32_t *)w;                        w += 256;
-    unsigned long long *acc = (unsigned long long *)w;          w += align_up((size_t)N * 8, 256);
-    uint32_t *big_list = (uint32_t *)w;
-    GMS_HIP_CHECK(hipMemsetAsync(workspace, 0, 256 + align_up((size_t)N * 8, 256), stream));
+    const DensityWorkspace w{workspace, N, P};
+    GMS_HIP_CHECK(hipMemsetAsync(workspace, 0, w.cleared, stream));
     if (P > 0) {
         const float sigma_floor = min_sigma_voxels * G.h;
         const int64_t nb = (P * WAVE + BLOCK - 1) / BLOCK;
         if (nb > 0x7fffffffll) { set_error("gms_density_grid: too many Gaussians for one launch"); return GMS_ERR_INVALID_ARGUMENT; }
-        density_splat_kernel<<<(unsigned)nb, BLOCK, 0, stream>>>(P, means, scales, rotations, opacities, G, sigma_floor, acc, big_list, big_count);
-        density_splat_big_kernel<<<dim3(BIG_BLOCKS_PER_BOX, BIG_ROWS), BLOCK, 0, stream>>>(means, scales, rotations, opacities, G, sigma_floor, acc, big_list,
-                                                                                          big_count);
+        density_splat_kernel<<<(unsigned)nb, BLOCK, 0, stream>>>(P, means, scales, rotations, opacities, G, sigma_floor, w.acc, w.big_list, w.big_count);
+        density_splat_big_kernel<<<dim3(BIG_BLOCKS_PER_BOX, BIG_ROWS), BLOCK, 0, stream>>>(means, scales, rotations, opacities, G, sigma_floor, w.acc, w.big_list,
+                                                                                          w.big_count);
     }
-    density_finalize_kernel<<<(unsigned)((N + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(G, acc, values_out);
+    density_finalize_kernel<<<(unsigned)((N + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(G, w.acc, values_out);
     GMS_KERNEL_CHECK(0, stream, "density_grid");
     return GMS_OK;
 }

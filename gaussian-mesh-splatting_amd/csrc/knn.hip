@@ -221,10 +221,15 @@ using namespace gms;
 
 static_assert(sizeof(KnnHeader) <= 256, "header slot");
 
-extern "C" size_t gms_knn_workspace_bytes(int32_t N)
-{
-    return 256 + GridBins::bytes(grid_max_cells(N), (size_t)(N > 0 ? N : 1));
-}
+struct KnnWorkspace {      // [grid header | the points' bins]
+    Carver c; int32_t N;
+    size_t mc = grid_max_cells(N);
+    KnnHeader *hd = c.take<KnnHeader>(1);
+    GridBins b = GridBins::layout(c, mc, (size_t)(N > 0 ? N : 1));
+    size_t bytes = c.offset;
+};
+
+extern "C" size_t gms_knn_workspace_bytes(int32_t N) { return KnnWorkspace{nullptr, N}.bytes; }
 
 extern "C" int32_t gms_knn_mean_dist2(int32_t N, const float *points, float *out, void *workspace, size_t workspace_bytes,
                                       void *stream_)
@@ -234,11 +239,9 @@ extern "C" int32_t gms_knn_mean_dist2(int32_t N, const float *points, float *out
     if (N < 0 || (N > 0 && (!points || !out || !workspace))) { set_error("gms_knn_mean_dist2: invalid argument"); return GMS_ERR_INVALID_ARGUMENT; }
     if (N == 0) return GMS_OK;
     if (workspace_bytes < gms_knn_workspace_bytes(N)) { set_error("gms_knn_mean_dist2: workspace too small"); return GMS_ERR_CAPACITY; }
-    const size_t mc = grid_max_cells(N);
-    KnnHeader *hd = (KnnHeader *)workspace;
-    const GridBins b = GridBins::carve((char *)workspace + 256, mc, (size_t)N);
-    grid_build(N, points, hd, mc, b, stream);
-    knn_query_kernel<<<(unsigned)((N + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(N, points, hd, b.cell_start, b.sorted, out);
+    const KnnWorkspace w{workspace, N};
+    grid_build(N, points, w.hd, w.mc, w.b, stream);
+    knn_query_kernel<<<(unsigned)((N + BLOCK - 1) / BLOCK), BLOCK, 0, stream>>>(N, points, w.hd, w.b.cell_start, w.b.sorted, out);
     GMS_KERNEL_CHECK(0, stream, "knn");
     return GMS_OK;
 }

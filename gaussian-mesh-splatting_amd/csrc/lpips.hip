@@ -282,8 +282,6 @@ static const int LP_CIN[LP_LAYERS] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 5
 static const int LP_COUT[LP_LAYERS] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
 static const int LP_LAST_OF_STAGE[LP_STAGES] = {1, 3, 6, 9, 12};       // relu1_2, 2_2, 3_3, 4_3, 5_3
 
-static size_t lp_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // floats of one ping-pong activation buffer: the first stage's maps are the largest (64 H W per image; 128 (H/2)(W/2) is half of it)
 static size_t lp_buffer_floats(int64_t pairs, int64_t H, int64_t W) { return (size_t)(2 * pairs) * 64 * (size_t)H * (size_t)W; }
 
@@ -298,11 +296,17 @@ static int lp_partials_per_pair(int32_t H, int32_t W, int *off /* [6] or null */
     return total;
 }
 
+struct LpipsWorkspace {      // [two ping-pong activation buffers | the stages' per-block partial sums, a row per pair]
+    Carver c; int32_t pairs, H, W;
+    float *buf[2] = {c.take<float>(lp_buffer_floats(pairs, H, W)), c.take<float>(lp_buffer_floats(pairs, H, W))};
+    float *partials = c.take<float>((size_t)pairs * lp_partials_per_pair(H, W, nullptr));
+    size_t bytes = c.offset;
+};
+
 extern "C" size_t gms_lpips_workspace_bytes(int32_t pairs, int32_t height, int32_t width)
 {
     if (pairs <= 0 || height <= 0 || width <= 0) return 256;
-    return 2 * lp_align(sizeof(float) * lp_buffer_floats(pairs, height, width)) +
-           lp_align(sizeof(float) * (size_t)pairs * lp_partials_per_pair(height, width, nullptr));
+    return LpipsWorkspace{nullptr, pairs, height, width}.bytes;
 }
 
 template <int MW>
@@ -363,9 +367,8 @@ extern "C" int32_t gms_lpips(const GmsLpipsWeights *w, const GmsLpipsArgs *a, vo
         set_error("gms_lpips: workspace too small (%zu bytes, %zu needed)", workspace_bytes, need);
         return GMS_ERR_CAPACITY;
     }
-    const size_t buf_bytes = lp_align(sizeof(float) * lp_buffer_floats(pairs, H, W));
-    float *buf[2] = {(float *)workspace, (float *)((char *)workspace + buf_bytes)};
-    float *partials = (float *)((char *)workspace + 2 * buf_bytes);
+    const LpipsWorkspace ws{workspace, pairs, H, W};
+    float *const *buf = ws.buf, *const partials = ws.partials;
     LpReduce red;
     const int stride = lp_partials_per_pair(H, W, red.off);
 

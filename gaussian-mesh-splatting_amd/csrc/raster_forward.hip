@@ -200,18 +200,8 @@ extern "C" int32_t gms_abi_version(void) { return GMS_ABI_VERSION; }
 extern "C" const char *gms_last_error(void) { return gms::g_err; }
 extern "C" size_t gms_geom_bytes(int32_t P) { return GeomState::bytes((size_t)(P > 0 ? P : 1)); }
 extern "C" size_t gms_image_bytes(int32_t w, int32_t h) { return ImageState::bytes((size_t)w, (size_t)h); }
-extern "C" size_t gms_image_n_contrib_offset(int32_t w, int32_t h)
-{
-    char *const base = reinterpret_cast<char *>(uintptr_t(1) << 20);
-    ImageState s = ImageState::carve(base, (size_t)w, (size_t)h);
-    return (size_t)(reinterpret_cast<char *>(s.n_contrib) - base);
-}
-extern "C" size_t gms_image_counts_offset(int32_t w, int32_t h)
-{
-    char *const base = reinterpret_cast<char *>(uintptr_t(1) << 20);
-    ImageState s = ImageState::carve(base, (size_t)w, (size_t)h);
-    return (size_t)(reinterpret_cast<char *>(s.scan_out) - base);
-}
+extern "C" size_t gms_image_n_contrib_offset(int32_t w, int32_t h) { return ImageState::published((size_t)w, (size_t)h).n_contrib; }
+extern "C" size_t gms_image_counts_offset(int32_t w, int32_t h) { return ImageState::published((size_t)w, (size_t)h).scan_out; }
 static FrameState *frame_state(const FrameKey &key)
 {
     std::vector<FrameState> &frames = t_state.frames;

@@ -179,8 +179,25 @@ def _carve(chunks):
     return at, p
 
 
+def geom_layout(P):
+    """GeomState of csrc/gms_common.h -> ({name: byte offset}, total bytes)"""
+    return _carve([("rec", P * 48), ("depth", P * 4), ("clamped", P), ("rect", P * 8), ("sh_ddir", P * 9 * 4)])
+
+
+def grid_bins_layout(max_cells, N):
+    """GridBins of csrc/gms_grid.h -> ({name: byte offset}, total bytes)"""
+    n1 = max(N, 1)
+    return _carve([("cell_count", (max_cells + 1) * 4), ("cell_start", (max_cells + 1) * 4), ("cell_cursor", (max_cells + 1) * 4),
+                   ("point_cell", n1 * 4), ("sorted", n1 * 16)])
+
+
+def knn_workspace_bytes(N):
+    """gms_knn_workspace_bytes: a 256-byte grid header, then the bins of N points in at most grid_max_cells(N) cells (csrc/knn.hip)"""
+    return 256 + grid_bins_layout(min(max(N, 1) // 2 + 64, 1 << 22), N)[1]
+
+
 def image_layout(W, H):
-    """ImageState::carve / ::bytes of csrc/gms_common.h -> ({name: byte offset}, total bytes)"""
+    """ImageState of csrc/gms_common.h -> ({name: byte offset}, total bytes)"""
     T = ((W + 15) // 16) * ((H + 15) // 16)
     at, end = _carve([("final_T", W * H * 4), ("n_contrib", W * H * 4), ("tile_count", T * 4), ("tile_cursor", T * 4),
                       ("tile_offset", (T + 1) * 4), ("unit_first", (T + 1) * 4), ("mseg_first", (T + 1) * 4), ("scan_rows", 8 * (T + 1) * 4),
@@ -190,7 +207,7 @@ def image_layout(W, H):
 
 
 def binning_layout(N, T, L, micro):
-    """BinningState::carve / ::bytes for a capacity of N instances, carved with segment length L -> ({name: byte offset}, total bytes)"""
+    """BinningState (csrc/gms_common.h) for a capacity of N instances, carved with segment length L -> ({name: byte offset}, total bytes)"""
     n1 = max(N, 1)
     return _carve([("keys", n1 * 8), ("units", (T + N // L + 1) * 32), ("seg_state", (2 * (N // L) + 2) * 7 * 256 * 4),
                    ("deep_tab", (N // 1024 + T + 2) * 8), ("multi_tab", (N // 1024 + 2) * 4)] + ([("mmask", n1 * 2)] if micro else []))
